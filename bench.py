@@ -14,12 +14,16 @@ N > 1  workload "graphslam" = configs[3]: 64 scans x 1M points on a closed loop,
        equations over RCCL, redundant solve, pose update.  Total work is fixed -> "strong".
        (--workload graphslam --gpus 1 gives the 1-GPU point of that curve.)
 
-Rank 0 prints ONE JSON line on stdout, at most 6 KB: the contract's keys + `roofline` + `cpu_baseline` + the key numbers of
-the other legs.  Everything else that was measured (the full headline record and every leg: tree_build_1gpu, normals_1gpu,
-doicp_small_scans, graphslam_1gpu, c5_shape_1gpu) goes to bench_legs.json beside this file and, one compact line per
-leg, to stderr.  What the fields mean is written down once, in DESIGN.md section 6 -- not in the record.
-Inputs are resident in HBM when the timed region starts; oracle/ is touched by the cpu_baseline legs only (whose first
-sample also serves as a parity spot-check of the GPU indices, outside the timed region).
+A plain N = 1 run sets up, warms up, times the K steps and prints ONE JSON line on stdout: the contract's keys (metric,
+value, unit, ms_per_step, ...) and what the timed loop itself returned (pairs / RMS of the last step, pose error).
+--full adds everything else, after the timed steps: the replays behind `roofline` (HIP events, visit counters), the
+`cpu_baseline`, the convergence check and the other legs (tree_build_1gpu, normals_1gpu, doicp_small_scans,
+graphslam_1gpu, c5_shape_1gpu).  Rank 0's line is at most 6 KB; with --full the full record goes to bench_legs.json
+beside this file and, one compact line per leg, to stderr.  What the fields mean is written down once, in DESIGN.md
+section 6 -- not in the record.
+--dump-outputs DIR writes what the timed loop computed (float64 .npy files, at most 64 MB together; see dump_outputs).
+Inputs are seeded and resident in HBM when the timed region starts; oracle/ is touched by the cpu_baseline legs only
+(whose first sample also serves as a parity spot-check of the GPU indices, outside the timed region).
 """
 import argparse
 import ctypes as C
@@ -47,6 +51,23 @@ PMC_ROUND = "r06"
 PMC_ROUND_C5 = "r06"
 LINE_MAX = 6144           # the driver parses the last stdout line; round 5's 21.7 KB line did not parse
 NUM_SIMD = 1024            # 256 CUs x 4 SIMDs
+DUMP_MAX_BYTES = 60 << 20  # --dump-outputs: array bytes of all files together (64 MB with room for the .npy headers)
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: every array as <outdir>/<name>.npy in float64.  When together they exceed DUMP_MAX_BYTES the
+    rows of the largest one are a fixed sample (seed 0, row indices in ascending order), so that two runs with the same
+    arguments -- two builds of the project -- write files that compare element for element."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        big = max(arrays, key=lambda k: arrays[k].nbytes)
+        a = arrays[big]
+        keep = max(1, (DUMP_MAX_BYTES - (total - a.nbytes)) // (a.nbytes // len(a)))
+        arrays[big] = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
 
 
 def pmc_file_for(steps, warmup):
@@ -522,6 +543,27 @@ def bench_icp(args, rank, world, local):
     assert steps == args.steps, (steps, args.steps)
     last = icp.last
     pose_err = float(np.abs(data.get_transMat() - T).max())
+    if args.dump_outputs and rank == 0:
+        # what a caller of icp6D::match receives: the data scan's pose (4x4, column-major as in the reference), its
+        # points where the loop left them, and the loop's trace (per iteration: pairs, RMS, alignxf; the last row is
+        # the last timed step)
+        dump_outputs(args.dump_outputs, {"transMat": data.get_transMat(), "dalignxf": data.dalignxf,
+                                         "trace": last["trace"], "points": data.get_xyz_reduced()})
+    out = {
+        "metric": "NN correspondences/sec (1M-vs-1M pairwise ICP, full iteration)",
+        "value": n * steps / dt, "unit": "NN correspondences/s",
+        "n_gpus": world, "steps": steps, "warmup": args.warmup, "ms_per_step": dt * 1e3 / steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "configs[1]: synthetic %d-vs-%d uniform pair, point-to-point ICP -a 1 -d 25 -b 20, 1xMI355X" % (n, n),
+                   "points": n, "bucket": 20, "max_dist_match": 25.0, "minimizer": "QUAT",
+                   "tree": {"internal": info["n_internal"], "leaves": info["n_leaves"], "depth": info["max_depth"]}},
+        "icp_iters_per_s": steps / dt,
+        "pairs_last": last["pairs"], "rms_last": last["rms"], "pose_max_abs_err": pose_err,
+        # for whoever reads a kernel trace of this command: the timed region is search launches [first, first + steps)
+        "search_launches_before_timed_region": max(1, args.warmup),
+    }
+    if not args.full:
+        return out
     # Device time of the timed launches.  The library's HIP events around its search and pair-sum launches are a
     # profiling switch that is off in the product (four marker packets, two waits and two read-outs cost ~10 us of an
     # iteration), so the timed region above ran without them; the same W + K iterations are run again on a second
@@ -598,24 +640,13 @@ def bench_icp(args, rank, world, local):
     convergence = {"further_iterations": more, "pose_max_abs_err": pose_err_converged, "rms": icp_f.last["rms"]}
     assert pose_err_converged < 2e-2, "ICP did not converge to the generating pose: %r" % (convergence,)
 
-    out = {
-        "metric": "NN correspondences/sec (1M-vs-1M pairwise ICP, full iteration)",
-        "value": n * steps / dt, "unit": "NN correspondences/s",
-        "n_gpus": world, "steps": steps, "warmup": args.warmup, "ms_per_step": dt * 1e3 / steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "configs[1]: synthetic %d-vs-%d uniform pair, point-to-point ICP -a 1 -d 25 -b 20, 1xMI355X" % (n, n),
-                   "points": n, "bucket": 20, "max_dist_match": 25.0, "minimizer": "QUAT",
-                   "tree": {"internal": info["n_internal"], "leaves": info["n_leaves"], "depth": info["max_depth"]},
-                   "tree_build_ms": info["build_ms"], "tree_upload_ms": info["upload_ms"]},
-        "icp_iters_per_s": steps / dt,
-        "pairs_last": last["pairs"], "rms_last": last["rms"], "pose_max_abs_err": pose_err, "convergence": convergence,
-        "host_buffer_path": host_path, "per_scan_preparation": prep,
+    out["config"].update(tree_build_ms=info["build_ms"], tree_upload_ms=info["upload_ms"])
+    out.update({
+        "convergence": convergence, "host_buffer_path": host_path, "per_scan_preparation": prep,
         "pair_sums_ms": sums_ms, "outside_kernels_ms": dt * 1e3 / steps - k_ms - sums_ms,
         "ms_per_step_with_kernel_events": dt_ev * 1e3 / steps,
-        # for whoever reads a kernel trace of this command: the timed region is search launches [first, first + steps)
-        "search_launches_before_timed_region": max(1, args.warmup),
         "roofline": roof,
-    }
+    })
     # tree build (A1) on the device, against the bytes its levels move: every level streams the 24-B points + 8 B of
     # permutation / keys in and out (64 B per point and level)
     levels = info["max_depth"]
@@ -665,7 +696,7 @@ def bench_icp(args, rank, world, local):
         # configs[3]); reported beside the headline so scaling can be read against the same workload
         del model, data, tree
         import copy
-        ga = copy.copy(args); ga.steps, ga.warmup = 10, 3
+        ga = copy.copy(args); ga.steps, ga.warmup, ga.dump_outputs = 10, 3, None    # (the headline wrote the dump)
         g1 = bench_graphslam(ga, rank, world, local)
         out["graphslam_1gpu"] = {k: g1[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "lum_iters_per_s", "roofline", "sharded_step_rehearsal")}
         out["graphslam_1gpu"]["workload"] = g1["config"]["workload"]
@@ -781,6 +812,9 @@ def bench_graphslam(args, rank, world, local):
     barrier_sync(world)
     dt = max_over_ranks(time.perf_counter() - t0, world, local)
     tdtk.lib().tdtk_kernel_timing(0)
+    if args.dump_outputs and rank == 0:
+        # what the last LUM iteration leaves a caller: every scan's pose (4x4, column-major) and the iteration's return value
+        dump_outputs(args.dump_outputs, {"transMat": np.stack([s.transMat for s in scans]), "ret": np.array([ret])})
     queries = links_done * npts                         # one whole-scan NN pass per link
     k_ms = nn_ms[0] / max(1, args.steps)                # one sampled k_search launch per step
     # algorithmic bytes of this rank's link passes: two more steps with the instrumented kernels (poses have converged to
@@ -1100,14 +1134,16 @@ def build_line(res):
     return text
 
 
-def emit(res):
-    """bench_legs.json (the full record), one compact line per leg on stderr, the ONE line on stdout (last)."""
-    full = json.dumps(res, allow_nan=False, indent=1, default=lambda o: o.item() if hasattr(o, "item") else str(o))
-    try:
-        with open(os.path.join(ROOT, "bench_legs.json"), "w") as f:
-            f.write(full + "\n")
-    except OSError as e:
-        print("bench.py: bench_legs.json not written: %s" % e, file=sys.stderr)
+def emit(res, record=True):
+    """bench_legs.json (the full record; not for a plain ICP run, whose line is its record), one compact line per leg on
+    stderr, the ONE line on stdout (last)."""
+    if record:
+        full = json.dumps(res, allow_nan=False, indent=1, default=lambda o: o.item() if hasattr(o, "item") else str(o))
+        try:
+            with open(os.path.join(ROOT, "bench_legs.json"), "w") as f:
+                f.write(full + "\n")
+        except OSError as e:
+            print("bench.py: bench_legs.json not written: %s" % e, file=sys.stderr)
     for k in LEG_KEYS:
         if res.get(k) is not None:
             print(json.dumps({"leg": k, **_sig(res[k], 5)}, separators=(",", ":"), default=lambda o: o.item() if hasattr(o, "item") else str(o)), file=sys.stderr)
@@ -1124,12 +1160,17 @@ def main():
     ap.add_argument("--workload", choices=["auto", "icp", "graphslam", "c5"], default="auto")
     ap.add_argument("--points", type=int, default=1000000)
     ap.add_argument("--scans", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="N=1 ICP: after the timed steps, also the roofline replays, cpu_baseline, convergence check and the "
+                         "other legs (bench_legs.json); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed loop computed in its last step to DIR/<name>.npy (float64, <= 64 MB in all)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-normals", action="store_true", help="N=1 only: skip the calcNormals measurement")
-    ap.add_argument("--no-small-scans", action="store_true", help="N=1 only: skip the doicp_small_scans leg")
+    ap.add_argument("--no-normals", action="store_true", help="N=1 with --full: skip the calcNormals measurement")
+    ap.add_argument("--no-small-scans", action="store_true", help="N=1 with --full: skip the doicp_small_scans leg")
     ap.add_argument("--no-rehearsal", action="store_true",
                     help="graph-SLAM at N=1: skip the one-GPU rehearsal of the sharded step (the profiles: every search dispatch is then a full step's)")
-    ap.add_argument("--no-c5", action="store_true", help="N=1 only: skip the configs[4]-shape leg (10M-point scans)")
+    ap.add_argument("--no-c5", action="store_true", help="N=1 with --full: skip the configs[4]-shape leg (10M-point scans)")
     ap.add_argument("--c5-scans", type=int, default=4, help="scans of the configs[4]-shape leg (of the 13 of the full-size test)")
     ap.add_argument("--c5-points", type=int, default=10000000)
     ap.add_argument("--c5-reps", type=int, default=4, help="whole-scan passes timed")
@@ -1137,7 +1178,7 @@ def main():
     ap.add_argument("--c5-rounds", type=int, default=3, help="lum6DEuler rounds timed")
     ap.add_argument("--c5-links", type=int, default=0, help="0: chain + all closures among the scans")
     ap.add_argument("--no-graphslam-base", action="store_true",
-                    help="N=1 only: skip the extra 1-GPU graph-SLAM measurement (the base of the N>1 curve)")
+                    help="N=1 with --full: skip the extra 1-GPU graph-SLAM measurement (the base of the N>1 curve)")
     args = ap.parse_args()
     capi = importlib.import_module("3dtk_amd._capi")
     if not os.path.exists(os.path.join(ROOT, "3dtk_amd", "lib3dtk_hip.so")):
@@ -1157,6 +1198,8 @@ def main():
     if wl == "c5":
         if world != 1:
             raise SystemExit("bench.py: --workload c5 is a one-GPU leg")
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is for the icp and graphslam workloads")
         c5 = bench_c5(args, local)
         # (a leg on its own: the line carries the leg's whole-scan pass as its headline so that it stays a valid record)
         p_ = c5["whole_scan_pass"]
@@ -1168,7 +1211,7 @@ def main():
     else:
         res = bench_icp(args, rank, world, local) if wl == "icp" else bench_graphslam(args, rank, world, local)
     if rank == 0:
-        emit(res)
+        emit(res, record=args.full or wl != "icp")
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

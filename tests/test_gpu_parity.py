@@ -2175,6 +2175,31 @@ def test_two_ranks_with_lazy_scan_moves_equal_one_rank_moving_eagerly(gpu):
     assert a["last_ret"] == b["last_ret"], (a["last_ret"], b["last_ret"])
 
 
+def test_bench_plain_run_dumps_what_the_timed_loop_computed(gpu, tmp_path):
+    """bench.py without --full: the headline only (no roofline, cpu_baseline or legs), exactly --steps timed iterations,
+    and --dump-outputs writes what the loop computed -- the same files, bit for bit, from two runs with the same arguments."""
+    import subprocess
+    import sys
+    root = os.path.dirname(HERE)
+    lines = []
+    for k in range(2):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--points", "60000", "--steps", "3",
+                            "--warmup", "1", "--dump-outputs", str(tmp_path / str(k))], cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    d = lines[0]
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f64"
+    assert d["roofline"] is None and "cpu_baseline" not in d and "legs" not in d
+    names = sorted(os.listdir(tmp_path / "0"))
+    assert names == ["dalignxf.npy", "points.npy", "trace.npy", "transMat.npy"] == sorted(os.listdir(tmp_path / "1"))
+    for f in names:
+        x, y = np.load(tmp_path / "0" / f), np.load(tmp_path / "1" / f)
+        assert x.dtype == np.float64 and np.array_equal(x, y), f
+    assert np.load(tmp_path / "0" / "points.npy").shape == (60000, 3)
+    tr = np.load(tmp_path / "0" / "trace.npy")                     # one row per timed iteration: pairs, RMS, alignxf
+    assert tr.shape == (3, 18) and tr[-1, 0] == d["pairs_last"] == lines[1]["pairs_last"]
+
+
 @pytest.mark.parametrize("name", ["one", "two", "identical70", "identical64", "two_values", "axis_ties"])
 def test_normals_degenerate_clouds(tdtk, orc, gpu, name):
     """Clouds on which every split of the ANN tree is a tie-break: a single point, two points, all points identical

@@ -920,6 +920,25 @@ def test_bench_line_is_compact_strict_json_with_roofline_and_cpu_baseline():
         bench.build_line(fat)
 
 
+def test_bench_dump_outputs_are_float64_capped_and_repeatable(tmp_path):
+    """bench.dump_outputs (--dump-outputs): one float64 .npy per array; arrays that together exceed the 64 MB budget keep
+    a seeded sample of the largest one's rows, the same from call to call, so that two builds' dumps compare file by file."""
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"pose": np.arange(16, dtype=np.float32), "points": rng.normal(size=(3_000_000, 3))}
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), arrays)
+    assert sorted(os.listdir(tmp_path / "0")) == ["points.npy", "pose.npy"]
+    assert sum(os.path.getsize(tmp_path / "0" / f) for f in os.listdir(tmp_path / "0")) <= 64 * 2 ** 20
+    a, b = np.load(tmp_path / "0" / "points.npy"), np.load(tmp_path / "1" / "points.npy")
+    assert a.dtype == np.float64 and a.shape[1] == 3 and 0 < len(a) < 3_000_000 and np.array_equal(a, b)
+    assert np.isin(a[:, 0], arrays["points"][:, 0]).all()                    # rows of the output, not new values
+    p = np.load(tmp_path / "0" / "pose.npy")
+    assert p.dtype == np.float64 and np.array_equal(p, np.arange(16))
+    bench.dump_outputs(str(tmp_path / "small"), {"points": arrays["points"][:1000]})   # under the budget: everything
+    assert np.array_equal(np.load(tmp_path / "small" / "points.npy"), arrays["points"][:1000])
+
+
 def test_product_and_bench_keep_clear_of_the_oracle():
     """oracle/ is test infrastructure: nothing under 3dtk_amd/, include/ or adapters/ may mention it, the shared
     library must not link it, and bench.py may import it only inside its cpu_baseline legs."""

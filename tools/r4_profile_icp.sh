@@ -9,7 +9,7 @@ for cfg in "20 5" "100 10"; do
   python tools/summarize_profiles.py $tag r04 > gpurun_out/keep/$tag.summary.txt 2>&1
   rm -rf gpurun_out/$tag
 done
+python bench.py --full --steps 20 --warmup 5 > profiles/r04_bench_n1_driver_args.json 2> /tmp/bench_driver_args.err
+python bench.py --full > profiles/r04_bench_n1.json 2> /tmp/bench_default.err
 cp profiles/r04_* gpurun_out/keep/ 2>/dev/null
-python bench.py --steps 20 --warmup 5 > gpurun_out/keep/r04_bench_n1_driver_args.json 2> gpurun_out/keep/bench_driver_args.err
-python bench.py > gpurun_out/keep/r04_bench_n1.json 2> gpurun_out/keep/bench_default.err
 ls -la gpurun_out/keep | head -40

@@ -1,6 +1,6 @@
 # GPU box: headline loop + the 10M legs (product library as built)
 for rep in 1 2; do
-python bench.py --steps 20 --warmup 5 --no-cpu --no-normals --no-small-scans --no-graphslam-base --no-c5 2>/dev/null | python -c "
+python bench.py --full --steps 20 --warmup 5 --no-cpu --no-normals --no-small-scans --no-graphslam-base --no-c5 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('icp 1M: ms_per_step %.4f k_search %.4f' % (d['ms_per_step'], d['roofline']['kernel_ms']))"
 done
 python bench.py --workload c5 --no-cpu --c5-scans 2 --c5-links 1 2>/dev/null | python -c "
