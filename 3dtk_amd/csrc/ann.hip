@@ -32,6 +32,7 @@
 
 #include "kernels.h"
 #include "part_scan.h"
+#include "eigen3.h"
 
 namespace tdtk {
 
@@ -1315,131 +1316,6 @@ AnnBuildResult ann_build_tree(const double* d_xyz, size_t M_, void* arena_, AnnN
 }
 
 // ---- search + PCA -------------------------------------------------------------------------------
-// newmat's EigenValues on a symmetric 3x3 (evalue.cpp:24-156, 283-284; sort.cpp:190-222): tred2, tql2, ascending
-// sort.  z holds the matrix (lower triangle used) on entry and the eigenvectors (columns) on exit.
-static __device__ __forceinline__ double nm_sign(double x, double y) { return (y >= 0) ? x : -x; }
-
-static __device__ void eigen3_newmat(double z[3][3], double D[3])
-{
-  double E[3];
-  const double tol = DBL_MIN / DBL_EPSILON;
-  // tred2, n = 3
-#pragma unroll
-  for (int i = 2; i > 0; i--) {
-    double f = z[i][i - 1], g = 0.0;
-#pragma unroll
-    for (int k = 0; k < i - 1; k++) g += z[i][k] * z[i][k];
-    double h = g + f * f;
-    if (g <= tol) { E[i] = f; h = 0.0; }
-    else {
-      g = nm_sign(-__dsqrt_rn(h), f); E[i] = g; h -= f * g;
-      z[i][i - 1] = f - g; f = 0.0;
-#pragma unroll
-      for (int j = 0; j < i; j++) {
-        z[j][i] = z[i][j] / h; g = 0.0;
-#pragma unroll
-        for (int k = 0; k < j; k++) g += z[j][k] * z[i][k];
-#pragma unroll
-        for (int k = j; k < i; k++) g += z[k][j] * z[i][k];
-        E[j] = g / h; f += g * z[j][i];
-      }
-      const double hh = f / (h + h);
-#pragma unroll
-      for (int j = 0; j < i; j++) {
-        f = z[i][j]; g = E[j] - hh * f; E[j] = g;
-#pragma unroll
-        for (int k = 0; k <= j; k++) z[j][k] -= (f * E[k] + g * z[i][k]);
-      }
-    }
-    D[i] = h;
-  }
-  D[0] = 0.0; E[0] = 0.0;
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    if (D[i] != 0.0) {
-#pragma unroll
-      for (int j = 0; j < i; j++) {
-        double g = 0.0;
-#pragma unroll
-        for (int k = 0; k < i; k++) g += z[i][k] * z[k][j];
-#pragma unroll
-        for (int k = 0; k < i; k++) z[k][j] -= g * z[k][i];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < i; j++) { z[i][j] = 0.0; z[j][i] = 0.0; }
-    D[i] = z[i][i]; z[i][i] = 1.0;
-  }
-  // tql2, n = 3
-  const double eps = DBL_EPSILON;
-  E[0] = E[1]; E[1] = E[2];
-  double b = 0.0, f = 0.0;
-  E[2] = 0.0;
-#pragma unroll
-  for (int l = 0; l < 3; l++) {
-    double h = eps * (fabs(D[l]) + fabs(E[l]));
-    if (b < h) b = h;
-    int m = 3;
-#pragma unroll
-    for (int mm = 2; mm >= 0; mm--)
-      if (mm >= l && fabs(E[mm]) <= b) m = mm;     // first m >= l with |E[m]| <= b (E[2] == 0 ends it)
-    for (int j = 0; j < 30; j++) {
-      if (m == l) break;
-      double g = D[l];
-      const double dl1 = (l == 0) ? D[1] : D[2];   // l < m <= 2 here
-      double p = (dl1 - g) / (2.0 * E[l]), r = __dsqrt_rn(p * p + 1.0);
-      D[l] = E[l] / (p < 0.0 ? p - r : p + r);
-      const double hh = g - D[l];
-      f += hh;
-#pragma unroll
-      for (int i = 1; i < 3; i++) if (i > l) D[i] -= hh;
-      p = (m == 1) ? D[1] : D[2];
-      double c = 1.0, s = 0.0;
-#pragma unroll
-      for (int i = 1; i >= 0; i--) {
-        if (i <= m - 1 && i >= l) {
-          const double ei = E[i], di = D[i];
-          g = c * ei; h = c * p;
-          if (fabs(p) >= fabs(ei)) {
-            c = ei / p; r = __dsqrt_rn(c * c + 1.0);
-            E[i + 1] = s * p * r; s = c / r; c = 1.0 / r;
-          } else {
-            c = p / ei; r = __dsqrt_rn(c * c + 1.0);
-            E[i + 1] = s * ei * r; s = 1.0 / r; c /= r;
-          }
-          p = c * di - s * g; D[i + 1] = h + s * (c * g + s * di);
-#pragma unroll
-          for (int k = 0; k < 3; k++) {
-            h = z[k][i + 1];
-            z[k][i + 1] = s * z[k][i] + c * h;
-            z[k][i] = c * z[k][i] - s * h;
-          }
-        }
-      }
-      E[l] = s * p; D[l] = c * p;
-      if (fabs(E[l]) <= b) break;
-    }
-    D[l] += f;     // (30 sweeps without convergence throw in the reference; unreachable for a 3x3)
-  }
-  // SortSV ascending: selection sort, columns follow
-#pragma unroll
-  for (int i = 0; i < 3; i++) {
-    int k = i;
-    double p = D[i];
-#pragma unroll
-    for (int j = i + 1; j < 3; j++) if (D[j] < p) { k = j; p = D[j]; }
-    if (k != i) {
-#pragma unroll
-      for (int kk = 1; kk < 3; kk++)
-        if (kk == k) {
-          D[kk] = D[i]; D[i] = p;
-#pragma unroll
-          for (int j = 0; j < 3; j++) { const double t = z[j][i]; z[j][i] = z[j][kk]; z[j][kk] = t; }
-        }
-    }
-  }
-}
-
 #define ANN_LDS_STACK 12   // far-child entries per thread kept in LDS; deeper ones spill to global memory
 
 // One thread per scan point (grid-stride over leaf positions).  KMAX >= k; the list keeps KMAX - k sentinels
@@ -1553,19 +1429,7 @@ __global__ void __launch_bounds__(256) k_ann_normals(const AnnNode* __restrict__
 #pragma unroll
           for (int c = 0; c <= r; c++) z[r][c] += (sc * x[c]) * x[r];
       }
-    z[0][1] = z[1][0]; z[0][2] = z[2][0]; z[1][2] = z[2][1];
-    double D[3];
-    eigen3_newmat(z, D);
-    double nv[3] = {z[0][0], z[1][0], z[2][0]};
-    double pv[3] = {q[0] - rx, q[1] - ry, q[2] - rz};
-    const double pl = 1.0 / __dsqrt_rn((pv[0] * pv[0] + pv[1] * pv[1]) + pv[2] * pv[2]);   // "v / norm" is v * (1 / norm) in newmat
-    pv[0] *= pl; pv[1] *= pl; pv[2] *= pl;
-    const double angle = (nv[0] * pv[0] + nv[1] * pv[1]) + nv[2] * pv[2];
-    if (angle < 0) { nv[0] *= -1.0; nv[1] *= -1.0; nv[2] *= -1.0; }
-    const double nl = 1.0 / __dsqrt_rn((nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2]);
-    normals[3 * (size_t)qp.orig] = nv[0] * nl;
-    normals[3 * (size_t)qp.orig + 1] = nv[1] * nl;
-    normals[3 * (size_t)qp.orig + 2] = nv[2] * nl;
+    normal_from_cov(z, q[0], q[1], q[2], rx, ry, rz, normals + 3 * (size_t)qp.orig);
   }
   if (COUNT && cnt) {
     unsigned long long a = c_split, b = c_leaf;

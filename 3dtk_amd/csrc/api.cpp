@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "query.h"
 
 using namespace tdtk;
 
@@ -1380,6 +1381,191 @@ int tdtk_find_closest(const tdtk_tree* t, const double* q, size_t K, double maxd
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(idx, c->ws[WS_IDX].p, K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   if (d2) HIPCHK(hipMemcpyAsync(d2, c->ws[WS_TMPB].p, K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return TDTK_OK;
+}
+
+}  // extern "C"
+
+// ---- k-NN and fixed-radius search (query.hip) ------------------------------------------------
+// the K queries at d_q [K][3], spatially binned into WS_QX / WS_QY / WS_QZ (order: sorted position -> caller index), the
+// tree's walk arguments and the stack overflow area
+static int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K, QueryArgs& a)
+{
+  int rc;
+  int ids[] = {WS_QX, WS_QY, WS_QZ};
+  for (int id : ids)
+    if ((rc = c->ws[id].ensure(K * sizeof(double)))) return rc;
+  if ((rc = c->ws[WS_ORDER].ensure(K * sizeof(int32_t)))) return rc;
+  if ((rc = c->ws[WS_CELL].ensure(K * sizeof(uint32_t)))) return rc;
+  if ((rc = c->ws[WS_HIST].ensure(32768 * sizeof(uint32_t)))) return rc;
+  BinArgs b{};
+  b.q = d_q; b.dir = nullptr; b.n = K;
+  for (int ax = 0; ax < 3; ax++) {
+    b.lo[ax] = t->bbmin[ax];
+    const double ext = t->bbmax[ax] - t->bbmin[ax];
+    b.scale[ax] = (ext > 0) ? 32.0 / ext : 0.0;
+  }
+  b.hist = c->ws[WS_HIST].as<uint32_t>();
+  b.cell = c->ws[WS_CELL].as<uint32_t>();
+  b.sx = c->ws[WS_QX].as<double>(); b.sy = c->ws[WS_QY].as<double>(); b.sz = c->ws[WS_QZ].as<double>();
+  b.order = c->ws[WS_ORDER].as<int32_t>();
+  HIPCHK(launch_bin(b, c->stream));
+  a = QueryArgs{};
+  a.nodes = t->dev.nodes; a.pts = t->dev.pts; a.leaf_tab = t->dev.leaf_tab;
+  a.root_ref = t->dev.root_ref; a.cb = t->dev.cb; a.cmask = t->dev.cmask;
+  a.x = b.sx; a.y = b.sy; a.z = b.sz; a.order = b.order; a.n = K;
+  const size_t ovf = query_overflow_entries(K, t->info.max_depth);
+  if (ovf) {
+    if ((rc = c->ws[WS_OVF_M2].ensure(ovf * sizeof(double)))) return rc;
+    if ((rc = c->ws[WS_OVF_REF].ensure(ovf * sizeof(uint32_t)))) return rc;
+    a.ovf_m2 = c->ws[WS_OVF_M2].as<double>();
+    a.ovf_ref = c->ws[WS_OVF_REF].as<uint32_t>();
+  }
+  return TDTK_OK;
+}
+
+static int knn_check_k(int k)
+{
+  if (k < 1) { set_error("k must be >= 1"); return TDTK_EINVAL; }
+  if (k > KNN_MAX_K) { set_error("k = " + std::to_string(k) + " exceeds the supported list capacity of " + std::to_string(KNN_MAX_K)); return TDTK_EUNSUP; }
+  return TDTK_OK;
+}
+
+// a tree over host points [n][3] for the normal estimators; the points stay in WS_TMPA (the build only reads them)
+static int normals_tree(Ctx* c, const double* xyz, size_t n, int bucket, int device, std::unique_ptr<tdtk_tree>& t)
+{
+  int rc;
+  t.reset(new tdtk_tree);
+  t->device = device; t->M = n; t->bucket = bucket;
+  if ((rc = tree_check_args(n, bucket))) return rc;
+  if ((rc = c->ws[WS_TMPA].ensure(3 * n * sizeof(double)))) return rc;
+  HIPCHK(hipMemcpyAsync(c->ws[WS_TMPA].p, xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if ((rc = tree_from_device_points(c, t.get(), n, bucket, now_ms()))) return rc;
+  return tree_finish(c, t.get(), n);
+}
+
+extern "C" {
+
+int tdtk_knn_search(const tdtk_tree* t, const double* q, size_t K, int k, int32_t* idx, double* d2)
+{
+  if (!t || (!q && K) || (!idx && K)) { set_error("NULL argument"); return TDTK_EINVAL; }
+  int rc;
+  if ((rc = knn_check_k(k))) return rc;
+  Ctx* c;
+  if ((rc = get_ctx(t->device, &c))) return rc;
+  if (K == 0) return TDTK_OK;
+  const size_t L = K * (size_t)k;
+  if ((rc = c->ws[WS_TMPA].ensure(3 * K * sizeof(double)))) return rc;
+  if ((rc = c->ws[WS_IDX].ensure(L * sizeof(int32_t)))) return rc;
+  if (d2 && (rc = c->ws[WS_TMPB].ensure(L * sizeof(double)))) return rc;
+  HIPCHK(hipMemcpyAsync(c->ws[WS_TMPA].p, q, 3 * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  QueryArgs a;
+  if ((rc = query_prepare(c, t, c->ws[WS_TMPA].as<double>(), K, a))) return rc;
+  a.k = k;
+  a.idx = c->ws[WS_IDX].as<int32_t>();
+  a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
+  HIPCHK(launch_knn(a, false, c->stream));
+  HIPCHK(hipMemcpyAsync(idx, a.idx, L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return TDTK_OK;
+}
+
+int tdtk_fixed_range_search(const tdtk_tree* t, const double* q, size_t K, double sqRad2, uint64_t* offsets, int32_t* idx,
+                            double* d2, size_t cap, uint64_t* total)
+{
+  if (!t || (!q && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
+  Ctx* c;
+  int rc;
+  if ((rc = get_ctx(t->device, &c))) return rc;
+  offsets[0] = 0; *total = 0;
+  if (K == 0) return TDTK_OK;
+  hipStream_t s = c->stream;
+  const size_t tmpb = range_scan_temp_bytes(K);
+  if ((rc = c->ws[WS_TMPA].ensure(3 * K * sizeof(double)))) return rc;
+  if ((rc = c->ws[WS_KPOS].ensure((K + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = c->ws[WS_D2].ensure((K + 1) * sizeof(unsigned long long)))) return rc;
+  if ((rc = c->ws[WS_ARENA].ensure(tmpb + 256))) return rc;
+  HIPCHK(hipMemcpyAsync(c->ws[WS_TMPA].p, q, 3 * K * sizeof(double), hipMemcpyHostToDevice, s));
+  QueryArgs a;
+  if ((rc = query_prepare(c, t, c->ws[WS_TMPA].as<double>(), K, a))) return rc;
+  a.r2 = sqRad2;
+  a.counts = c->ws[WS_KPOS].as<uint32_t>();
+  unsigned long long* d_off = c->ws[WS_D2].as<unsigned long long>();
+  HIPCHK(hipMemsetAsync(a.counts + K, 0, sizeof(uint32_t), s));
+  HIPCHK(launch_range_count(a, s));
+  HIPCHK(launch_range_scan(a.counts, d_off, K, c->ws[WS_ARENA].p, tmpb, s));
+  HIPCHK(hipMemcpyAsync(offsets, d_off, (K + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const uint64_t tot = offsets[K];
+  *total = tot;
+  if (cap < tot) {
+    set_error("fixedRangeSearch: " + std::to_string(tot) + " neighbours, capacity " + std::to_string(cap) + " (offsets and total are filled)");
+    return TDTK_EINVAL;
+  }
+  if (tot == 0) return TDTK_OK;
+  if (!idx) { set_error("idx is NULL"); return TDTK_EINVAL; }
+  if ((rc = c->ws[WS_IDX].ensure(tot * sizeof(int32_t)))) return rc;
+  if (d2 && (rc = c->ws[WS_TMPB].ensure(tot * sizeof(double)))) return rc;
+  a.offsets = d_off;
+  a.idx = c->ws[WS_IDX].as<int32_t>();
+  a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
+  HIPCHK(launch_range_fill(a, s));
+  HIPCHK(hipMemcpyAsync(idx, a.idx, tot * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, tot * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return TDTK_OK;
+}
+
+int tdtk_normals_knn(const double* xyz, size_t n, int k, const double rPos[3], int bucket, int device, double* normals_out,
+                     int32_t* knn_out)
+{
+  if (!rPos) { set_error("rPos is NULL"); return TDTK_EINVAL; }
+  if (!xyz || n == 0) { set_error("Could not calculate normals, XYZ data is empty"); return TDTK_EINVAL; }
+  if (!normals_out) { set_error("NULL argument"); return TDTK_EINVAL; }
+  int rc;
+  if ((rc = knn_check_k(k))) return rc;
+  Ctx* c;
+  if ((rc = get_ctx(device, &c))) return rc;
+  std::unique_ptr<tdtk_tree> t;
+  if ((rc = normals_tree(c, xyz, n, bucket, device, t))) return rc;
+  const size_t L = n * (size_t)k;
+  if ((rc = c->ws[WS_TMPB].ensure(3 * n * sizeof(double)))) return rc;
+  if (knn_out && (rc = c->ws[WS_IDX].ensure(L * sizeof(int32_t)))) return rc;
+  QueryArgs a;
+  if ((rc = query_prepare(c, t.get(), c->ws[WS_TMPA].as<double>(), n, a))) return rc;
+  a.k = k;
+  a.rx = rPos[0]; a.ry = rPos[1]; a.rz = rPos[2];
+  a.normals = c->ws[WS_TMPB].as<double>();
+  a.knn_out = knn_out ? c->ws[WS_IDX].as<int32_t>() : nullptr;
+  HIPCHK(launch_knn(a, true, c->stream));
+  HIPCHK(hipMemcpyAsync(normals_out, a.normals, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (knn_out) HIPCHK(hipMemcpyAsync(knn_out, a.knn_out, L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return TDTK_OK;
+}
+
+int tdtk_normals_range(const double* xyz, size_t n, double sqRad2, const double rPos[3], int bucket, int device,
+                       double* normals_out)
+{
+  if (!rPos) { set_error("rPos is NULL"); return TDTK_EINVAL; }
+  if (!xyz || n == 0) { set_error("Could not calculate normals, XYZ data is empty"); return TDTK_EINVAL; }
+  if (!normals_out) { set_error("NULL argument"); return TDTK_EINVAL; }
+  if (!(sqRad2 > 0)) { set_error("sqRad2 must be > 0 (an empty neighbourhood has no mean)"); return TDTK_EINVAL; }
+  int rc;
+  Ctx* c;
+  if ((rc = get_ctx(device, &c))) return rc;
+  std::unique_ptr<tdtk_tree> t;
+  if ((rc = normals_tree(c, xyz, n, bucket, device, t))) return rc;
+  if ((rc = c->ws[WS_TMPB].ensure(3 * n * sizeof(double)))) return rc;
+  QueryArgs a;
+  if ((rc = query_prepare(c, t.get(), c->ws[WS_TMPA].as<double>(), n, a))) return rc;
+  a.r2 = sqRad2;
+  a.rx = rPos[0]; a.ry = rPos[1]; a.rz = rPos[2];
+  a.normals = c->ws[WS_TMPB].as<double>();
+  HIPCHK(launch_range_normals(a, c->stream));
+  HIPCHK(hipMemcpyAsync(normals_out, a.normals, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return TDTK_OK;
 }

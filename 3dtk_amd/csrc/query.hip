@@ -1,0 +1,501 @@
+// lib3dtk_hip.so -- k nearest neighbours and fixed-radius search on the resident kd-tree, and the two normal estimators built
+// on them: KDTreeImpl::_KNNSearch (kdTreeImpl.h:627-682), _FixedRangeSearch (kdTreeImpl.h:585-625), calculateNormalsKNN /
+// calculateNormalsRange with calculateNormal's PCA (normals.cc:369-439, 442-516, 518-558).
+//
+// Layout of every kernel here: one query per lane, the queries spatially binned first (launch_bin) so that the lanes of a
+// wave walk neighbouring parts of the tree, a grid-stride loop over the sorted queries, results written straight to the
+// caller's position (order[]).  The walk is a DFS with an explicit per-lane stack (LaneStackQ: LDS levels + an HBM overflow
+// column sized from the tree's depth); the node records are the fp64 KdNode ones, so every decision below is the reference's
+// own expression on the reference's own values -- no fp32 shortcut, nothing to prove under rounding.
+//
+// The two walks, rule by rule (each is easy to get subtly wrong):
+//
+// k-NN (_KNNSearch):
+//   * list of k slots (distance, point), distances start at -1 ("unset").  "full" = distances[k-1] != -1.
+//   * internal node, on entering it: ONLY when the list is full, the box check
+//       a = max(max(|p0-cx|-hx, |p1-cy|-hy), |p2-cz|-hz);  prune when a >= 0 && a*a >= distances[k-1]
+//     (a node entered while the list is not full is never pruned, however far away it is).
+//   * near child first when p[axis] < splitval -- a STRICT '<' (FindClosest and the range search use splitval - p >= 0,
+//     so on a split plane the two rules pick different sides).  The far child is never pruned by its plane: it is pushed
+//     unconditionally and meets only its own box check when it is popped (with the list as it is then).
+//   * a leaf has no box: it is scanned whenever it is reached, in bucket order, over its real count (padded group slots
+//     are never looked at).  Each point goes in before the first slot that is unset or holds a strictly larger distance;
+//     the last slot drops out.  Equal distances keep their visiting order, a point equal to the k-th distance of a full
+//     list is dropped.  Once the list is full, "kth <= d2" therefore means "no slot is larger": skipped without a scan.
+//   * fewer than k points in the tree: the list holds M entries, the rest is reported as -1 / -1.0.
+// Fixed radius (_FixedRangeSearch), r2 fixed for the whole walk:
+//   * internal node: prune when a >= 0 && a*a >= r2 (a as above).
+//   * myd = splitval - p[axis]; myd >= 0: child1 first, child2 after it only if myd*myd < r2; otherwise child2 first and
+//     child1 under the same condition.  r2 never changes, so the condition is tested when the far child is pushed.
+//   * leaf: every point with Dist2 < r2, in bucket order; the list is in visiting order.
+// Dist2 (globals.icc:238) = (dx*dx + dy*dy) + dz*dz, dx = point - query; fp64 everywhere, FMA contraction off (Makefile).
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
+
+#include "kernels.h"
+#include "lane_stack.h"
+#include "eigen3.h"
+#include "query.h"
+
+namespace tdtk {
+
+constexpr int Q_BLOCK = 128;     // register-list and range kernels
+constexpr int Q_SD = 16;         // LDS stack levels (16 bytes each): 32 KB per 128-lane workgroup
+constexpr int Q_BLOCK_L = 64;    // the LDS-list k-NN kernel: 64 lanes x 64 slots x 12 bytes = 48 KB + 16 KB of stack
+constexpr int Q_MAX_BLOCKS = 2048;   // grid-stride cap (256 CUs x 8); the overflow area is sized for it
+
+// The argument block read through the kernarg segment pointer (as kernels.hip's kernarg_block): behind an opaque pointer of
+// the constant address space its fields are s_load'ed where they are used instead of being held in SGPRs across the walk
+// (the register lists leave no room for that).  The block is every kernel's only parameter.
+__device__ __forceinline__ const QueryArgs& q_args()
+{
+  typedef const QueryArgs __attribute__((address_space(4))) * kernarg_ptr;
+  kernarg_ptr p = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *(const QueryArgs*)p;
+}
+
+// one node's box test (kdTreeImpl.h:606-612 / 662-668): std::max(std::max(ax, ay), az)
+__device__ __forceinline__ double box_dist(const KdNode& nd, const double qx, const double qy, const double qz)
+{
+  const double ax = fabs(qx - nd.cx) - nd.hx;
+  const double ay = fabs(qy - nd.cy) - nd.hy;
+  const double az = fabs(qz - nd.cz) - nd.hz;
+  const double ab = (ax < ay) ? ay : ax;
+  return (ab < az) ? az : ab;
+}
+
+__device__ __forceinline__ void leaf_span(const QueryArgs& a, const uint32_t ref, uint32_t& start, uint32_t& count)
+{
+  const uint32_t v = ref & REF_VAL;
+  if (a.leaf_tab) { const LeafEntry e = a.leaf_tab[v]; start = (uint32_t)e.start; count = (uint32_t)e.count; }
+  else { start = v >> a.cb; count = v & a.cmask; }
+}
+
+__device__ __forceinline__ double dist2(const KdPoint& p, const double qx, const double qy, const double qz)
+{
+  const double dx = p.x - qx, dy = p.y - qy, dz = p.z - qz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
+template <int BLOCK>
+__device__ __forceinline__ void stack_init(LaneStackQ<BLOCK, Q_SD>& st, uint4 (*lds)[BLOCK], const QueryArgs& a)
+{
+  st.l_e = &lds[0][threadIdx.x];
+  st.g_m2 = a.ovf_m2;
+  st.g_ref = a.ovf_ref;
+  st.gcol = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  st.gstride = (size_t)gridDim.x * BLOCK;
+  st.sp = 0;
+}
+
+// ---- the k-NN list ----------------------------------------------------------------------------------------------
+// in registers, KC slots, every index static (nothing goes to scratch).  The list is the LAST k slots, k0 = KC - k;
+// the k0 slots in front hold -0.0, which is neither unset (-0.0 < 0.0 is false) nor larger than any distance, so an
+// insertion never stops there and never shifts them: the bubble below needs no per-slot test of k, and distances[k-1]
+// is always slot KC-1.
+template <int KC>
+struct ListReg {
+  double d[KC];
+  uint32_t s[KC];
+  double kth;   // distances[k-1]
+  __device__ __forceinline__ void init(const int k0)
+  {
+#pragma unroll
+    for (int j = 0; j < KC; j++) { d[j] = (j < k0) ? -0.0 : -1.0; s[j] = 0xFFFFFFFFu; }
+    kth = -1.0;
+  }
+  __device__ __forceinline__ bool full() const { return kth != -1.0; }
+  __device__ __forceinline__ void insert(const double md, const uint32_t slot)
+  {
+    if (kth != -1.0 && kth <= md) return;      // full and no slot larger than md: the reference's loop finds no place
+    // the first slot that is unset or strictly larger takes the point (found from the back: a plain minimum, exact even
+    // where a NaN distance breaks the order), every slot behind it takes its left neighbour, the last one drops out
+    int pos = KC;
+#pragma unroll
+    for (int j = KC - 1; j >= 0; j--) {
+      double mj = md;
+      asm volatile("" : "+v"(mj));
+      pos = (d[j] < 0.0 || d[j] > mj) ? j : pos;
+    }
+#pragma unroll
+    for (int j = KC - 1; j > 0; j--) {
+      // (pos - j through an empty asm: the compiler would otherwise form all 2 KC lane masks up front, in SGPRs -- they spill)
+      int pj = pos - j;
+      asm volatile("" : "+v"(pj));
+      const bool up = pj < 0, at = pj == 0;
+      d[j] = up ? d[j - 1] : (at ? md : d[j]);
+      s[j] = up ? s[j - 1] : (at ? slot : s[j]);
+    }
+    d[0] = (pos == 0) ? md : d[0];
+    s[0] = (pos == 0) ? slot : s[0];
+    kth = d[KC - 1];
+  }
+};
+
+// in LDS, [slot][lane] (a wave's accesses to one slot are 64 consecutive 8-byte words: no bank conflict)
+template <int BLOCK>
+struct ListLds {
+  double* ld;
+  uint32_t* ls;
+  int k, cnt;
+  double kth;
+  __device__ __forceinline__ void init(int kk)
+  {
+    k = kk; cnt = 0; kth = -1.0;
+    for (int j = 0; j < k; j++) { ld[j * BLOCK] = -1.0; ls[j * BLOCK] = 0xFFFFFFFFu; }
+  }
+  __device__ __forceinline__ bool full() const { return kth != -1.0; }
+  __device__ __forceinline__ void insert(const double md, const uint32_t slot)
+  {
+    if (kth != -1.0 && kth <= md) return;
+    int j = 0;
+    for (; j < cnt; j++) if (ld[j * BLOCK] > md) break;     // slots >= cnt are unset
+    if (j >= k) return;
+    // the reference moves slots j .. k-2 up by one; beyond cnt they are unset and stay so
+    for (int l = (cnt < k - 1 ? cnt : k - 1); l > j; --l) { ld[l * BLOCK] = ld[(l - 1) * BLOCK]; ls[l * BLOCK] = ls[(l - 1) * BLOCK]; }
+    ld[j * BLOCK] = md;
+    ls[j * BLOCK] = slot;
+    if (cnt < k) ++cnt;
+    if (cnt == k) kth = ld[(k - 1) * BLOCK];
+  }
+  __device__ __forceinline__ double dist(int j) const { return ld[j * BLOCK]; }
+  __device__ __forceinline__ uint32_t slot(int j) const { return ls[j * BLOCK]; }
+};
+
+// ---- the walks -------------------------------------------------------------------------------------------------
+template <int BLOCK, class LIST>
+__device__ void knn_walk(const QueryArgs& a, const double qx, const double qy, const double qz, LIST& L,
+                         LaneStackQ<BLOCK, Q_SD>& st)
+{
+  uint32_t cur = a.root_ref;
+  for (;;) {
+    if (cur & REF_LEAF) {
+      uint32_t start, count;
+      leaf_span(a, cur, start, count);
+      for (uint32_t i = 0; i < count; i++) {
+        const KdPoint p = a.pts[start + i];
+        L.insert(dist2(p, qx, qy, qz), start + i);
+      }
+    } else {
+      const KdNode nd = a.nodes[cur & REF_VAL];
+      bool pruned = false;
+      if (L.full()) {
+        const double ap = box_dist(nd, qx, qy, qz);
+        pruned = (ap >= 0.0 && ap * ap >= L.kth);
+      }
+      if (!pruned) {
+        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
+        const double qa = (axis == 0) ? qx : ((axis == 1) ? qy : qz);
+        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2 = nd.c2 & ~REF_AXIS;
+        const bool first = qa < nd.splitval;
+        st.push(first ? r2 : r1, 0.0);
+        cur = first ? r1 : r2;
+        continue;
+      }
+    }
+    if (st.sp == 0) break;
+    --st.sp;
+    double unused;
+    st.top(cur, unused);
+  }
+}
+
+// EMIT(point, slot, d2) for every point of the radius list, in the reference's visiting order
+template <int BLOCK, class EMIT>
+__device__ void range_walk(const QueryArgs& a, const double qx, const double qy, const double qz, const double r2,
+                           LaneStackQ<BLOCK, Q_SD>& st, EMIT& emit)
+{
+  uint32_t cur = a.root_ref;
+  for (;;) {
+    if (cur & REF_LEAF) {
+      uint32_t start, count;
+      leaf_span(a, cur, start, count);
+      for (uint32_t i = 0; i < count; i++) {
+        const KdPoint p = a.pts[start + i];
+        const double md = dist2(p, qx, qy, qz);
+        if (md < r2) emit(p, start + i, md);
+      }
+    } else {
+      const KdNode nd = a.nodes[cur & REF_VAL];
+      const double ap = box_dist(nd, qx, qy, qz);
+      if (!(ap >= 0.0 && ap * ap >= r2)) {
+        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
+        const double qa = (axis == 0) ? qx : ((axis == 1) ? qy : qz);
+        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2c = nd.c2 & ~REF_AXIS;
+        const double myd = nd.splitval - qa;
+        const bool first = myd >= 0.0;
+        if (myd * myd < r2) st.push(first ? r2c : r1, 0.0);
+        cur = first ? r1 : r2c;
+        continue;
+      }
+    }
+    if (st.sp == 0) break;
+    --st.sp;
+    double unused;
+    st.top(cur, unused);
+  }
+}
+
+// calculateNormal (normals.cc:518-558) over a list the caller enumerates: each(f) calls f(point) for the nr points of the
+// list in list order, and is called twice (mean, then covariance -- the arithmetic of k_ann_normals: mean / nr, then
+// A = (1/nr X^T) X summed in list order); eigen3.h's normal_from_cov does the rest.  nr is read after the first pass (the
+// range normals count their list there).
+template <class EACH>
+__device__ __forceinline__ void list_normal(EACH&& each, const int& nr, const double qx, const double qy, const double qz,
+                                            const QueryArgs& a, double* out)
+{
+  double mean[3] = {0.0, 0.0, 0.0};
+  each([&](const KdPoint& p) { mean[0] += p.x; mean[1] += p.y; mean[2] += p.z; });
+  mean[0] /= nr; mean[1] /= nr; mean[2] /= nr;
+  const double sc = 1.0 / nr;
+  double z[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  each([&](const KdPoint& p) {
+    const double x[3] = {p.x - mean[0], p.y - mean[1], p.z - mean[2]};
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c <= r; c++) z[r][c] += (sc * x[c]) * x[r];
+  });
+  normal_from_cov(z, qx, qy, qz, a.rx, a.ry, a.rz, out);
+}
+
+// ---- kernels ---------------------------------------------------------------------------------------------------
+// Both k-NN kernels end alike: the list as a caller-order row (idx and d2, or knn_out for the normals: -1 / -1.0 beyond nr
+// entries) and, for the normals, list_normal over it.  They differ in how a list slot is reached: a register list only by
+// static indices (every loop fully unrolled over the capacity), the LDS list by a run-time index.
+
+// the register-list form: list slot jl is register slot j = k0 + jl
+template <int KC, bool NORMALS>
+__global__ void __launch_bounds__(Q_BLOCK) k_knn_reg(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  LaneStackQ<Q_BLOCK, Q_SD> st;
+  stack_init<Q_BLOCK>(st, s_stack, a);
+  ListReg<KC> L;
+  const int k = a.k;
+  const size_t T = (size_t)gridDim.x * Q_BLOCK;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+    const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
+    const size_t o = a.order ? (size_t)a.order[i] : i;
+    // (k0 through an empty asm, per query: as a loop invariant the list's initial values and the slot tests below would be
+    // formed once, in SGPRs, and held across the walk -- they spill)
+    int k0 = KC - k;
+    asm volatile("" : "+v"(k0));
+    L.init(k0);
+    st.sp = 0;
+    knn_walk<Q_BLOCK>(a, qx, qy, qz, L, st);
+    // entries: the slots with a distance >= 0 (kdIndexed.cc:152-156), which are the first nr -- fewer than k only when the
+    // tree has fewer than k points.  (jl through an empty asm per slot, for the reason above.)
+    int nr = 0;
+#pragma unroll
+    for (int j = 0; j < KC; j++) {
+      int jl = j - k0;
+      asm volatile("" : "+v"(jl));
+      nr += (jl >= 0 && L.d[j] >= 0.0) ? 1 : 0;
+    }
+    if (NORMALS) {
+      auto each = [&](auto&& f) {
+#pragma unroll
+        for (int j = 0; j < KC; j++) {
+          int jl = j - k0;
+          asm volatile("" : "+v"(jl));
+          if (jl >= 0 && jl < nr) f(a.pts[L.s[j]]);
+        }
+      };
+      list_normal(each, nr, qx, qy, qz, a, a.normals + 3 * o);
+    }
+    // (the row after the normal: written first, its loads of the points were kept live across the PCA -- 170 registers
+    // instead of 134 at k = 20)
+    int32_t* row = NORMALS ? a.knn_out : a.idx;
+    row = row ? row + o * k : nullptr;
+    double* drow = (!NORMALS && a.d2) ? a.d2 + o * k : nullptr;
+#pragma unroll
+    for (int j = 0; j < KC; j++) {
+      int jl = j - k0;
+      asm volatile("" : "+v"(jl));
+      if (jl >= 0) {
+        const bool v = jl < nr;
+        if (row) row[jl] = v ? a.pts[v ? L.s[j] : 0u].orig : -1;     // (an unset slot's point is never loaded)
+        if (drow) drow[jl] = v ? L.d[j] : -1.0;
+      }
+    }
+  }
+}
+
+// the LDS-list form (33 <= k <= 64)
+template <bool NORMALS>
+__global__ void __launch_bounds__(Q_BLOCK_L) k_knn_lds(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK_L];
+  __shared__ double s_d[KNN_MAX_K][Q_BLOCK_L];
+  __shared__ uint32_t s_s[KNN_MAX_K][Q_BLOCK_L];
+  LaneStackQ<Q_BLOCK_L, Q_SD> st;
+  stack_init<Q_BLOCK_L>(st, s_stack, a);
+  ListLds<Q_BLOCK_L> L;
+  L.ld = &s_d[0][threadIdx.x];
+  L.ls = &s_s[0][threadIdx.x];
+  const int k = a.k;
+  const size_t T = (size_t)gridDim.x * Q_BLOCK_L;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK_L + threadIdx.x; i < a.n; i += T) {
+    const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
+    const size_t o = a.order ? (size_t)a.order[i] : i;
+    L.init(k);
+    st.sp = 0;
+    knn_walk<Q_BLOCK_L>(a, qx, qy, qz, L, st);
+    int nr = 0;
+    for (int j = 0; j < k; j++) nr += (L.dist(j) >= 0.0) ? 1 : 0;   // kdIndexed.cc:152-156
+    int32_t* row = NORMALS ? a.knn_out : a.idx;
+    row = row ? row + o * k : nullptr;
+    double* drow = (!NORMALS && a.d2) ? a.d2 + o * k : nullptr;
+    for (int j = 0; j < k; j++) {
+      const bool v = j < nr;
+      if (row) row[j] = v ? a.pts[v ? L.slot(j) : 0u].orig : -1;
+      if (drow) drow[j] = v ? L.dist(j) : -1.0;
+    }
+    if (NORMALS) {
+      auto each = [&](auto&& f) { for (int j = 0; j < nr; j++) f(a.pts[L.slot(j)]); };
+      list_normal(each, nr, qx, qy, qz, a, a.normals + 3 * o);
+    }
+  }
+}
+
+// range search, first walk: the length of every list (caller order)
+__global__ void __launch_bounds__(Q_BLOCK) k_range_count(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  LaneStackQ<Q_BLOCK, Q_SD> st;
+  stack_init<Q_BLOCK>(st, s_stack, a);
+  const size_t T = (size_t)gridDim.x * Q_BLOCK;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+    uint32_t c = 0;
+    auto emit = [&](const KdPoint&, uint32_t, double) { ++c; };
+    st.sp = 0;
+    range_walk<Q_BLOCK>(a, a.x[i], a.y[i], a.z[i], a.r2, st, emit);
+    a.counts[a.order ? (size_t)a.order[i] : i] = c;
+  }
+}
+
+// second walk, the same visits: every list at its offset
+__global__ void __launch_bounds__(Q_BLOCK) k_range_fill(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  LaneStackQ<Q_BLOCK, Q_SD> st;
+  stack_init<Q_BLOCK>(st, s_stack, a);
+  const size_t T = (size_t)gridDim.x * Q_BLOCK;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+    const size_t o = a.order ? (size_t)a.order[i] : i;
+    unsigned long long w = a.offsets[o];
+    const unsigned long long end = a.offsets[o + 1];
+    auto emit = [&](const KdPoint& p, uint32_t, double md) {
+      if (w < end) {       // (the count walk made the same visits: never false)
+        a.idx[w] = p.orig;
+        if (a.d2) a.d2[w] = md;
+      }
+      ++w;
+    };
+    st.sp = 0;
+    range_walk<Q_BLOCK>(a, a.x[i], a.y[i], a.z[i], a.r2, st, emit);
+  }
+}
+
+// calculateNormalsRange: the list has no upper bound and is not stored -- list_normal's two passes over it are two
+// identical walks (same visits, same order); nr >= 1 because a point finds itself
+__global__ void __launch_bounds__(Q_BLOCK) k_range_normals(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  LaneStackQ<Q_BLOCK, Q_SD> st;
+  stack_init<Q_BLOCK>(st, s_stack, a);
+  const size_t T = (size_t)gridDim.x * Q_BLOCK;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+    const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
+    const size_t o = a.order ? (size_t)a.order[i] : i;
+    int nr = 0;
+    bool counted = false;
+    auto each = [&](auto&& f) {
+      auto emit = [&](const KdPoint& p, uint32_t, double) { f(p); if (!counted) ++nr; };
+      st.sp = 0;
+      range_walk<Q_BLOCK>(a, qx, qy, qz, a.r2, st, emit);
+      counted = true;
+    };
+    list_normal(each, nr, qx, qy, qz, a, a.normals + 3 * o);
+  }
+}
+
+// ---- launchers -------------------------------------------------------------------------------------------------
+static uint32_t q_grid(size_t n, int block)
+{
+  const size_t nb = (n + block - 1) / block;
+  return (uint32_t)(nb < (size_t)Q_MAX_BLOCKS ? (nb ? nb : 1) : Q_MAX_BLOCKS);
+}
+
+size_t query_overflow_entries(size_t n, uint32_t max_depth)
+{
+  // a path holds at most max_depth internal nodes, each pushes at most one entry
+  const int need = (int)max_depth + 1 - Q_SD;
+  if (need <= 0) return 0;
+  const size_t lanes = std::max<size_t>((size_t)q_grid(n, Q_BLOCK) * Q_BLOCK, (size_t)q_grid(n, Q_BLOCK_L) * Q_BLOCK_L);
+  return lanes * (size_t)need;
+}
+
+hipError_t launch_knn(const QueryArgs& a, bool normals, hipStream_t s)
+{
+  if (a.k < 1 || a.k > KNN_MAX_K) return hipErrorInvalidValue;
+  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
+#define KNN_REG(KC)                                                                         \
+  do {                                                                                      \
+    if (normals) hipLaunchKernelGGL((k_knn_reg<KC, true>), g, b, 0, s, a);                  \
+    else hipLaunchKernelGGL((k_knn_reg<KC, false>), g, b, 0, s, a);                         \
+  } while (0)
+  // k = 10 (slam6D) and k = 20 (calc_normals) get lists of exactly their size
+  if (a.k <= 4) KNN_REG(4);
+  else if (a.k <= 10) KNN_REG(10);
+  else if (a.k <= 20) KNN_REG(20);
+  else if (a.k <= 32) KNN_REG(32);
+  else {
+    const dim3 gl(q_grid(a.n, Q_BLOCK_L)), bl(Q_BLOCK_L);
+    if (normals) hipLaunchKernelGGL(k_knn_lds<true>, gl, bl, 0, s, a);
+    else hipLaunchKernelGGL(k_knn_lds<false>, gl, bl, 0, s, a);
+  }
+#undef KNN_REG
+  return hipGetLastError();
+}
+
+hipError_t launch_range_count(const QueryArgs& a, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_range_count, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_range_fill(const QueryArgs& a, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_range_fill, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_range_normals(const QueryArgs& a, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_range_normals, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
+  return hipGetLastError();
+}
+
+// counts [n + 1] (counts[n] == 0) -> exclusive 64-bit offsets [n + 1]: offsets[n] is the total
+size_t range_scan_temp_bytes(size_t n)
+{
+  size_t bytes = 0;
+  (void)rocprim::exclusive_scan(nullptr, bytes, (const uint32_t*)nullptr, (unsigned long long*)nullptr, 0ull, n + 1,
+                                rocprim::plus<unsigned long long>(), (hipStream_t)0);
+  return bytes;
+}
+hipError_t launch_range_scan(const uint32_t* counts, unsigned long long* offsets, size_t n, void* tmp, size_t tmp_bytes,
+                             hipStream_t s)
+{
+  return rocprim::exclusive_scan(tmp, tmp_bytes, counts, offsets, 0ull, n + 1, rocprim::plus<unsigned long long>(), s);
+}
+
+}  // namespace tdtk

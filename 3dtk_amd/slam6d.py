@@ -233,6 +233,46 @@ class KDtree:
                                                 iptr(idx), dptr(d2)))
         return idx, d2
 
+    def kNearestNeighbors(self, p, k, threadNum=0):
+        """kdIndexed.cc:125-161.  Returns the indices of the k nearest points, nearest first (fewer when the tree
+        holds fewer than k points)."""
+        idx, _ = self.kNearestNeighborsBatch(np.asarray(p, dtype=np.float64).reshape(1, 3), k)
+        return [int(i) for i in idx[0] if i >= 0]
+
+    def kNearestNeighborsBatch(self, q, k):
+        """tdtk_knn_search: (idx [K][k], d2 [K][k]); -1 / -1.0 beyond the tree's points"""
+        q = f64(q).reshape(-1, 3)
+        idx = np.empty((len(q), int(k)), np.int32)
+        d2 = np.empty((len(q), int(k)), np.float64)
+        check(lib().tdtk_knn_search(self._h, dptr(q), len(q), int(k), iptr(idx), dptr(d2)))
+        return idx, d2
+
+    def fixedRangeSearch(self, p, sqRad2, threadNum=0):
+        """kdIndexed.cc:215-230.  Returns the indices of every point with Dist2 < sqRad2, in the reference's order."""
+        _, idx, _ = self.fixedRangeSearchBatch(np.asarray(p, dtype=np.float64).reshape(1, 3), sqRad2)
+        return [int(i) for i in idx]
+
+    def fixedRangeSearchBatch(self, q, sqRad2):
+        """tdtk_fixed_range_search as CSR lists: (offsets [K+1] uint64, idx [offsets[K]], d2 [offsets[K]]); query i owns
+        idx[offsets[i]:offsets[i+1]].  Sizes the lists from the first call's total and asks again when they do not fit."""
+        q = f64(q).reshape(-1, 3)
+        offsets = np.zeros(len(q) + 1, np.uint64)
+        total = C.c_uint64(0)
+        cap = max(32 * len(q), 1)
+        while True:
+            idx = np.empty(cap, np.int32)
+            d2 = np.empty(cap, np.float64)
+            rc = lib().tdtk_fixed_range_search(self._h, dptr(q), len(q), float(sqRad2),
+                                               offsets.ctypes.data_as(C.POINTER(C.c_uint64)), iptr(idx), dptr(d2),
+                                               cap, C.byref(total))
+            if rc == 0:
+                break
+            if total.value <= cap:
+                check(rc)
+            cap = int(total.value)
+        n = int(total.value)
+        return offsets, idx[:n].copy(), d2[:n].copy()
+
     def count_visits(self, q, maxdist2):
         q = f64(q).reshape(-1, 3)
         cnt = (C.c_uint64 * 3)()
@@ -588,6 +628,28 @@ def calculateNormalsApxKNN(points, k, rPos, eps, device=0, want_knn=False):
     check(lib().tdtk_normals_apx_knn(dptr(xyz), len(xyz), int(k), dptr(f64(rPos)), float(eps), int(device),
                                      dptr(out), iptr(knn)))
     return (out, knn) if want_knn else out
+
+
+def calculateNormalsKNN(points, k, rPos, bucketSize=20, device=0, want_knn=False):
+    """normals.cc:442-516 (calculateNormalsKNN(normals, points, k, rPos, bucketsize)) on the device: the [n][3] normals in
+    point order (the reference's OpenMP loop appends in completion order; the values are the same) and, with want_knn,
+    the [n][k] lists of the exact k-NN search (nearest first, -1 beyond the cloud's points)."""
+    xyz = f64(points).reshape(-1, 3)
+    out = np.empty_like(xyz)
+    knn = np.empty((len(xyz), int(k)), np.int32) if want_knn else None
+    check(lib().tdtk_normals_knn(dptr(xyz), len(xyz), int(k), dptr(f64(rPos)), int(bucketSize), int(device),
+                                 dptr(out), iptr(knn)))
+    return (out, knn) if want_knn else out
+
+
+def calculateNormalsRange(points, sqRad2, rPos, bucketSize=20, device=0):
+    """normals.cc:369-439 (calculateNormalsRange(normals, points, r2, rPos)) on the device: the PCA over every point's
+    fixed-radius list; [n][3] normals in point order."""
+    xyz = f64(points).reshape(-1, 3)
+    out = np.empty_like(xyz)
+    check(lib().tdtk_normals_range(dptr(xyz), len(xyz), float(sqRad2), dptr(f64(rPos)), int(bucketSize), int(device),
+                                   dptr(out)))
+    return out
 
 
 def read_pose(path):

@@ -29,6 +29,36 @@ inline void calculateNormalsApxKNN_hip(std::vector<Point>& normals, const std::v
   for (size_t i = 0; i < n; i++) normals.push_back(Point(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]));   // normals.cc:105
 }
 
+// calculateNormalsKNN (src/slam6d/normals.cc:442-516) and calculateNormalsRange (normals.cc:369-439) on the GPU
+// (tdtk_normals_knn / tdtk_normals_range): the KDtree over the points, the exact k-NN / fixed-radius lists and
+// calculateNormal's PCA (normals.cc:518-558), every normal bit-identical to the reference's.  Output order: the
+// reference's OpenMP loops append under `omp critical`, i.e. in thread-completion order; these append in point order,
+// which is what calculateNormalsIndexedKNN and a single-thread run give -- the per-point values are the same either way.
+inline void calculateNormalsKNN_hip(std::vector<Point>& normals, const std::vector<Point>& points, const int k,
+                                    const double _rPos[3], int bucketsize = 20, int device = 0)
+{
+  const size_t n = points.size();
+  std::vector<double> xyz(3 * n), nrm(3 * n);
+  for (size_t i = 0; i < n; i++) { xyz[3 * i] = points[i].x; xyz[3 * i + 1] = points[i].y; xyz[3 * i + 2] = points[i].z; }
+  if (tdtk_normals_knn(xyz.data(), n, k, _rPos, bucketsize, device, nrm.data(), 0) != TDTK_OK)
+    throw std::runtime_error(tdtk_last_error());
+  normals.reserve(normals.size() + n);
+  for (size_t i = 0; i < n; i++) normals.push_back(Point(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]));
+}
+
+// (the reference builds this KDtree with its default bucket size, 20)
+inline void calculateNormalsRange_hip(std::vector<Point>& normals, const std::vector<Point>& points, const double r2,
+                                      const double _rPos[3], int bucketsize = 20, int device = 0)
+{
+  const size_t n = points.size();
+  std::vector<double> xyz(3 * n), nrm(3 * n);
+  for (size_t i = 0; i < n; i++) { xyz[3 * i] = points[i].x; xyz[3 * i + 1] = points[i].y; xyz[3 * i + 2] = points[i].z; }
+  if (tdtk_normals_range(xyz.data(), n, r2, _rPos, bucketsize, device, nrm.data()) != TDTK_OK)
+    throw std::runtime_error(tdtk_last_error());
+  normals.reserve(normals.size() + n);
+  for (size_t i = 0; i < n; i++) normals.push_back(Point(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]));
+}
+
 // Where the scan is already resident (adapters/graphSlam6D_hip.h, addition (2): Scan::hipResident()), skip the host
 // round trip: tdtk_scan_calc_normals(scan->hipResident(), K_NEIGHBOURS, scan->get_rPos(), 1.0) computes the normals
 // of the resident points in place and keeps them on the device as the scan's "normal reduced".

@@ -166,6 +166,32 @@ int tdtk_find_closest_dev(const tdtk_tree* t, const double* d_q, size_t K, doubl
 int tdtk_find_closest_along_dir(const tdtk_tree* t, const double* q, const double* dir, size_t K,
                                 double maxdist2, int32_t* idx, double* d2);
 
+/* ---- batched KDtreeIndexed::kNearestNeighbors (kdIndexed.cc:125-161; _KNNSearch kdTreeImpl.h:627-682).  q [K][3] in
+ * the tree frame, host memory.  idx [K][k]: indices into the xyz given to tdtk_tree_create (through the concatenation
+ * for trees from scans), nearest first, ties in the reference's visiting order; d2 (nullable) [K][k] their squared
+ * distances.  A tree of M < k points gives M entries per row, the rest -1 / -1.0.  Errors: k < 1 (TDTK_EINVAL),
+ * k > 64 (TDTK_EUNSUP: the device lists hold at most 64 entries).                                          */
+int tdtk_knn_search(const tdtk_tree* t, const double* q, size_t K, int k, int32_t* idx, double* d2);
+/* batched KDtreeIndexed::fixedRangeSearch (kdIndexed.cc:215-230; _FixedRangeSearch kdTreeImpl.h:585-625): every point
+ * with Dist2 < sqRad2, in the reference's visiting order, as CSR lists.  offsets [K+1] is always filled (query i owns
+ * idx[offsets[i] .. offsets[i+1])) and *total = offsets[K].  When cap < *total nothing else is written and the call
+ * returns TDTK_EINVAL: call again with cap >= *total, the lists are the same.  d2 nullable.  sqRad2 <= 0 gives
+ * empty lists.                                                                                             */
+int tdtk_fixed_range_search(const tdtk_tree* t, const double* q, size_t K, double sqRad2, uint64_t* offsets,
+                            int32_t* idx, double* d2, size_t cap, uint64_t* total);
+/* calculateNormalsKNN (normals.cc:442-516; calculateNormal :518-558): a KDtree(points, bucket) and, for every point, its
+ * k nearest neighbours (itself included), their mean and covariance, the eigenvector of the smallest eigenvalue
+ * (newmat EigenValues), oriented so that n . (p - rPos) >= 0, normalised.  normals_out [n][3] in point order (the
+ * reference's OpenMP loop pushes in completion order; the single-thread order is point order, the values are the
+ * same); knn_out (nullable) [n][k] the lists (-1 beyond n points).  Errors: n == 0, k < 1, bucket < 1 (TDTK_EINVAL);
+ * k > 64 (TDTK_EUNSUP).                                                                                    */
+int tdtk_normals_knn(const double* xyz, size_t n, int k, const double rPos[3], int bucket, int device,
+                     double* normals_out, int32_t* knn_out);
+/* calculateNormalsRange (normals.cc:369-439): the same PCA over every point's fixedRangeSearch list (itself included)
+ * at sqRad2, in visiting order.  Errors: n == 0, bucket < 1, sqRad2 <= 0 (the reference would divide 0 by 0). */
+int tdtk_normals_range(const double* xyz, size_t n, double sqRad2, const double rPos[3], int bucket, int device,
+                       double* normals_out);
+
 /* ---- SearchTree::getPtPairs, DataXYZ overload (src/slam6d/searchTree.cc:92-189), fused
  * with the per-thread Si pass of icp6D::match (icp6D.cc:170-191) and the APX/NAPX/LUM
  * pair loops.  Host buffers.  xyz_r = Target "xyz reduced" [*][3]; normal_r nullable
