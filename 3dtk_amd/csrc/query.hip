@@ -404,7 +404,9 @@ __global__ void __launch_bounds__(Q_BLOCK) k_range_fill(const QueryArgs a_)
 }
 
 // calculateNormalsRange: the list has no upper bound and is not stored -- list_normal's two passes over it are two
-// identical walks (same visits, same order); nr >= 1 because a point finds itself
+// identical walks (same visits, same order).  A point normally finds itself (nr >= 1); where it does not -- coordinates so
+// large that the box test's |q - c| - h rounds by more than the radius and prunes the point's own leaf, as the reference's
+// does -- nr is 0 and the mean is 0 / 0: NaN normals, the reference's calculateNormal on an empty list
 __global__ void __launch_bounds__(Q_BLOCK) k_range_normals(const QueryArgs a_)
 {
   const QueryArgs& a = q_args();

@@ -125,3 +125,121 @@ def test_header_and_exports_name_the_new_entry_points(tdtk):
         assert hasattr(tdtk, fn)
     for m in ("kNearestNeighbors", "kNearestNeighborsBatch", "fixedRangeSearch", "fixedRangeSearchBatch"):
         assert hasattr(tdtk.KDtree, m)
+
+
+# ---- the k9 fixture (tests/golden/make_golden_knn_edges.py): the cases of test_gpu_kdtree_query_edges.py ---------------
+def _me():
+    spec = importlib.util.spec_from_file_location("make_golden_knn_edges", os.path.join(G, "make_golden_knn_edges.py"))
+    me = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(me)
+    return me
+
+
+def _k9():
+    return np.load(os.path.join(G, "k9_kdtree_query_edges.npz"))
+
+
+def test_k9_fixture_equals_the_reference_library(orc):
+    if not orc.have_ref():
+        pytest.skip("oracle/_ref not built (no reference checkout)")
+    me, z = _me(), _k9()
+    got = me.compute(orc)
+    assert sorted(got) == sorted(z.files)
+    for key in z.files:
+        assert got[key].dtype == z[key].dtype and np.array_equal(got[key], z[key]), key
+
+
+def test_k9_fixture_is_no_larger_than_k8():
+    assert os.path.getsize(os.path.join(G, "k9_kdtree_query_edges.npz")) <= os.path.getsize(os.path.join(G, "k8_kdtree_queries.npz"))
+
+
+def _brute_knn(me, pts, Q, knn, k, tag):
+    m = min(k, len(pts))
+    assert knn.shape == (len(Q), k) and (knn[:, m:] == -1).all() and (knn[:, :m] >= 0).all() and (knn < len(pts)).all(), tag
+    for i, q in enumerate(Q):
+        all_d = me.dist2(pts, np.broadcast_to(q, pts.shape), np.arange(len(pts)))
+        assert len(set(knn[i, :m].tolist())) == m, (tag, i)
+        d = all_d[knn[i, :m]]
+        assert np.array_equal(d, np.sort(d)) and np.array_equal(d, np.sort(all_d)[:m]), (tag, i)
+
+
+def _brute_range(me, pts, Q, off, idx, r2, tag):
+    assert off[0] == 0 and off[-1] == len(idx) and len(off) == len(Q) + 1, tag
+    for i, q in enumerate(Q):
+        all_d = me.dist2(pts, np.broadcast_to(q, pts.shape), np.arange(len(pts)))
+        l = idx[int(off[i]):int(off[i + 1])]
+        assert len(set(l.tolist())) == len(l), (tag, i)
+        assert set(l.tolist()) == set(np.nonzero(all_d < r2)[0].tolist()), (tag, i)
+
+
+def test_k9_fixture_agrees_with_brute_force():
+    """as test_fixture_agrees_with_brute_force: the k smallest distances as a sorted multiset, the set d2 < r2"""
+    me, z = _me(), _k9()
+    # deep: lengths only; never longer than the set d2 < r2, equal to it for the queries of the uniform part, and shorter
+    # for own points far out in the geometric part (the reference's box test rounds by more than the radius there)
+    pts, geo = me.deep_cloud()
+    for b in me.DEEP_BUCKETS:
+        _, qs = me.deep_range_queries(pts, geo, me.DEEP_FALLBACK_Q, b)
+        for j, (q, r2) in enumerate(zip(qs, me.DEEP_R2)):
+            cnt = z["deep_b%d_r%d_cnt" % (b, j)]
+            brute = np.array([int((me.dist2(pts, np.broadcast_to(x, pts.shape), np.arange(len(pts))) < r2).sum()) for x in q])
+            assert len(cnt) == len(q) and (cnt <= brute).all(), (b, j)
+            inner = np.abs(q).max(1) <= 50
+            assert inner.sum() >= len(q) // 2 and np.array_equal(cnt[inner], brute[inner]), (b, j)
+    c0 = z["deep_b1_r0_cnt"][:me.DEEP_FALLBACK_Q // 3]
+    assert (c0 == 0).sum() > 10 and (c0 == 1).sum() > 10        # own points of the geometric part: lost, or found alone
+    # table: the leaf of copies as one run in every list that reaches it
+    pts, copies, blob = me.table_cloud()
+    qk, qrs = me.table_queries(pts, blob)
+    for k in me.BAND_KS:
+        _brute_knn(me, pts, qk, z["table_knn%d" % k], k, ("table", k))
+    big = z["table_big"]
+    assert len(big) == me.TABLE_COPIES and set(big.tolist()) == set(copies.tolist())
+    n_big = 0
+    for j, (q, r2) in enumerate(zip(qrs, me.TABLE_R2)):
+        pos = z["table_r%d_pos" % j]
+        off, idx = me.restore_run(z["table_r%d_soff" % j], z["table_r%d_sidx" % j], pos, big)
+        assert np.array_equal(off, z["table_r%d_off" % j])
+        assert not np.isin(z["table_r%d_sidx" % j], copies).any()        # a list holds the copies as that run or not at all
+        _brute_range(me, pts, q, off, idx, r2, ("table", j))
+        n_big += int((pos >= 0).sum())
+    assert 16 <= n_big <= 48
+    # short
+    rows = me.short_rows(z["short_knn"])
+    for M in me.SHORT_MS:
+        pts, Q = me.short_cloud(M)
+        assert len(pts) == M and len(Q) == 12
+        for b in me.SHORT_BUCKETS:
+            for k in me.SHORT_KS:
+                _brute_knn(me, pts, Q, rows[(M, b, k)], k, ("short", M, b, k))
+    # lattice: the stored queries
+    pts, Q = me.lattice_cloud()
+    Q = Q[:me.LATTICE_STORED]
+    for k in me.BAND_KS:
+        per_bucket = me.lattice_unpack_knn(Q, z["lattice_knn%d" % k])
+        assert len(per_bucket) == len(me.LATTICE_BUCKETS)
+        for b, knn in zip(me.LATTICE_BUCKETS, per_bucket):
+            _brute_knn(me, pts, Q, knn, k, ("lattice", b, k))
+    ties = 0
+    for j, r2 in enumerate(me.LATTICE_R2):
+        for b in me.LATTICE_BUCKETS:
+            off = z["lattice_b%d_r%d_off" % (b, j)].astype(np.uint64)
+            _brute_range(me, pts, Q, off, me.lattice_unpack_range(Q, off, z["lattice_b%d_r%d_idx" % (b, j)]), r2, ("lattice", b, r2))
+        ties += sum(int((me.dist2(pts, np.broadcast_to(q, pts.shape), np.arange(len(pts))) == r2).sum()) for q in Q)
+    assert ties > 1000                       # distances equal to r2 exist, and are left out
+    # nonfinite: ordinary rows by brute force; what the reference returned for the others
+    pts, Q, i_ord, i_nan, i_far = me.nonfinite_cloud()
+    assert np.isnan(Q[i_nan]).any(1).all() and not np.isnan(Q[i_far]).any() and np.isfinite(Q[i_ord]).all()
+    assert (np.abs(Q[i_far]).max(1) >= 1e160).all()
+    for k in me.BAND_KS:
+        knn = z["nonfinite_knn%d" % k]
+        _brute_knn(me, pts, Q[i_ord], knn[i_ord], k, ("nonfinite", k))
+        assert (knn[i_nan] == -1).all()
+        assert (knn[i_far] >= 0).all() and all(len(set(r.tolist())) == k for r in knn[i_far])
+    off, idx = z["nonfinite_roff"], z["nonfinite_ridx"]
+    cnt = np.diff(off.astype(np.int64))
+    assert (cnt[i_nan] == 0).all() and (cnt[i_far] == 0).all()
+    sel = np.concatenate([np.arange(int(off[i]), int(off[i + 1])) for i in i_ord]).astype(np.int64)
+    o2 = np.concatenate([[0], np.cumsum(cnt[i_ord])]).astype(np.uint64)
+    assert len(sel) == len(idx)
+    _brute_range(me, pts, Q[i_ord], o2, idx[sel], me.NONFINITE_R2, "nonfinite")
