@@ -1390,17 +1390,24 @@ int tdtk_find_closest(const tdtk_tree* t, const double* q, size_t K, double maxd
 // ---- k-NN and fixed-radius search (query.hip) ------------------------------------------------
 // the K queries at d_q [K][3], spatially binned into WS_QX / WS_QY / WS_QZ (order: sorted position -> caller index), the
 // tree's walk arguments and the stack overflow area
-static int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K, QueryArgs& a)
+// (d_v: a second vector per query [K][3], carried through the bin into WS_DX / WS_DY / WS_DZ -- the cylinder, box and
+// segment queries)
+static int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K, QueryArgs& a, const double* d_v = nullptr)
 {
   int rc;
   int ids[] = {WS_QX, WS_QY, WS_QZ};
   for (int id : ids)
     if ((rc = c->ws[id].ensure(K * sizeof(double)))) return rc;
+  if (d_v) {
+    int vids[] = {WS_DX, WS_DY, WS_DZ};
+    for (int id : vids)
+      if ((rc = c->ws[id].ensure(K * sizeof(double)))) return rc;
+  }
   if ((rc = c->ws[WS_ORDER].ensure(K * sizeof(int32_t)))) return rc;
   if ((rc = c->ws[WS_CELL].ensure(K * sizeof(uint32_t)))) return rc;
   if ((rc = c->ws[WS_HIST].ensure(32768 * sizeof(uint32_t)))) return rc;
   BinArgs b{};
-  b.q = d_q; b.dir = nullptr; b.n = K;
+  b.q = d_q; b.dir = d_v; b.n = K;
   for (int ax = 0; ax < 3; ax++) {
     b.lo[ax] = t->bbmin[ax];
     const double ext = t->bbmax[ax] - t->bbmin[ax];
@@ -1409,9 +1416,11 @@ static int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K
   b.hist = c->ws[WS_HIST].as<uint32_t>();
   b.cell = c->ws[WS_CELL].as<uint32_t>();
   b.sx = c->ws[WS_QX].as<double>(); b.sy = c->ws[WS_QY].as<double>(); b.sz = c->ws[WS_QZ].as<double>();
+  if (d_v) { b.sdx = c->ws[WS_DX].as<double>(); b.sdy = c->ws[WS_DY].as<double>(); b.sdz = c->ws[WS_DZ].as<double>(); }
   b.order = c->ws[WS_ORDER].as<int32_t>();
   HIPCHK(launch_bin(b, c->stream));
   a = QueryArgs{};
+  a.node_r = t->dev.node_r; a.vx = b.sdx; a.vy = b.sdy; a.vz = b.sdz;
   a.nodes = t->dev.nodes; a.pts = t->dev.pts; a.leaf_tab = t->dev.leaf_tab;
   a.root_ref = t->dev.root_ref; a.cb = t->dev.cb; a.cmask = t->dev.cmask;
   a.x = b.sx; a.y = b.sy; a.z = b.sz; a.order = b.order; a.n = K;
@@ -1517,6 +1526,120 @@ int tdtk_fixed_range_search(const tdtk_tree* t, const double* q, size_t K, doubl
   HIPCHK(hipStreamSynchronize(s));
   return TDTK_OK;
 }
+
+}  // extern "C"
+
+// the four list queries of query.hip's shape walks: tdtk_fixed_range_search's contract and workspaces (WS_KPOS the counts,
+// WS_D2 the offsets, WS_ARENA the scan's, WS_IDX the lists), the queries and their second vectors side by side in WS_TMPA
+static int shape_list_query(const char* name, int mode, const tdtk_tree* t, const double* p, const double* v, size_t K,
+                            double maxdist2, uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total)
+{
+  Ctx* c;
+  int rc;
+  if ((rc = get_ctx(t->device, &c))) return rc;
+  offsets[0] = 0; *total = 0;
+  if (K == 0) return TDTK_OK;
+  hipStream_t s = c->stream;
+  const size_t tmpb = range_scan_temp_bytes(K);
+  if ((rc = c->ws[WS_TMPA].ensure(6 * K * sizeof(double)))) return rc;
+  if ((rc = c->ws[WS_KPOS].ensure((K + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = c->ws[WS_D2].ensure((K + 1) * sizeof(unsigned long long)))) return rc;
+  if ((rc = c->ws[WS_ARENA].ensure(tmpb + 256))) return rc;
+  double* dp = c->ws[WS_TMPA].as<double>();
+  double* dv = dp + 3 * K;
+  HIPCHK(hipMemcpyAsync(dp, p, 3 * K * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dv, v, 3 * K * sizeof(double), hipMemcpyHostToDevice, s));
+  QueryArgs a;
+  if ((rc = query_prepare(c, t, dp, K, a, dv))) return rc;
+  a.r2 = maxdist2;
+  a.counts = c->ws[WS_KPOS].as<uint32_t>();
+  unsigned long long* d_off = c->ws[WS_D2].as<unsigned long long>();
+  HIPCHK(hipMemsetAsync(a.counts + K, 0, sizeof(uint32_t), s));
+  HIPCHK(launch_shape_count(a, mode, s));
+  HIPCHK(launch_range_scan(a.counts, d_off, K, c->ws[WS_ARENA].p, tmpb, s));
+  HIPCHK(hipMemcpyAsync(offsets, d_off, (K + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const uint64_t tot = offsets[K];
+  *total = tot;
+  if (cap < tot) {
+    set_error(std::string(name) + ": " + std::to_string(tot) + " points, capacity " + std::to_string(cap) + " (offsets and total are filled)");
+    return TDTK_EINVAL;
+  }
+  if (tot == 0) return TDTK_OK;
+  if (!idx) { set_error("idx is NULL"); return TDTK_EINVAL; }
+  if ((rc = c->ws[WS_IDX].ensure(tot * sizeof(int32_t)))) return rc;
+  a.offsets = d_off;
+  a.idx = c->ws[WS_IDX].as<int32_t>();
+  HIPCHK(launch_shape_fill(a, mode, s));
+  HIPCHK(hipMemcpyAsync(idx, a.idx, tot * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return TDTK_OK;
+}
+
+extern "C" {
+
+int tdtk_fixed_range_search_along_dir(const tdtk_tree* t, const double* p, const double* dir, size_t K, double maxdist2,
+                                      uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total)
+{
+  if (!t || ((!p || !dir) && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
+  return shape_list_query("fixedRangeSearchAlongDir", SHAPE_ALONG_DIR, t, p, dir, K, maxdist2, offsets, idx, cap, total);
+}
+
+int tdtk_fixed_range_search_between(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
+                                    uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total)
+{
+  if (!t || ((!p || !p0) && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
+  return shape_list_query("fixedRangeSearchBetween2Points", SHAPE_BETWEEN, t, p, p0, K, maxdist2, offsets, idx, cap, total);
+}
+
+int tdtk_aabb_search(const tdtk_tree* t, const double* lo, const double* hi, size_t K, uint64_t* offsets, int32_t* idx,
+                     size_t cap, uint64_t* total)
+{
+  if (!t || ((!lo || !hi) && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
+  // kdIndexed.cc:237-238, the comparison in the reference's sense (a NaN corner passes it); nothing is written or launched
+  for (size_t i = 0; i < 3 * K; i++)
+    if (lo[i] > hi[i]) { set_error("invalid bbox"); return TDTK_EINVAL; }
+  return shape_list_query("AABBSearch", SHAPE_AABB, t, lo, hi, K, 0.0, offsets, idx, cap, total);
+}
+
+int tdtk_segment_search_all(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
+                            uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total)
+{
+  if (!t || ((!p || !p0) && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
+  return shape_list_query("segmentSearch_all", SHAPE_SEGMENT, t, p, p0, K, maxdist2, offsets, idx, cap, total);
+}
+
+int tdtk_segment_search_nearest(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
+                                int32_t* idx, double* d2)
+{
+  if (!t || ((!p || !p0 || !idx) && K)) { set_error("NULL argument"); return TDTK_EINVAL; }
+  Ctx* c;
+  int rc;
+  if ((rc = get_ctx(t->device, &c))) return rc;
+  if (K == 0) return TDTK_OK;
+  hipStream_t s = c->stream;
+  if ((rc = c->ws[WS_TMPA].ensure(6 * K * sizeof(double)))) return rc;
+  if ((rc = c->ws[WS_IDX].ensure(K * sizeof(int32_t)))) return rc;
+  if (d2 && (rc = c->ws[WS_TMPB].ensure(K * sizeof(double)))) return rc;
+  double* dp = c->ws[WS_TMPA].as<double>();
+  double* dv = dp + 3 * K;
+  HIPCHK(hipMemcpyAsync(dp, p, 3 * K * sizeof(double), hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(dv, p0, 3 * K * sizeof(double), hipMemcpyHostToDevice, s));
+  QueryArgs a;
+  if ((rc = query_prepare(c, t, dp, K, a, dv))) return rc;
+  a.r2 = maxdist2;
+  a.idx = c->ws[WS_IDX].as<int32_t>();
+  a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
+  HIPCHK(launch_segment_nearest(a, s));
+  HIPCHK(hipMemcpyAsync(idx, a.idx, K * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, K * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return TDTK_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int tdtk_normals_knn(const double* xyz, size_t n, int k, const double rPos[3], int bucket, int device, double* normals_out,
                      int32_t* knn_out)

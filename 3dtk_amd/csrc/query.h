@@ -1,4 +1,5 @@
-// Argument block and launchers of query.hip: k nearest neighbours, fixed-radius search and the normals built on them.
+// Argument block and launchers of query.hip: k nearest neighbours, fixed-radius search, the normals built on them, and the
+// cylinder / box / segment queries.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,13 +28,22 @@ struct QueryArgs {
   double rx, ry, rz;           // normals: the scanner position
   double* normals;             // [n][3], caller order
   int32_t* knn_out;            // k-NN normals: the lists [n][k] (nullable)
+  // cylinder / box / segment queries (r2 is their maxdist2; idx / d2 of the nearest-point query: [n], caller order)
+  const double* node_r;        // bounding-sphere radius per internal node
+  const double *vx, *vy, *vz;  // the query's second vector (dir, p0 or the box's upper corner), sorted like x / y / z
 };
+
+// the four list queries of the shape walks (launch_shape_count / launch_shape_fill)
+enum ShapeMode { SHAPE_ALONG_DIR = 0, SHAPE_BETWEEN = 1, SHAPE_AABB = 2, SHAPE_SEGMENT = 3 };
 
 size_t query_overflow_entries(size_t n, uint32_t max_depth);
 hipError_t launch_knn(const QueryArgs& a, bool normals, hipStream_t s);
 hipError_t launch_range_count(const QueryArgs& a, hipStream_t s);
 hipError_t launch_range_fill(const QueryArgs& a, hipStream_t s);
 hipError_t launch_range_normals(const QueryArgs& a, hipStream_t s);
+hipError_t launch_shape_count(const QueryArgs& a, int mode, hipStream_t s);   // a.counts, as launch_range_count
+hipError_t launch_shape_fill(const QueryArgs& a, int mode, hipStream_t s);    // a.idx at a.offsets, as launch_range_fill
+hipError_t launch_segment_nearest(const QueryArgs& a, hipStream_t s);         // a.idx [n], a.d2 [n] (nullable)
 size_t range_scan_temp_bytes(size_t n);
 hipError_t launch_range_scan(const uint32_t* counts, unsigned long long* offsets, size_t n, void* tmp, size_t tmp_bytes,
                              hipStream_t s);

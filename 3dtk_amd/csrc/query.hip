@@ -1,6 +1,8 @@
-// lib3dtk_hip.so -- k nearest neighbours and fixed-radius search on the resident kd-tree, and the two normal estimators built
-// on them: KDTreeImpl::_KNNSearch (kdTreeImpl.h:627-682), _FixedRangeSearch (kdTreeImpl.h:585-625), calculateNormalsKNN /
-// calculateNormalsRange with calculateNormal's PCA (normals.cc:369-439, 442-516, 518-558).
+// lib3dtk_hip.so -- k nearest neighbours and fixed-radius search on the resident kd-tree, the two normal estimators built
+// on them, and the cylinder, box and segment queries: KDTreeImpl::_KNNSearch (kdTreeImpl.h:627-682), _FixedRangeSearch
+// (kdTreeImpl.h:585-625), calculateNormalsKNN / calculateNormalsRange with calculateNormal's PCA (normals.cc:369-439,
+// 442-516, 518-558), _fixedRangeSearchAlongDir / _fixedRangeSearchBetween2Points / _AABBSearch / _segmentSearch_all /
+// _segmentSearch_1NearestPoint (kdTreeImpl.h:432-577, 747-913).
 //
 // Layout of every kernel here: one query per lane, the queries spatially binned first (launch_bin) so that the lanes of a
 // wave walk neighbouring parts of the tree, a grid-stride loop over the sorted queries, results written straight to the
@@ -29,6 +31,47 @@
 //     child1 under the same condition.  r2 never changes, so the condition is tested when the far child is pushed.
 //   * leaf: every point with Dist2 < r2, in bucket order; the list is in visiting order.
 // Dist2 (globals.icc:238) = (dx*dx + dy*dy) + dz*dz, dx = point - query; fp64 everywhere, FMA contraction off (Makefile).
+//
+// The cylinder, box and segment queries (kdIndexed.cc:164-213, 233-301; kdTreeImpl.h:432-577, 747-913).  p is the query
+// the lanes are binned by, v its second vector (dir, p0 or the box's upper corner); maxdist2 is one value per call.  Len2(x)
+// = (x0*x0 + x1*x1) + x2*x2, Dot(x, y) = (x0*y0 + x1*y1) + x2*y2, sqr(x) = x*x (globals.icc:197-213, 1374), r = the node's
+// bounding-sphere radius (node_r).  Every comparison is kept in the reference's sense ("skip when >=" is not "take when <"
+// once a NaN is involved).  Four of them return lists (count walk, scan, fill walk, as the fixed radius does), one a point.
+//
+// fixedRangeSearchAlongDir (_fixedRangeSearchAlongDir), dir as given -- never normalised:
+//   * internal node: p2c = p - centre; prune when Len2(p2c) - sqr(Dot(p2c, dir)) > sqr(r + sqrt(maxdist2)).
+//   * BOTH children, child1 first when p[axis] < splitval (strict); no plane test: the far child is always pushed.
+//   * leaf: p2p = p - point; every point with Len2(p2p) - sqr(Dot(p2p, dir)) < maxdist2, in bucket order.
+// fixedRangeSearchBetween2Points (_fixedRangeSearchBetween2Points): dist = sqrt(Dist2(p, p0)), dir = p0 - p divided by
+//   sqrt(d0*d0 + d1*d1 + d2*d2) (Normalize3 -- the same value as dist); p == p0 gives a NaN dir and an empty list.
+//   * the method's own node code runs ONLY on the node the walk starts at: it recurses into _fixedRangeSearchAlongDir.  So
+//     the root gets the cylinder test above and then two more, as written in the reference (a squared length plus a
+//     length in the first):  prune when dist > Len2(p0 - centre) + r,  prune when dist > sqrt(Len2(p - centre)) + r.
+//   * everything below the root, and a root that is a leaf: the cylinder walk.
+// AABBSearch (_AABBSearch), box [p, v]; a box with p[i] > v[i] is refused on the host before anything is launched:
+//   * internal node: prune when cx+hx < p0 || cy+hy < p1 || cz+hz < p2 || cx-hx > v0 || cy-hy > v1 || cz-hz > v2.
+//   * splitval > p[axis]: child1, and child2 after it only if splitval < v[axis]; otherwise child2 ALONE.  This is not the
+//     geometric set: a point on the split plane that went to child1 is missed by a box whose lower face lies on the plane,
+//     and the answer depends on the bucket size.  It is the reference's answer.
+//   * leaf: x >= p0 && x <= v0 && y >= p1 && y <= v1 && z >= p2 && z <= v2, in bucket order.
+// The segment queries share their set-up (kdIndexed.cc:252-301): segment_dir = p0 - p, segment_len2 = Len2(dir), segment_n
+//   = dir / len2 (NOT a unit vector: p + t * n is the projection for t = Dot(x - p, dir)), maxdist_d = sqrt(maxdist2).
+//   The comparison point of x (a bucket point or a node centre): t = Dot(x - p, dir);  t < 0: p;  t > len2: p0;  otherwise
+//   p + t * n.  comp_d2(x) = Dist2(comp, x).  With p == p0, n is 0/0: t is 0, the third case applies and comp_d2 is NaN.
+// segmentSearch_all (_segmentSearch_all): segment_center = p + dir*0.5, segment_r2 = sqr(0.5*sqrt(len2) + sqrt(maxdist2)).
+//   * internal node: the box test of segment_center, prune when a >= 0 && a*a >= segment_r2 (a as in the k-NN walk); then
+//     prune when comp_d2(centre) > sqr(r + maxdist_d).
+//   * both children, child1 first when p[axis] < splitval (strict), no plane test.
+//   * leaf: every point with comp_d2(point) < maxdist2 (a NaN comp_d2 takes nothing: p == p0 gives an empty list).
+// segmentSearch_1NearestPoint (_segmentSearch_1NearestPoint): closest_d2 starts at sqr(sqrt(Dist2(p, p0)) + sqrt(maxdist2)).
+//   * internal node: the box test of p, prune when a >= 0 && a*a >= closest_d2 (its value at that moment); then the same
+//     comp_d2(centre) > sqr(r + maxdist_d).
+//   * myd = splitval - p[axis]; myd >= 0: child1 first, otherwise child2; the far child only if sqr(myd) < closest_d2 WHEN
+//     THE NEAR CHILD HAS RETURNED: myd*myd goes on the stack and is tested against the then-current closest_d2 at the pop.
+//   * leaf: a point is skipped when comp_d2(point) >= maxdist2 (a NaN comp_d2 is NOT skipped: p == p0 still finds the nearest
+//     point within the initial closest_d2 = sqr(0 + sqrt(maxdist2))); then newdist2 = Dist2(p, point), taken when < closest_d2 (strict: the
+//     first visited point wins a tie).
+//   * nothing found: index -1 and d2 -1.0 (the reference returns size_t max).
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 
@@ -429,6 +472,252 @@ __global__ void __launch_bounds__(Q_BLOCK) k_range_normals(const QueryArgs a_)
   }
 }
 
+// ---- cylinder, box and segment queries ------------------------------------------------------------------------
+// the segment of the two segment queries with the reference's set-up values, and the three-case comparison point
+struct Segment {
+  double px, py, pz, ex, ey, ez;   // p, p0
+  double dx, dy, dz, len2;         // segment_dir, segment_len2
+  double nx, ny, nz;               // segment_n = dir / len2
+  __device__ __forceinline__ void init(const double px_, const double py_, const double pz_, const double ex_,
+                                       const double ey_, const double ez_)
+  {
+    px = px_; py = py_; pz = pz_; ex = ex_; ey = ey_; ez = ez_;
+    dx = ex - px; dy = ey - py; dz = ez - pz;
+    len2 = (dx * dx + dy * dy) + dz * dz;
+    nx = dx / len2; ny = dy / len2; nz = dz / len2;
+  }
+  // Dist2(comp, x), comp the comparison point of x
+  __device__ __forceinline__ double comp_d2(const double x, const double y, const double z) const
+  {
+    const double ax = x - px, ay = y - py, az = z - pz;
+    const double t = (ax * dx + ay * dy) + az * dz;
+    double cx, cy, cz;
+    if (t < 0.0) { cx = px; cy = py; cz = pz; }
+    else if (t > len2) { cx = ex; cy = ey; cz = ez; }
+    else { cx = px + t * nx; cy = py + t * ny; cz = pz + t * nz; }
+    const double gx = x - cx, gy = y - cy, gz = z - cz;
+    return (gx * gx + gy * gy) + gz * gz;
+  }
+};
+
+// Len2(p2x) - sqr(Dot(p2x, dir)), p2x = p - x (kdTreeImpl.h:507-510, 519-522)
+__device__ __forceinline__ double line_d2(const double px, const double py, const double pz, const double x, const double y,
+                                          const double z, const double ux, const double uy, const double uz, double& len2)
+{
+  const double wx = px - x, wy = py - y, wz = pz - z;
+  len2 = (wx * wx + wy * wy) + wz * wz;
+  const double dot = (wx * ux + wy * uy) + wz * uz;
+  return len2 - dot * dot;
+}
+
+// EMIT(point) for every point of the list of query (p, v), in the reference's visiting order
+template <int MODE, int BLOCK, class EMIT>
+__device__ void shape_walk(const QueryArgs& a, const double px, const double py, const double pz, const double vx,
+                           const double vy, const double vz, LaneStackQ<BLOCK, Q_SD>& st, EMIT& emit)
+{
+  const double md2 = a.r2;
+  const double maxd = __dsqrt_rn(md2);
+  // the cylinder's axis, and Between2Points' dist
+  double ux = vx, uy = vy, uz = vz, dist = 0.0;
+  if (MODE == SHAPE_BETWEEN) {
+    ux = vx - px; uy = vy - py; uz = vz - pz;
+    dist = __dsqrt_rn((ux * ux + uy * uy) + uz * uz);
+    ux /= dist; uy /= dist; uz /= dist;
+  }
+  Segment sg;
+  double scx = 0.0, scy = 0.0, scz = 0.0, sr2 = 0.0;   // segment_center, segment_r2
+  if (MODE == SHAPE_SEGMENT) {
+    sg.init(px, py, pz, vx, vy, vz);
+    scx = px + sg.dx * 0.5; scy = py + sg.dy * 0.5; scz = pz + sg.dz * 0.5;
+    const double sr = 0.5 * __dsqrt_rn(sg.len2) + maxd;
+    sr2 = sr * sr;
+  }
+  bool root = (MODE == SHAPE_BETWEEN);
+  uint32_t cur = a.root_ref;
+  for (;;) {
+    if (cur & REF_LEAF) {
+      uint32_t start, count;
+      leaf_span(a, cur, start, count);
+      for (uint32_t i = 0; i < count; i++) {
+        const KdPoint p = a.pts[start + i];
+        bool take;
+        if (MODE == SHAPE_ALONG_DIR || MODE == SHAPE_BETWEEN) {
+          double unused;
+          take = line_d2(px, py, pz, p.x, p.y, p.z, ux, uy, uz, unused) < md2;
+        } else if (MODE == SHAPE_AABB) {
+          take = p.x >= px && p.x <= vx && p.y >= py && p.y <= vy && p.z >= pz && p.z <= vz;
+        } else {
+          take = sg.comp_d2(p.x, p.y, p.z) < md2;
+        }
+        if (take) emit(p);
+      }
+    } else {
+      const KdNode nd = a.nodes[cur & REF_VAL];
+      bool pruned;
+      if (MODE == SHAPE_ALONG_DIR || MODE == SHAPE_BETWEEN) {
+        const double r = a.node_r[cur & REF_VAL];
+        double len2;
+        const double d2c = line_d2(px, py, pz, nd.cx, nd.cy, nd.cz, ux, uy, uz, len2);
+        const double lim = r + maxd;
+        pruned = d2c > lim * lim;
+        if (MODE == SHAPE_BETWEEN && root && !pruned) {
+          // "check if not between points", as written (kdTreeImpl.h:465-472)
+          const double wx = vx - nd.cx, wy = vy - nd.cy, wz = vz - nd.cz;
+          const double dxp2 = (wx * wx + wy * wy) + wz * wz;
+          if (dist > dxp2 + r) pruned = true;
+          else if (dist > __dsqrt_rn(len2) + r) pruned = true;
+        }
+      } else if (MODE == SHAPE_AABB) {
+        pruned = nd.cx + nd.hx < px || nd.cy + nd.hy < py || nd.cz + nd.hz < pz ||
+                 nd.cx - nd.hx > vx || nd.cy - nd.hy > vy || nd.cz - nd.hz > vz;
+      } else {
+        const double ap = box_dist(nd, scx, scy, scz);
+        pruned = (ap >= 0.0 && ap * ap >= sr2);
+        if (!pruned) {
+          const double lim = a.node_r[cur & REF_VAL] + maxd;
+          pruned = sg.comp_d2(nd.cx, nd.cy, nd.cz) > lim * lim;
+        }
+      }
+      if (!pruned) {
+        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
+        const double pa = (axis == 0) ? px : ((axis == 1) ? py : pz);
+        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2c = nd.c2 & ~REF_AXIS;
+        root = false;
+        if (MODE == SHAPE_AABB) {
+          const double va = (axis == 0) ? vx : ((axis == 1) ? vy : vz);
+          if (nd.splitval > pa) {
+            if (nd.splitval < va) st.push(r2c, 0.0);
+            cur = r1;
+          } else {
+            cur = r2c;
+          }
+        } else {
+          const bool first = pa < nd.splitval;
+          st.push(first ? r2c : r1, 0.0);
+          cur = first ? r1 : r2c;
+        }
+        continue;
+      }
+    }
+    root = false;
+    if (st.sp == 0) break;
+    --st.sp;
+    double unused;
+    st.top(cur, unused);
+  }
+}
+
+// segmentSearch_1NearestPoint: best / bslot are closest_d2 / the bucket slot of closest (0xFFFFFFFF: none)
+template <int BLOCK>
+__device__ void segment_nearest_walk(const QueryArgs& a, const Segment& sg, LaneStackQ<BLOCK, Q_SD>& st, double& best,
+                                     uint32_t& bslot)
+{
+  const double md2 = a.r2;
+  const double maxd = __dsqrt_rn(md2);
+  uint32_t cur = a.root_ref;
+  for (;;) {
+    if (cur & REF_LEAF) {
+      uint32_t start, count;
+      leaf_span(a, cur, start, count);
+      for (uint32_t i = 0; i < count; i++) {
+        const KdPoint p = a.pts[start + i];
+        if (sg.comp_d2(p.x, p.y, p.z) >= md2) continue;
+        const double nd2 = dist2(p, sg.px, sg.py, sg.pz);
+        if (nd2 < best) { best = nd2; bslot = start + i; }
+      }
+    } else {
+      const KdNode nd = a.nodes[cur & REF_VAL];
+      const double ap = box_dist(nd, sg.px, sg.py, sg.pz);
+      bool pruned = (ap >= 0.0 && ap * ap >= best);
+      if (!pruned) {
+        const double lim = a.node_r[cur & REF_VAL] + maxd;
+        pruned = sg.comp_d2(nd.cx, nd.cy, nd.cz) > lim * lim;
+      }
+      if (!pruned) {
+        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
+        const double pa = (axis == 0) ? sg.px : ((axis == 1) ? sg.py : sg.pz);
+        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2c = nd.c2 & ~REF_AXIS;
+        const double myd = nd.splitval - pa;
+        const bool first = myd >= 0.0;
+        st.push(first ? r2c : r1, myd * myd);
+        cur = first ? r1 : r2c;
+        continue;
+      }
+    }
+    // the far child of the innermost open node, if its plane still lies inside closest_d2
+    bool more = false;
+    while (st.sp > 0) {
+      --st.sp;
+      double m2;
+      st.top(cur, m2);
+      if (m2 < best) { more = true; break; }
+    }
+    if (!more) break;
+  }
+}
+
+// first walk of a list query: the length of every list (caller order)
+template <int MODE>
+__global__ void __launch_bounds__(Q_BLOCK) k_shape_count(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  LaneStackQ<Q_BLOCK, Q_SD> st;
+  stack_init<Q_BLOCK>(st, s_stack, a);
+  const size_t T = (size_t)gridDim.x * Q_BLOCK;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+    uint32_t c = 0;
+    auto emit = [&](const KdPoint&) { ++c; };
+    st.sp = 0;
+    shape_walk<MODE, Q_BLOCK>(a, a.x[i], a.y[i], a.z[i], a.vx[i], a.vy[i], a.vz[i], st, emit);
+    a.counts[a.order ? (size_t)a.order[i] : i] = c;
+  }
+}
+
+// second walk, the same visits: every list at its offset
+template <int MODE>
+__global__ void __launch_bounds__(Q_BLOCK) k_shape_fill(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  LaneStackQ<Q_BLOCK, Q_SD> st;
+  stack_init<Q_BLOCK>(st, s_stack, a);
+  const size_t T = (size_t)gridDim.x * Q_BLOCK;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+    const size_t o = a.order ? (size_t)a.order[i] : i;
+    unsigned long long w = a.offsets[o];
+    const unsigned long long end = a.offsets[o + 1];
+    auto emit = [&](const KdPoint& p) {
+      if (w < end) a.idx[w] = p.orig;       // (the count walk made the same visits: never false)
+      ++w;
+    };
+    st.sp = 0;
+    shape_walk<MODE, Q_BLOCK>(a, a.x[i], a.y[i], a.z[i], a.vx[i], a.vy[i], a.vz[i], st, emit);
+  }
+}
+
+__global__ void __launch_bounds__(Q_BLOCK) k_segment_nearest(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  LaneStackQ<Q_BLOCK, Q_SD> st;
+  stack_init<Q_BLOCK>(st, s_stack, a);
+  const size_t T = (size_t)gridDim.x * Q_BLOCK;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+    const size_t o = a.order ? (size_t)a.order[i] : i;
+    Segment sg;
+    sg.init(a.x[i], a.y[i], a.z[i], a.vx[i], a.vy[i], a.vz[i]);
+    const double b0 = __dsqrt_rn(sg.len2) + __dsqrt_rn(a.r2);     // Dist2(p, p0) is Len2(segment_dir), term for term
+    double best = b0 * b0;
+    uint32_t bslot = 0xFFFFFFFFu;
+    st.sp = 0;
+    segment_nearest_walk<Q_BLOCK>(a, sg, st, best, bslot);
+    const bool found = bslot != 0xFFFFFFFFu;
+    a.idx[o] = found ? a.pts[found ? bslot : 0u].orig : -1;
+    if (a.d2) a.d2[o] = found ? best : -1.0;
+  }
+}
+
 // ---- launchers -------------------------------------------------------------------------------------------------
 static uint32_t q_grid(size_t n, int block)
 {
@@ -483,6 +772,38 @@ hipError_t launch_range_fill(const QueryArgs& a, hipStream_t s)
 hipError_t launch_range_normals(const QueryArgs& a, hipStream_t s)
 {
   hipLaunchKernelGGL(k_range_normals, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_shape_count(const QueryArgs& a, int mode, hipStream_t s)
+{
+  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
+  switch (mode) {
+    case SHAPE_ALONG_DIR: hipLaunchKernelGGL(k_shape_count<SHAPE_ALONG_DIR>, g, b, 0, s, a); break;
+    case SHAPE_BETWEEN: hipLaunchKernelGGL(k_shape_count<SHAPE_BETWEEN>, g, b, 0, s, a); break;
+    case SHAPE_AABB: hipLaunchKernelGGL(k_shape_count<SHAPE_AABB>, g, b, 0, s, a); break;
+    case SHAPE_SEGMENT: hipLaunchKernelGGL(k_shape_count<SHAPE_SEGMENT>, g, b, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_shape_fill(const QueryArgs& a, int mode, hipStream_t s)
+{
+  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
+  switch (mode) {
+    case SHAPE_ALONG_DIR: hipLaunchKernelGGL(k_shape_fill<SHAPE_ALONG_DIR>, g, b, 0, s, a); break;
+    case SHAPE_BETWEEN: hipLaunchKernelGGL(k_shape_fill<SHAPE_BETWEEN>, g, b, 0, s, a); break;
+    case SHAPE_AABB: hipLaunchKernelGGL(k_shape_fill<SHAPE_AABB>, g, b, 0, s, a); break;
+    case SHAPE_SEGMENT: hipLaunchKernelGGL(k_shape_fill<SHAPE_SEGMENT>, g, b, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_segment_nearest(const QueryArgs& a, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_segment_nearest, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
   return hipGetLastError();
 }
 

@@ -273,6 +273,80 @@ class KDtree:
         n = int(total.value)
         return offsets, idx[:n].copy(), d2[:n].copy()
 
+    def _shape_lists(self, fn, p, v, *maxdist2):
+        """one of the four CSR list queries (tdtk_fixed_range_search's contract): (offsets [K+1] uint64, idx [offsets[K]]).
+        Sizes the lists from the first call's total and asks again when they do not fit."""
+        p = f64(p).reshape(-1, 3); v = f64(v).reshape(-1, 3)
+        if len(p) != len(v):
+            raise ValueError("%d queries, %d second vectors" % (len(p), len(v)))
+        offsets = np.zeros(len(p) + 1, np.uint64)
+        total = C.c_uint64(0)
+        cap = max(32 * len(p), 1)
+        while True:
+            idx = np.empty(cap, np.int32)
+            rc = fn(self._h, dptr(p), dptr(v), len(p), *[float(m) for m in maxdist2],
+                    offsets.ctypes.data_as(C.POINTER(C.c_uint64)), iptr(idx), cap, C.byref(total))
+            if rc == 0:
+                break
+            if total.value <= cap:
+                check(rc)
+            cap = int(total.value)
+        return offsets, idx[:int(total.value)].copy()
+
+    @staticmethod
+    def _one(a):
+        return np.asarray(a, dtype=np.float64).reshape(1, 3)
+
+    def fixedRangeSearchAlongDir(self, p, direction, maxdist2, threadNum=0):
+        """kdIndexed.cc:195-213.  The indices of every point closer than sqrt(maxdist2) to the line through p along
+        direction (used as given, not normalised), in the reference's order."""
+        return [int(i) for i in self.fixedRangeSearchAlongDirBatch(self._one(p), self._one(direction), maxdist2)[1]]
+
+    def fixedRangeSearchAlongDirBatch(self, p, dirs, maxdist2):
+        """tdtk_fixed_range_search_along_dir as CSR lists: (offsets [K+1] uint64, idx [offsets[K]])"""
+        return self._shape_lists(lib().tdtk_fixed_range_search_along_dir, p, dirs, maxdist2)
+
+    def fixedRangeSearchBetween2Points(self, p, p0, maxdist2, threadNum=0):
+        """kdIndexed.cc:164-192."""
+        return [int(i) for i in self.fixedRangeSearchBetween2PointsBatch(self._one(p), self._one(p0), maxdist2)[1]]
+
+    def fixedRangeSearchBetween2PointsBatch(self, p, p0, maxdist2):
+        """tdtk_fixed_range_search_between as CSR lists"""
+        return self._shape_lists(lib().tdtk_fixed_range_search_between, p, p0, maxdist2)
+
+    def AABBSearch(self, p, p0, threadNum=0):
+        """kdIndexed.cc:233-250: the points the reference's box walk collects for the box [p, p0].  A box with
+        p[i] > p0[i] raises (the reference throws std::logic_error("invalid bbox"))."""
+        return [int(i) for i in self.AABBSearchBatch(self._one(p), self._one(p0))[1]]
+
+    def AABBSearchBatch(self, lo, hi):
+        """tdtk_aabb_search as CSR lists"""
+        return self._shape_lists(lib().tdtk_aabb_search, lo, hi)
+
+    def segmentSearch_all(self, p, p0, maxdist2, threadNum=0):
+        """kdIndexed.cc:252-278.  The indices of every point closer than sqrt(maxdist2) to the segment p .. p0."""
+        return [int(i) for i in self.segmentSearch_allBatch(self._one(p), self._one(p0), maxdist2)[1]]
+
+    def segmentSearch_allBatch(self, p, p0, maxdist2):
+        """tdtk_segment_search_all as CSR lists"""
+        return self._shape_lists(lib().tdtk_segment_search_all, p, p0, maxdist2)
+
+    def segmentSearch_1NearestPoint(self, p, p0, maxdist2, threadNum=0):
+        """kdIndexed.cc:280-301.  Of the points within sqrt(maxdist2) of the segment the one nearest to p, or None
+        (reference: size_t max)."""
+        idx, _ = self.segmentSearch_1NearestPointBatch(self._one(p), self._one(p0), maxdist2)
+        return None if idx[0] < 0 else int(idx[0])
+
+    def segmentSearch_1NearestPointBatch(self, p, p0, maxdist2):
+        """tdtk_segment_search_nearest: (idx [K], d2 [K]); -1 / -1.0 where no point qualifies"""
+        p = f64(p).reshape(-1, 3); p0 = f64(p0).reshape(-1, 3)
+        if len(p) != len(p0):
+            raise ValueError("%d queries, %d end points" % (len(p), len(p0)))
+        idx = np.empty(len(p), np.int32)
+        d2 = np.empty(len(p), np.float64)
+        check(lib().tdtk_segment_search_nearest(self._h, dptr(p), dptr(p0), len(p), float(maxdist2), iptr(idx), dptr(d2)))
+        return idx, d2
+
     def count_visits(self, q, maxdist2):
         q = f64(q).reshape(-1, 3)
         cnt = (C.c_uint64 * 3)()

@@ -179,6 +179,33 @@ int tdtk_knn_search(const tdtk_tree* t, const double* q, size_t K, int k, int32_
  * empty lists.                                                                                             */
 int tdtk_fixed_range_search(const tdtk_tree* t, const double* q, size_t K, double sqRad2, uint64_t* offsets,
                             int32_t* idx, double* d2, size_t cap, uint64_t* total);
+/* ---- the cylinder, box and segment queries of KDtreeIndexed, batched.  Query i is (p[i], v[i]), both [K][3] host memory in
+ * the tree frame; maxdist2 is one value per call.  The four list queries return CSR lists under tdtk_fixed_range_search's
+ * contract: offsets [K+1] and *total are always filled, cap < *total writes nothing else and returns TDTK_EINVAL (the
+ * message names both numbers), K == 0 is a no-op; the lists hold original point indices in the reference's visiting
+ * order.  Degenerate input (p == p0, a zero or non-unit dir, NaN / infinite coordinates) gives the reference's answer. */
+/* KDtreeIndexed::fixedRangeSearchAlongDir (kdIndexed.cc:195-213; _fixedRangeSearchAlongDir kdTreeImpl.h:491-536): every
+ * point closer than sqrt(maxdist2) to the line through p along dir; dir is used as given, not normalised. */
+int tdtk_fixed_range_search_along_dir(const tdtk_tree* t, const double* p, const double* dir, size_t K, double maxdist2,
+                                      uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total);
+/* KDtreeIndexed::fixedRangeSearchBetween2Points (kdIndexed.cc:164-192; _fixedRangeSearchBetween2Points kdTreeImpl.h:
+ * 432-483): the same with dir = (p0 - p) normalised and the reference's two extra tests at the root. */
+int tdtk_fixed_range_search_between(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
+                                    uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total);
+/* KDtreeIndexed::AABBSearch (kdIndexed.cc:233-250; _AABBSearch kdTreeImpl.h:542-577): the points the reference's box walk
+ * collects for the box [lo, hi] -- a subset of the points in the box that depends on the bucket size.  A box with
+ * lo[i] > hi[i] anywhere in the batch: TDTK_EINVAL "invalid bbox" (the reference throws), nothing written or launched. */
+int tdtk_aabb_search(const tdtk_tree* t, const double* lo, const double* hi, size_t K, uint64_t* offsets, int32_t* idx,
+                     size_t cap, uint64_t* total);
+/* KDtreeIndexed::segmentSearch_all (kdIndexed.cc:252-278; _segmentSearch_all kdTreeImpl.h:747-820): every point closer
+ * than sqrt(maxdist2) to the segment p .. p0. */
+int tdtk_segment_search_all(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
+                            uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total);
+/* KDtreeIndexed::segmentSearch_1NearestPoint (kdIndexed.cc:280-301; _segmentSearch_1NearestPoint kdTreeImpl.h:828-913):
+ * of those points the one nearest to p.  idx [K]: its index or -1 (the reference returns size_t max); d2 (nullable) [K]:
+ * its squared distance to p or -1.0. */
+int tdtk_segment_search_nearest(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
+                                int32_t* idx, double* d2);
 /* calculateNormalsKNN (normals.cc:442-516; calculateNormal :518-558): a KDtree(points, bucket) and, for every point, its
  * k nearest neighbours (itself included), their mean and covariance, the eigenvector of the smallest eigenvalue
  * (newmat EigenValues), oriented so that n . (p - rPos) >= 0, normalised.  normals_out [n][3] in point order (the

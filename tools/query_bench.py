@@ -5,8 +5,12 @@ scaled up to the whole cloud; labelled as such).  Prints one JSON line.
 
     python tools/query_bench.py [--sizes 1000000,10000000] [--reps 5] [--ref-queries 100000] [--ref-threads 16]
 
+--segments adds one leg per cylinder / box / segment query at 1M points: 1M queries starting at the cloud's points, segments
+a few point spacings long, maxdist2 (the box's half extent) chosen for about 20 entries per list, each next to the
+reference's method in the same host loop; --only-segments runs nothing else.
+
 Kernel times: run the same command under `rocprofv3 --kernel-trace --stats` (k_knn_reg, k_range_count / k_range_fill,
-k_range_normals)."""
+k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest)."""
 import argparse
 import importlib
 import json
@@ -64,12 +68,83 @@ def ref_legs(pts, r2, tag, rng, nq, threads):
     return res
 
 
+def _ref_loop_lib():
+    import ctypes as C
+    import subprocess
+    import tempfile
+    so = os.path.join(tempfile.mkdtemp(), "ref_query_loop.so")
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-fopenmp", "-fPIC", "-shared",
+                           os.path.join(ROOT, "tools", "ref_query_loop.cc"), "-o", so])
+    return C.CDLL(so)
+
+
+def segment_legs(tdtk, pts, tag, rng, reps, nq, threads):
+    """fixedRangeSearchAlongDir / Between2Points, AABBSearch, segmentSearch_all / _1NearestPoint: the queries start at the
+    cloud's points (density 1 per unit volume), p0 = p + N(0, 1.5) per axis -- segments about 2.4 spacings long.  About 20
+    entries per list: the cylinders run through the whole cloud (pi r^2 x 100 = 20), the segment's capsule has
+    pi r^2 x 2.4 + 4/3 pi r^3 = 20 at r^2 = 1.5, the box is the cube of volume 20 around p."""
+    import ctypes as C
+    out = {}
+    M = len(pts)
+    ext = 100.0 * (M / 1e6) ** (1 / 3)
+    P = pts
+    P0 = pts + rng.normal(0.0, 1.5, pts.shape)
+    d = P0 - P
+    DIR = d / np.sqrt((d * d).sum(1))[:, None]
+    h = 20.0 ** (1 / 3) / 2
+    LO, HI = P - h, P + h
+    md2 = {"along_dir": 20.0 / (np.pi * ext), "between": 20.0 / (np.pi * ext), "segment_all": 1.5, "segment_nearest": 1.5}
+    kd = tdtk.KDtree(pts, 20)
+    legs = {
+        "along_dir": (lambda: kd.fixedRangeSearchAlongDirBatch(P, DIR, md2["along_dir"]), P, DIR),
+        "between": (lambda: kd.fixedRangeSearchBetween2PointsBatch(P, P0, md2["between"]), P, P0),
+        "aabb": (lambda: kd.AABBSearchBatch(LO, HI), LO, HI),
+        "segment_all": (lambda: kd.segmentSearch_allBatch(P, P0, md2["segment_all"]), P, P0),
+        "segment_nearest": (lambda: kd.segmentSearch_1NearestPointBatch(P, P0, md2["segment_nearest"]), P, P0),
+    }
+    for name, (fn, _, _) in legs.items():
+        out["%s_%s" % (name, tag)] = timed(fn, reps)
+        r = fn()
+        if name == "segment_nearest":
+            out["%s_%s_found" % (name, tag)] = round(float((r[0] >= 0).mean()), 4)
+        else:
+            out["%s_%s_mean_list" % (name, tag)] = round(float(r[0][-1]) / M, 2)
+    from oracle import orc
+    if not orc.have_ref() or nq <= 0:
+        return out
+    spec = importlib.util.spec_from_file_location("make_golden_segments",
+                                                  os.path.join(ROOT, "tests", "golden", "make_golden_segments.py"))
+    ms = importlib.util.module_from_spec(spec); spec.loader.exec_module(ms)
+    Lq = _ref_loop_lib()
+    dp = C.POINTER(C.c_double)
+    Lq.ref_pair_query_loop.restype = C.c_double
+    Lq.ref_pair_query_loop.argtypes = [C.c_void_p, C.c_void_p, dp, dp, C.c_size_t, C.c_int, C.c_double, C.c_int,
+                                       C.POINTER(C.c_ulonglong)]
+    t = ms.SegRef(pts, 20)
+    rows = rng.choice(M, nq, replace=False)
+    found = C.c_ulonglong(0)
+    label = "ref_host_%dthreads_%dkq_scaled" % (threads, nq // 1000)
+    kinds = {"along_dir": ("along", 2), "between": ("between", 2), "aabb": ("aabb", 3), "segment_all": ("segall", 2),
+             "segment_nearest": ("near", 4)}
+    for name, (_, A, B) in legs.items():
+        kind, mode = kinds[name]
+        a = np.ascontiguousarray(A[rows]); b = np.ascontiguousarray(B[rows])
+        fn = C.cast(t.fn[kind], C.c_void_p)
+        args = (fn, t.kdi, a.ctypes.data_as(dp), b.ctypes.data_as(dp))
+        Lq.ref_pair_query_loop(*args, min(nq, 2000), mode, float(md2.get(name, 0.0)), threads, C.byref(found))     # warm
+        ms_ = Lq.ref_pair_query_loop(*args, nq, mode, float(md2.get(name, 0.0)), threads, C.byref(found))
+        out["%s_%s_%s_ms" % (label, name, tag)] = round(ms_ * M / nq, 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000000,10000000")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--ref-queries", type=int, default=100000)
     ap.add_argument("--ref-threads", type=int, default=16)
+    ap.add_argument("--segments", action="store_true", help="add the cylinder / box / segment query legs (1M points)")
+    ap.add_argument("--only-segments", action="store_true", help="those legs alone")
     args = ap.parse_args()
     tdtk = importlib.import_module("3dtk_amd")
     if tdtk.device_count() < 1:
@@ -77,6 +152,12 @@ def main():
     out = {"workload": "kdtree_queries", "reps": args.reps}
     rng = np.random.default_rng(2024)
     rpos = [0.0, 0.0, 0.0]
+    if args.segments or args.only_segments:
+        pts = np.random.default_rng(2025).uniform(-50, 50, (1_000_000, 3))
+        out.update(segment_legs(tdtk, pts, "1M", np.random.default_rng(2026), args.reps, args.ref_queries, args.ref_threads))
+        if args.only_segments:
+            print(json.dumps(out))
+            return
     for M in [int(s) for s in args.sizes.split(",")]:
         pts = rng.uniform(-50, 50, (M, 3)) * (M / 1e6) ** (1 / 3)     # same density at every size
         r2 = (20.0 * 3 / (4 * np.pi)) ** (2.0 / 3.0)                   # ~20 neighbours per query at that density
