@@ -4,18 +4,22 @@
 // dual paths.  Everything is fp64 with FMA contraction off (-ffp-contract=off) and the
 // reference's association, because the deliverable is the reference's *indices*, bit for bit.
 //
-// Kernel inventory (DESIGN.md has the roofline of each):
-//   k_search      one lane = one query: near-first DFS over the BFS-flattened tree with an
-//                 explicit per-lane stack in LDS (+ HBM overflow), leaf buckets scanned as
-//                 32-byte records.  Optionally applies the pending ICP transform in place
-//                 first and maps the query into the tree frame.      [hot: ~all the time]
-//   k_search_dir  FindClosestAlongDir variant (bounding-sphere pruning only).
-//   k_accum       streams (query, hit) pairs and reduces the pair sums with wave64
-//                 shuffles -> LDS -> one partial row per workgroup.
-//   k_final       fixed-order reduction of the partial rows (deterministic).
-//   k_transform   Scan::transformReduced on the resident scan.
-//   k_bin_*       counting sort of an unsorted query batch into spatial order.
-//   k_scatter_idx sorted-position hits -> caller-order model indices.
+// What this file holds (DESIGN.md has the roofline of each).  The product launches all of it; what only the lab library (-DTDTK_LAB)
+// builds is in the lab_*.inc files: k_search_coop, k_search_refill2, k_search_step, k_slab_bounds, k_make_fat and the lab's
+// configurations of the kernels below (lab_launch.inc).
+//   search, three families by batch size (launch_search picks; each has a COUNT instantiation that tallies the visits):
+//     k_search_refill  persistent lanes, from 256K queries: a wave owns a slab of sorted queries, a lane that finishes takes the
+//                      next one.  Configured by one type (RefillCfg; the product's: SinglePass).
+//     k_search         one query per lane, 96K..256K queries: near-first DFS, per-lane stack in LDS (+ HBM overflow); also FindClosestAlongDir (DIRMODE)
+//     k_search_g8      four lanes per query, below 96K queries
+//     k_search_refill_multi (LinkPass), k_search_multi, k_search_g8_multi: several batches (a graph-SLAM round's links) in one launch
+//   k_accum, k_accum_multi   stream (query, hit) pairs and reduce the pair sums: wave64 shuffles -> LDS -> one row per workgroup
+//   k_final, k_final_multi   fixed-order reduction of those rows (deterministic)
+//   k_transform, k_transform_chain_batch   Scan::transformReduced on the resident scan; a chain of them for many scans at once
+//   k_bin_count / _scan / _scatter, k_split_soa   counting sort of an unsorted query batch into spatial order
+//   k_scatter_idx, k_skip_from_mask, k_idx_hash, k_found_flags, k_pair_list   results in caller order, the -R mask, the pair list
+//   k_make_hot, k_pad_mark, k_pad_fill   search-side layout of a finished tree: hot node records, padded buckets, fp32 / 16-bit shadows
+//   k_pp_error, k_pp_final   icp6D::Point_Point_Error
 #include <atomic>
 #include <cstdio>
 #include <vector>
@@ -757,9 +761,6 @@ __device__ __forceinline__ void kd_search_dir(const TreeDev& T, const double qx,
   }
 }
 
-#ifdef TDTK_LAB
-#include "lab_part_1.inc"
-#endif
 
 // FUSE (k_search, k_search_g8: the batches too small for the persistent-lane kernel): once the workgroup is through with
 // its chunk of the queries it sums the base pair block of that chunk itself (defined behind wave_sum below), so an
@@ -1239,10 +1240,28 @@ __device__ unsigned long long g_wtrace[3];     // (never touched: a.trace is a l
 
 // the body of k_search_refill for workgroup `bid` of the `nb` that search one batch of queries (the kernel proper and
 // the several-batches-in-one-launch kernel below share it)
-template <int BLOCK, int SD, int THRESH, int WPS, bool COUNT, int FUSE, bool DYN, bool ORDER = !DYN, int PTS = 4, int PROBE = 0, bool FAT = false,
-          int ORD_MAX = 256, bool LAZY = false, int TOP = 0, bool SHARE = false, bool PIPE = false, bool DEFER = false>
+// A configuration of the body is one type whose static members are its seventeen values.  RefillCfg holds the product's defaults;
+// every other configuration derives from it and overrides what it changes: the product's SinglePass and LinkPass (with the launch
+// policy below) and, in the lab library, one derivation per experiment (lab_launch.inc).
+struct RefillCfg {
+  static constexpr int BLOCK = 128, SD = 4;       // threads per workgroup; levels of the traversal stack kept in LDS (REFILL_SD)
+  static constexpr int THRESH = 16, WPS = 4;      // idle lanes a wave collects before it hands out queries; waves per SIMD asked of the compiler (1: its own choice)
+  static constexpr bool COUNT = false;            // tally the visits (above)
+  static constexpr int FUSE = 0;                  // where the pair sums are added up (above; 3 / 5: by each wave over its own slab)
+  static constexpr bool ORDER = true; static constexpr int ORD_MAX = 256;      // a piece of the slab of up to ORD_MAX queries can be handed out expensive queries first
+  static constexpr bool LAZY = false;             // the launch applies queued scan moves itself (SearchArgs::moves)
+  static constexpr bool DEFER = false;            // warm queries defer the quick check (SearchArgs::tie)
+  // lab: slabs drawn from a work queue (above); bucket points per round trip; sensitivity probes 1-3 (extra loads or arithmetic,
+  // result unused); two tree levels per round trip (KdFat); hot records of the upper levels staged in LDS; a workgroup's waves
+  // hand out one slab together; a lane just handed a query becomes one during the same trip
+  static constexpr bool DYN = false, FAT = false, SHARE = false, PIPE = false;
+  static constexpr int PTS = 4, PROBE = 0, TOP = 0;
+};
+template <class CFG>
 __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const uint32_t bid, const uint32_t nb)
 {
+  constexpr int BLOCK = CFG::BLOCK, SD = CFG::SD, THRESH = CFG::THRESH, FUSE = CFG::FUSE, PTS = CFG::PTS, PROBE = CFG::PROBE, ORD_MAX = CFG::ORD_MAX, TOP = CFG::TOP;
+  constexpr bool COUNT = CFG::COUNT, DYN = CFG::DYN, ORDER = CFG::ORDER, FAT = CFG::FAT, LAZY = CFG::LAZY, SHARE = CFG::SHARE, PIPE = CFG::PIPE, DEFER = CFG::DEFER;
   __shared__ uint4 lds_stk[SD][BLOCK];
   // TOP > 0 (round 4): the first TOP hot records -- the tree's upper levels, the array is breadth-first -- are staged in
   // LDS once per workgroup, and a visit of one of them reads LDS instead of the vector L1.  A query's first descent is 17
@@ -2028,17 +2047,17 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   }
 }
 
-template <int BLOCK, int SD, int THRESH, int WPS, bool COUNT, int FUSE, bool DYN, int PTS = 4, int PROBE = 0, bool FAT = false, int TOP = 0, bool SHARE = false, bool PIPE = false,
-          bool DEFER = false>
-__global__ void __launch_bounds__(BLOCK, WPS) k_search_refill(const SearchArgs a_by_value)
+template <class CFG>
+__global__ void __launch_bounds__(CFG::BLOCK, CFG::WPS) k_search_refill(const SearchArgs a_by_value)
 {
+  static_assert(CFG::ORDER == !CFG::DYN && CFG::ORD_MAX == 256 && !CFG::LAZY, "a single-pass configuration");
   // The argument block (three 4x4 fp64 matrices among its 700 bytes) is read through the kernarg segment pointer, not
   // through the by-value parameter: a by-value parameter is known dereferenceable and loop-invariant, so the compiler
   // hoists every field into SGPRs up front -- 106 SGPRs with 80 of them spilled into VGPR lanes in round 2, every use a
   // v_readlane in a kernel that is short of issue slots.  Behind an opaque pointer the fields are s_load'ed where they
   // are used (the matrices only when a lane takes a new query), like k_search_refill_multi reads its table entry.
   (void)a_by_value;
-  search_refill_body<BLOCK, SD, THRESH, WPS, COUNT, FUSE, DYN, !DYN, PTS, PROBE, FAT, 256, false, TOP, SHARE, PIPE, DEFER>(kernarg_block<SearchArgs>(), blockIdx.x, gridDim.x);
+  search_refill_body<CFG>(kernarg_block<SearchArgs>(), blockIdx.x, gridDim.x);
 }
 
 #ifdef TDTK_LAB
@@ -2049,15 +2068,17 @@ __global__ void __launch_bounds__(BLOCK, WPS) k_search_refill(const SearchArgs a
 // batch l with the arguments args[l] (device memory; every base[] a multiple of 8, so a workgroup's XCD is the one its
 // batch-relative index says).  Workgroups are dispatched in order, so the tail of one batch is filled by the next --
 // what several streams give, without depending on how the runtime maps streams to hardware queues.
-template <int BLOCK, int SD, int THRESH, int WPS, bool COUNT, int FUSE, bool ORDER = false, bool PIPE = false>
-__global__ void __launch_bounds__(BLOCK, WPS) k_search_refill_multi(const SearchArgs* __restrict__ args,
+template <class CFG>
+__global__ void __launch_bounds__(CFG::BLOCK, CFG::WPS) k_search_refill_multi(const SearchArgs* __restrict__ args,
                                                                     const uint32_t* __restrict__ base, int nbatch)
 {
+  static_assert(!CFG::DYN && CFG::PTS == 4 && CFG::PROBE == 0 && !CFG::FAT && CFG::ORD_MAX == 320 && CFG::LAZY && CFG::TOP == 0 && !CFG::SHARE && !CFG::DEFER,
+                "a several-links configuration");
   int l = 0;
   while (l + 1 < nbatch && blockIdx.x >= base[l + 1]) ++l;
   l = __builtin_amdgcn_readfirstlane(l);
   const uint32_t b0 = base[l], b1 = base[l + 1];
-  search_refill_body<BLOCK, SD, THRESH, WPS, COUNT, FUSE, false, ORDER, 4, 0, false, 320, true, 0, false, PIPE>(args[l], blockIdx.x - b0, b1 - b0);
+  search_refill_body<CFG>(args[l], blockIdx.x - b0, b1 - b0);
 }
 
 #ifdef TDTK_LAB
@@ -2520,7 +2541,7 @@ constexpr int SEARCH_SD_MIN = 4;  // overflow area is sized for the shallowest L
 //   9 / 10 / 11: eight / four / sixteen lanes per query (k_search_g8); four is the default below 96K queries
 //  20: persistent lanes, 256 queries per wave, 128-thread workgroups
 //  40: persistent lanes, one loop in which every lane takes one step per trip (k_search_step, "if-if")
-//  30: persistent lanes fed from a work queue (k_search_refill<.., DYN>): resident waves draw 64-query slabs
+//  30: persistent lanes fed from a work queue (k_search_refill<LabQueue>, DYN): resident waves draw 64-query slabs
 // (the TDTK_* knobs are read on every launch: a getenv is nothing beside a launch, and tests / probes flip them
 // inside one process)
 static int search_variant()
@@ -2604,95 +2625,6 @@ static uint32_t refill_grid_b(size_t n, int block, int* qpw_out, int side_by_sid
   *qpw_out = (int)qpw;
   return (uint32_t)nb;
 }
-#ifdef TDTK_LAB
-static uint32_t refill_grid_b_fwd(size_t n, int* qpw_out) { return refill_grid_b(n, 128, qpw_out); }
-#endif
-// Upper tree levels in LDS (search_refill_body<.., TOP>): the workgroup size of the single-pass launch that stages them,
-// 0 = the plain 128-thread kernel.  Only while the launch is ONE generation of resident waves: a big workgroup leaves
-// its CU when its slowest wave does, which costs nothing when nobody is waiting for the CU.
-// MEASURED NEGATIVE (lab only, TDTK_TOP_BLOCK=512|1024): 1M-vs-1M k_search 0.2041-0.2047 ms (1024) / 0.2071-0.2080 (512)
-// against 0.1933-0.1945; the upper levels' visits coalesce in the vector L1 anyway -- a wave's sorted queries share their
-// first ten nodes -- so LDS takes little off the tag pipeline and the mixed trips pay for two paths.
-static int refill_top_block(size_t n, int side_by_side)
-{
-#ifdef TDTK_LAB
-  const char* e = lab_env("TDTK_TOP_BLOCK");
-  const int blk = e ? atoi(e) : 0;
-  if (blk != 128 && blk != 512 && blk != 1024) return 0;      // (128: seven levels per 128-thread workgroup; TDTK_TOP_LEVELS=0 with 1024: no staging, the workgroup size alone)
-  if (side_by_side > 1 || (n + 255) / 256 >= (size_t)num_cu() * 4 * 7) return 0;
-  if (lab_env("TDTK_REFILL_POOL") || lab_env("TDTK_BUCKET_PTS") || lab_env("TDTK_FAT_NODES") || lab_env("TDTK_WAVE_TRACE") || lab_env("TDTK_REFILL_THRESH") ||
-      lab_env("TDTK_TWO_PER_LANE") || lab_env("TDTK_FUSE_SUMS") || lab_env("TDTK_SEARCH_VARIANT") || lab_env("TDTK_REFILL_QPW"))
-    return 0;
-  return blk;
-#else
-  (void)n; (void)side_by_side;
-  return 0;
-#endif
-}
-// Slabs handed out by the workgroup's waves together (search_refill_body<.., SHARE>): the workgroup size of the single-pass
-// launch, 0 = every wave for itself (128-thread workgroups).  While the launch is ONE generation of resident waves.
-// MEASURED NEGATIVE (lab only, TDTK_SHARE_BLOCK=256|512|1024): 1M-vs-1M k_search 0.2075-0.2085 / 0.2171-0.2179 / 0.2121-0.2131 ms
-// against 0.1945-0.1956: the waves of a big workgroup sit on ONE CU and share its vector L1, which is what the kernel is
-// bound by (TCP busy 80-91 % of the launch, profiles/r04_tcp_diag.txt); 128-thread workgroups spread a CU's sixteen waves
-// over eight distant stretches of the scan, and that averaging is worth more than what the shared cursor evens out.
-static int refill_share_block(size_t n, int side_by_side)
-{
-#ifndef TDTK_LAB
-  (void)n; (void)side_by_side;
-  return 0;
-#endif
-  int blk = 0;
-  if (const char* e = lab_env("TDTK_SHARE_BLOCK")) blk = atoi(e);
-  if (blk != 256 && blk != 512 && blk != 1024) return 0;
-  if (side_by_side > 1 || (n + 255) / 256 >= (size_t)num_cu() * 4 * 7) return 0;
-  if (lab_env("TDTK_REFILL_POOL") || lab_env("TDTK_BUCKET_PTS") || lab_env("TDTK_FAT_NODES") || lab_env("TDTK_WAVE_TRACE") || lab_env("TDTK_REFILL_THRESH") ||
-      lab_env("TDTK_TWO_PER_LANE") || lab_env("TDTK_FUSE_SUMS") || lab_env("TDTK_SEARCH_VARIANT") || lab_env("TDTK_REFILL_QPW") || lab_env("TDTK_TOP_BLOCK") ||
-      lab_env("TDTK_REFILL_PHASES") || lab_env("TDTK_BALANCE"))
-    return 0;
-  return blk;
-}
-// lab (TDTK_SINGLE_BLOCK=64): the single-pass launch in workgroups of ONE wave (a CU's sixteen waves then come from sixteen
-// distant stretches of the scan instead of eight)
-static int refill_single64(size_t n, int side_by_side)
-{
-#ifdef TDTK_LAB
-  const char* e = lab_env("TDTK_SINGLE_BLOCK");
-  if (!(e && atoi(e) == 64)) return 0;
-  if (side_by_side > 1 || (n + 255) / 256 >= (size_t)num_cu() * 4 * 7) return 0;
-  if (lab_env("TDTK_REFILL_POOL") || lab_env("TDTK_BUCKET_PTS") || lab_env("TDTK_FAT_NODES") || lab_env("TDTK_WAVE_TRACE") || lab_env("TDTK_REFILL_THRESH") ||
-      lab_env("TDTK_TWO_PER_LANE") || lab_env("TDTK_FUSE_SUMS") || lab_env("TDTK_SEARCH_VARIANT") || lab_env("TDTK_REFILL_QPW") || lab_env("TDTK_TOP_BLOCK") ||
-      lab_env("TDTK_REFILL_PHASES") || lab_env("TDTK_BALANCE") || lab_env("TDTK_SHARE_BLOCK") || lab_env("TDTK_PIPE"))
-    return 0;
-  return 64;
-#else
-  (void)n; (void)side_by_side;
-  return 0;
-#endif
-}
-// the workgroup size of the single-pass persistent-lane launch for n queries (128 unless one of the two above applies)
-static int refill_big_block(size_t n, int side_by_side)
-{
-  if (const int tb = refill_top_block(n, side_by_side)) return tb;
-  return refill_share_block(n, side_by_side);
-}
-size_t search_max_lanes(size_t n)
-{
-  int q;
-  {
-    const int tb = refill_big_block(n, 1);
-    if (tb) {
-      const size_t t = (size_t)refill_grid_b(n, tb, &q) * (size_t)tb;
-      const size_t a0 = (size_t)search_grid(n) * SEARCH_BLOCK, b0 = (size_t)refill_grid_b(n, 128, &q) * 128;
-      return std::max(t, std::max(a0, b0));
-    }
-  }
-  const size_t a = (size_t)search_grid(n) * SEARCH_BLOCK;
-  const size_t b = std::max((size_t)refill_grid_b(n, 128, &q) * 128, (size_t)refill_grid_b(n, 64, &q) * 64);
-  const size_t c = (size_t)refill_grid_b(n, SEARCH_BLOCK, &q) * SEARCH_BLOCK;
-  const size_t d = (size_t)num_cu() * 4 * 8 * WAVE;     // the work-queue kernel: at most every wave slot of the chip
-  const size_t m1 = a > b ? a : b, m2 = c > d ? c : d;
-  return m1 > m2 ? m1 : m2;
-}
 static uint32_t g8_grid(size_t n)
 {
   size_t nb = (n + 31) / 32;            // 32 queries (groups of 8 lanes) per 256-thread workgroup
@@ -2749,34 +2681,6 @@ static int refill_pool_pct(size_t n, int side_by_side)
   return v;
 }
 bool search_uses_queue(size_t n) { return pick_variant(n) == 30 || (pick_variant(n) == 20 && refill_pool_pct(n, 1) > 0); }
-#ifdef TDTK_LAB
-#include "lab_part_2.inc"
-#endif
-uint32_t search_fused_rows(size_t n, int side_by_side)
-{
-  const int v = pick_variant(n);
-  if (v == 10) return g8_grid4(n);
-  if (v == 4) return search_grid(n);
-  int q;
-#ifdef TDTK_LAB
-  if (two_per_lane_for(n, side_by_side)) return refill2_grid(n, &q);
-#endif
-  if (const int tb = refill_big_block(n, side_by_side)) return refill_grid_b(n, tb, &q, side_by_side) * (uint32_t)(tb / 128);
-  if (refill_single64(n, side_by_side)) return refill_grid_b(n, 64, &q, side_by_side);
-  return refill_grid_b(n, 128, &q, side_by_side);
-}
-
-// pipelined hand-out (search_refill_body<.., PIPE>), lab only (TDTK_PIPE=1).  MEASURED NEGATIVE: parity-green, and the bucket
-// scan -- where the register demand peaks -- finds 8-9 more registers live with it (phi copies of the query registers the
-// staged loads land in): 134 VGPRs = three waves per SIMD, or at 128 nine spilled registers in hot code: 1M-vs-1M k_search
-// 0.2348 ms against 0.1954-0.1959, one lum6DEuler round of 84 links 13.9 ms against 10.5.
-#ifdef TDTK_LAB
-static bool pipe_on()
-{
-  if (const char* e = lab_env("TDTK_PIPE")) return e[0] == '1';
-  return false;
-}
-#endif
 // waves of the single-pass persistent-lane kernel (the FUSE 3 instantiation the ICP loop runs) a SIMD holds at once, by the
 // runtime's own occupancy calculation for this code object (registers, LDS); 4 if it cannot say
 // (round 5, second step: SIX.  The compiler is asked for six waves per SIMD -- __launch_bounds__' second argument, 80 VGPRs --
@@ -2795,11 +2699,28 @@ constexpr int MULTI_WPS = TDTK_MULTI_WPS;
 #endif
 template <bool COUNT, int FUSE>
 constexpr int REFILL_WPS = COUNT ? 4 : ((FUSE == 0 || FUSE == 3) ? TDTK_REFILL_WPS : 1);
+// ---- the product's configurations of the persistent-lane kernels (RefillCfg: the defaults; the lab's: lab_launch.inc) ----
+// the single pass: 128 threads, static slabs that can be handed out expensive queries first, the plain walk
+template <int THRESH_, bool COUNT_, int FUSE_, bool DEFER_>
+struct SinglePass : RefillCfg {
+  static_assert((THRESH_ == 16 || THRESH_ == 32) && (FUSE_ == 0 || FUSE_ == 3), "the lab's values have configurations of their own");
+  static constexpr int SD = REFILL_SD<FUSE_>, THRESH = THRESH_, WPS = REFILL_WPS<COUNT_, FUSE_>, FUSE = FUSE_;
+  static constexpr bool COUNT = COUNT_, DEFER = DEFER_;
+};
+// several links per launch: 128 threads, lazy scan moves, half slabs of up to 320 queries ordered where ORDER_ says so
+template <int THRESH_, bool COUNT_, int FUSE_, bool ORDER_, int WPS_>
+struct LinkPass : RefillCfg {
+  static_assert((THRESH_ == 16 || THRESH_ == 32) && (FUSE_ == 0 || FUSE_ == 5) && (WPS_ == 4 || WPS_ == MULTI_WPS), "the lab's values have configurations of their own");
+  static constexpr int SD = MULTI_SD, THRESH = THRESH_, WPS = WPS_, FUSE = FUSE_, ORD_MAX = 320;
+  static constexpr bool COUNT = COUNT_, ORDER = ORDER_, LAZY = true;
+};
+template <class CFG> static void launch_refill(uint32_t nb, unsigned lds, hipStream_t s, const SearchArgs& a) { hipLaunchKernelGGL((k_search_refill<CFG>), dim3(nb), dim3(CFG::BLOCK), lds, s, a); }
+template <class CFG> static void launch_refill_multi(uint32_t nb, hipStream_t s, const SearchArgs* d_args, const uint32_t* d_base, int nbatch) { hipLaunchKernelGGL((k_search_refill_multi<CFG>), dim3(nb), dim3(CFG::BLOCK), 0, s, d_args, d_base, nbatch); }
 static int refill_waves_per_simd()
 {
   static const int w = [] {
     int blocks = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(&k_search_refill<128, 4, 16, REFILL_WPS<false, 3>, false, 3, false>), 128, 0) != hipSuccess) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(&k_search_refill<SinglePass<16, false, 3, false>>), 128, 0) != hipSuccess) {
       (void)hipGetLastError();
       return 4;
     }
@@ -2808,31 +2729,39 @@ static int refill_waves_per_simd()
   }();
   return w;
 }
+#ifdef TDTK_LAB
+#include "lab_launch.inc"   // the lab's configurations, grids and launches: what the hooks below call
+#endif
+size_t search_max_lanes(size_t n)
+{
+#ifdef TDTK_LAB
+  if (const size_t lanes = lab_max_lanes(n)) return lanes;
+#endif
+  int q;
+  const size_t a = (size_t)search_grid(n) * SEARCH_BLOCK;
+  const size_t b = std::max((size_t)refill_grid_b(n, 128, &q) * 128, (size_t)refill_grid_b(n, 64, &q) * 64);
+  const size_t c = (size_t)refill_grid_b(n, SEARCH_BLOCK, &q) * SEARCH_BLOCK;
+  const size_t d = (size_t)num_cu() * 4 * 8 * WAVE;     // the work-queue kernel: at most every wave slot of the chip
+  return std::max(std::max(a, b), std::max(c, d));
+}
+uint32_t search_fused_rows(size_t n, int side_by_side)
+{
+  const int v = pick_variant(n);
+  if (v == 10) return g8_grid4(n);
+  if (v == 4) return search_grid(n);
+#ifdef TDTK_LAB
+  if (const uint32_t rows = lab_fused_rows(n, side_by_side)) return rows;
+#endif
+  int q;
+  return refill_grid_b(n, 128, &q, side_by_side);
+}
 template <bool COUNT, int FUSE>
 static void launch_refill128(SearchArgs& a, hipStream_t s)
 {
+#ifdef TDTK_LAB
+  if (lab_refill_own_grid<COUNT, FUSE>(a, s)) return;
+#endif
   int qpw;
-#ifdef TDTK_LAB
-  if constexpr (FUSE == 0 || FUSE == 3) {
-    if (const int tb = a.bounds ? 0 : refill_top_block(a.n, a.side_by_side)) {
-      const uint32_t nbt = refill_grid_b(a.n, tb, &qpw, a.side_by_side);
-      a.qpw = qpw; a.phases = 1; a.pool_slab = 0; a.region = 0; a.trace = 0;
-      const char* lv = lab_env("TDTK_TOP_LEVELS");
-      if (tb == 1024 && lv && lv[0] == '0') hipLaunchKernelGGL((k_search_refill<1024, 4, 16, 4, COUNT, FUSE, false, 4, 0, false, 0>), dim3(nbt), dim3(1024), 0, s, a);
-      else if (tb == 128) hipLaunchKernelGGL((k_search_refill<128, 4, 16, 4, COUNT, FUSE, false, 4, 0, false, 127>), dim3(nbt), dim3(128), 0, s, a);
-      else
-      if (tb == 1024) hipLaunchKernelGGL((k_search_refill<1024, 4, 16, 4, COUNT, FUSE, false, 4, 0, false, 1023>), dim3(nbt), dim3(1024), 0, s, a);
-      else hipLaunchKernelGGL((k_search_refill<512, 4, 16, 4, COUNT, FUSE, false, 4, 0, false, 511>), dim3(nbt), dim3(512), 0, s, a);
-      return;
-    }
-  }
-#endif
-#ifdef TDTK_LAB
-#include "lab_part_3.inc"
-#endif
-#ifdef TDTK_LAB
-#include "lab_part_4.inc"
-#endif
   const uint32_t nb = refill_grid_b(a.n, 128, &qpw, a.side_by_side);
   a.qpw = qpw;
   // Two pieces when every wave of the launch is resident at once (the XCD's waves then move through its eighth of the
@@ -2869,46 +2798,22 @@ static void launch_refill128(SearchArgs& a, hipStream_t s)
   while (ph > 1 && (qpw % (ph * 16)) != 0) --ph;   // pieces stay multiples of 16 queries
   a.phases = ph;
   // diagnostics: TDTK_OCC_LDS=<bytes> of unused dynamic LDS per workgroup caps the waves resident per SIMD (how the launch
-  // time depends on occupancy alone); TDTK_BUCKET_PTS=8 scans buckets eight points per round trip instead of four
+  // time depends on occupancy alone)
   static const unsigned occ_lds = [] { const char* e = lab_env("TDTK_OCC_LDS"); return e ? (unsigned)atoi(e) : 0u; }();
-  const char* pe = lab_env("TDTK_BUCKET_PTS");
-  const int bpts = pe ? atoi(pe) : 4;
-  // the instantiation whose warm queries defer the quick check (SearchArgs::tie): a repeated pass over a tree that has the
-  // split halves and the 16-bit shadow; everything else -- every cold pass -- runs the kernel without that machinery
-  constexpr int SD_ = REFILL_SD<FUSE>;
-  const bool defer_ok = (FUSE == 0 || FUSE == 3) && a.warm && a.tie > 0.0 && a.T.split != nullptr && a.T.q16 != nullptr && BUCKET_Q16;
+  bool launched = false;
 #ifdef TDTK_LAB
-  if (!COUNT && FUSE == 0 && bpts == 8 && refill_thresh(a.n) == 16) {
-    hipLaunchKernelGGL((k_search_refill<128, SD_, 16, 1, false, 0, false, 8>), dim3(nb), dim3(128), occ_lds, s, a);
-  } else if (!COUNT && FUSE == 0 && bpts == 41 && refill_thresh(a.n) == 16) {
-    hipLaunchKernelGGL((k_search_refill<128, SD_, 16, 1, false, 0, false, 4, 1>), dim3(nb), dim3(128), occ_lds, s, a);
-  } else if (!COUNT && FUSE == 0 && bpts == 42 && refill_thresh(a.n) == 16) {
-    hipLaunchKernelGGL((k_search_refill<128, SD_, 16, 1, false, 0, false, 4, 2>), dim3(nb), dim3(128), occ_lds, s, a);
-  } else if (!COUNT && FUSE == 0 && bpts == 43 && refill_thresh(a.n) == 16) {
-    hipLaunchKernelGGL((k_search_refill<128, SD_, 16, 1, false, 0, false, 4, 3>), dim3(nb), dim3(128), occ_lds, s, a);
-  } else if (!COUNT && FUSE == 0 && refill_thresh(a.n) == 16 && a.T.fat != nullptr && lab_env("TDTK_FAT_NODES") && lab_env("TDTK_FAT_NODES")[0] == '1') {
-    // two tree levels per round trip (KdFat): a measured negative, kept selectable -- see the comment at the walk
-    hipLaunchKernelGGL((k_search_refill<128, SD_, 16, 1, false, 0, false, 4, 0, true>), dim3(nb), dim3(128), occ_lds, s, a);
-  } else
+  launched = lab_refill_on_grid<COUNT, FUSE>(a, nb, occ_lds, s);
 #endif
-  switch (refill_thresh(a.n)) {
-#ifdef TDTK_LAB
-    case 8: hipLaunchKernelGGL((k_search_refill<128, SD_, 8, 1, COUNT, FUSE, false>), dim3(nb), dim3(128), occ_lds, s, a); break;
-#endif
-    case 32:
-      if (defer_ok) hipLaunchKernelGGL((k_search_refill<128, SD_, 32, REFILL_WPS<COUNT, FUSE>, COUNT, FUSE, false, 4, 0, false, 0, false, false, (FUSE == 0 || FUSE == 3)>), dim3(nb), dim3(128), occ_lds, s, a);
-      else hipLaunchKernelGGL((k_search_refill<128, SD_, 32, REFILL_WPS<COUNT, FUSE>, COUNT, FUSE, false>), dim3(nb), dim3(128), occ_lds, s, a);
-      break;
-    default:
-#ifdef TDTK_LAB
-      if ((FUSE == 0 || FUSE == 3) && pipe_on() && !a.skip)
-        hipLaunchKernelGGL((k_search_refill<128, SD_, 16, 4, COUNT, (FUSE == 3 ? 3 : 0), false, 4, 0, false, 0, false, true>), dim3(nb), dim3(128), occ_lds, s, a);
-      else
-#endif
-      if (defer_ok) hipLaunchKernelGGL((k_search_refill<128, SD_, 16, REFILL_WPS<COUNT, FUSE>, COUNT, FUSE, false, 4, 0, false, 0, false, false, (FUSE == 0 || FUSE == 3)>), dim3(nb), dim3(128), occ_lds, s, a);
-      else
-      hipLaunchKernelGGL((k_search_refill<128, SD_, 16, REFILL_WPS<COUNT, FUSE>, COUNT, FUSE, false>), dim3(nb), dim3(128), occ_lds, s, a);
-      break;
+  if constexpr (FUSE == 0 || FUSE == 3) {      // (every other FUSE is the lab's, and launched above)
+    // SinglePass<THRESH, COUNT, FUSE, DEFER>.  DEFER: the instantiation whose warm queries defer the quick check (SearchArgs::tie): a repeated pass over a tree that has
+    // the split halves and the 16-bit shadow; everything else -- every cold pass -- runs the kernel without that machinery
+    const bool defer = a.warm && a.tie > 0.0 && a.T.split != nullptr && a.T.q16 != nullptr && BUCKET_Q16;
+    const bool thresh32 = refill_thresh(a.n) == 32;
+    if (launched) {}      // (by the lab's hook)
+    else if (thresh32 && defer) launch_refill<SinglePass<32, COUNT, FUSE, true>>(nb, occ_lds, s, a);
+    else if (thresh32) launch_refill<SinglePass<32, COUNT, FUSE, false>>(nb, occ_lds, s, a);
+    else if (defer) launch_refill<SinglePass<16, COUNT, FUSE, true>>(nb, occ_lds, s, a);
+    else launch_refill<SinglePass<16, COUNT, FUSE, false>>(nb, occ_lds, s, a);
   }
   if (kLab && a.trace) {
     (void)hipStreamSynchronize(s);
@@ -2919,10 +2824,6 @@ static void launch_refill128(SearchArgs& a, hipStream_t s)
         fprintf(stderr, "WTRACE %u %u %llu %llu %llu\n", w / 2u, w % 2u, h[3 * w + 2], h[3 * w], h[3 * w + 1]);
   }
 }
-
-#ifdef TDTK_LAB
-#include "lab_part_5.inc"
-#endif   // TDTK_LAB
 
 // a.fuse != 0 (only where search_can_fuse(a.n)): the base pair sums come out of the search itself, one row of
 // ACC_TOTAL per workgroup in a.partials (search_fused_rows(a.n) rows) -- follow with launch_final.
@@ -2948,56 +2849,23 @@ hipError_t launch_search(const SearchArgs& a_in, uint32_t grid, int dirmode, boo
     // lane (4), four lanes per query (10) -- and their instrumented instantiations
     if (!kLab && v == 20 && !(a.fuse == 0 || a.fuse == 3)) return hipErrorInvalidValue;
 #ifdef TDTK_LAB
-    if (v == 30 && (!a.q_ctr || !a.q_ctr_next)) return hipErrorInvalidValue;
+    hipError_t lab_err;
+    if (lab_launch_search(a, v, count, g, s, &lab_err)) return lab_err;
 #endif
     if (count) {
       // the instrumented instantiation of whatever this batch would get: same traversal, same warm radius
-      if (v == 20) {
-        if (a.fuse == 3) launch_refill128<true, 3>(a, s);
-#ifdef TDTK_LAB
-        else if (a.fuse == 2) launch_refill128<true, 2>(a, s);
-        else if (a.fuse) launch_refill128<true, 1>(a, s);
-#endif
-        else launch_refill128<true, 0>(a, s);
-      }
-#ifdef TDTK_LAB
-      else if (v == 30) launch_stream128<true>(a, s);
-      else if (v == 40) launch_step128<true, false>(a, s);
-      else if (v == 41) launch_step128<true, true>(a, s);
-#endif
+      if (v == 20 && a.fuse == 3) launch_refill128<true, 3>(a, s);
+      else if (v == 20) launch_refill128<true, 0>(a, s);
       else hipLaunchKernelGGL((k_search<SEARCH_BLOCK, 8, true, 0, false, 1>), g, b, 0, s, a);
-      return hipGetLastError();
-    }
-    switch (v) {
-#ifdef TDTK_LAB
-#include "lab_part_6.inc"
-#endif
-      case 20:
-        if (a.fuse == 3) launch_refill128<false, 3>(a, s);
-#ifdef TDTK_LAB
-        else if (a.fuse == 2) launch_refill128<false, 2>(a, s);
-        else if (a.fuse) launch_refill128<false, 1>(a, s);
-#endif
-        else launch_refill128<false, 0>(a, s);
-        break;
-      case 10:
-#ifdef TDTK_LAB
-        if (a.loop) {
-          if (!a.fuse) return hipErrorInvalidValue;
-          hipLaunchKernelGGL((k_search_g8<256, 16, 4, true, true>), dim3(g8_grid4(a.n)), dim3(256), 0, s, a);
-          break;
-        }
-#endif
-        if (a.fuse) hipLaunchKernelGGL((k_search_g8<256, 16, 4, true>), dim3(g8_grid4(a.n)), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_search_g8<256, 16, 4>), dim3(g8_grid4(a.n)), dim3(256), 0, s, a);
-        break;
-      default:
-#ifdef TDTK_LAB
-        if (a.loop) return hipErrorInvalidValue;      // (the host-free loop is the four-lanes-per-query family's alone)
-#endif
-        if (a.fuse) hipLaunchKernelGGL((k_search<SEARCH_BLOCK, 4, false, 0, true, 1, 4, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((k_search<SEARCH_BLOCK, 4, false, 0, true, 1>), g, b, 0, s, a);
-        break;
+    } else if (v == 20) {
+      if (a.fuse == 3) launch_refill128<false, 3>(a, s);
+      else launch_refill128<false, 0>(a, s);
+    } else if (v == 10) {
+      if (a.fuse) hipLaunchKernelGGL((k_search_g8<256, 16, 4, true>), dim3(g8_grid4(a.n)), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((k_search_g8<256, 16, 4>), dim3(g8_grid4(a.n)), dim3(256), 0, s, a);
+    } else {
+      if (a.fuse) hipLaunchKernelGGL((k_search<SEARCH_BLOCK, 4, false, 0, true, 1, 4, true>), g, b, 0, s, a);
+      else hipLaunchKernelGGL((k_search<SEARCH_BLOCK, 4, false, 0, true, 1>), g, b, 0, s, a);
     }
   }
   return hipGetLastError();
@@ -3017,9 +2885,9 @@ __global__ void __launch_bounds__(256) k_make_hot(const KdNode* __restrict__ nod
   hot[i] = h;
   if (split) split[i] = make_double2(nd.splitval, __hiloint2double((int)nd.c2, (int)nd.c1));     // { splitval, c1 | c2 << 32 }
 }
-#ifdef TDTK_LAB   // two tree levels per record: a measured negative (see the FAT walk in search_refill_body)
-#include "lab_part_7.inc"
-#endif   // TDTK_LAB
+#ifdef TDTK_LAB
+#include "lab_fat_make.inc"   // k_make_fat: two tree levels per record (a measured negative)
+#endif
 hipError_t launch_make_hot(const KdNode* nodes, size_t n, KdHot* hot, hipStream_t s, double2* split)
 {
   if (!n) return hipSuccess;
@@ -3133,17 +3001,6 @@ hipError_t launch_final(const double* partials, uint32_t rows, double* d_out, hi
 // 640 -> 11.4, 1024 -> 11.5, 1536 -> 11.7; a rank's 11 links in one launch: 320 -> 1.79 ms, 448 -> 1.77, 640 -> 1.81
 // (three streams: 12.6 / 1.89 on the same box).
 int search_multi_class(size_t n) { const int v = pick_variant(n); return (v == 20 || v == 4 || v == 10) ? v : 0; }
-// lab (TDTK_MULTI_BLOCK=64): the several-links launch in workgroups of ONE wave -- a wave slot is free again when its wave is
-// done, not when its workgroup's slower wave is (the rows of partial sums are then one per wave)
-static bool multi_block64()
-{
-#ifdef TDTK_LAB
-  const char* e = lab_env("TDTK_MULTI_BLOCK");
-  return e && atoi(e) == 64;
-#else
-  return false;
-#endif
-}
 uint32_t search_multi_prepare(SearchArgs& a, int links_in_launch, bool long_slabs)
 {
   const int v = pick_variant(a.n);
@@ -3176,7 +3033,9 @@ uint32_t search_multi_prepare(SearchArgs& a, int links_in_launch, bool long_slab
   if (ph < 1) ph = 1;
   while (ph > 1 && (qpw % (ph * 16)) != 0) --ph;
   a.phases = ph;
-  if (long_slabs && multi_block64()) nb *= 2;
+#ifdef TDTK_LAB
+  if (long_slabs && multi_block64()) nb *= 2;      // (workgroups of one wave)
+#endif
   return nb;
 }
 int search_multi_thresh(size_t n) { return refill_thresh(n); }
@@ -3192,49 +3051,23 @@ hipError_t launch_search_multi(const SearchArgs* d_args, const uint32_t* d_base,
     else hipLaunchKernelGGL((k_search_g8_multi<256, 16, 4>), gs, dim3(256), 0, s, d_args, d_base, nbatch);
     return hipGetLastError();
   }
-  const dim3 g(total_blocks), b(128);
 #ifdef TDTK_LAB
-  if (!count && lum_sums && multi_block64()) {
-    if (thresh == 32) hipLaunchKernelGGL((k_search_refill_multi<64, 4, 32, 4, false, 5, true>), g, dim3(64), 0, s, d_args, d_base, nbatch);
-    else hipLaunchKernelGGL((k_search_refill_multi<64, 4, 16, 4, false, 5, true>), g, dim3(64), 0, s, d_args, d_base, nbatch);
-    return hipGetLastError();
-  }
+  if (lab_launch_search_multi(d_args, d_base, nbatch, total_blocks, thresh, count, ordered, lum_sums, s)) return hipGetLastError();
 #endif
+  // LinkPass<THRESH, COUNT, FUSE, ORDER, WPS>; FUSE 5: the link's sums by each wave over its own slab
+  const bool thresh32 = thresh == 32;
   if (count) {
-    switch (thresh) {
-#ifdef TDTK_LAB
-      case 8: hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 8, 4, true, 0>), g, b, 0, s, d_args, d_base, nbatch); break;
-#endif
-      case 32: hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 32, 4, true, 0>), g, b, 0, s, d_args, d_base, nbatch); break;
-      default: hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 16, 4, true, 0>), g, b, 0, s, d_args, d_base, nbatch); break;
-    }
+    if (thresh32) launch_refill_multi<LinkPass<32, true, 0, false, 4>>(total_blocks, s, d_args, d_base, nbatch);
+    else launch_refill_multi<LinkPass<16, true, 0, false, 4>>(total_blocks, s, d_args, d_base, nbatch);
+  } else if (lum_sums) {
+    if (thresh32) launch_refill_multi<LinkPass<32, false, 5, true, MULTI_WPS>>(total_blocks, s, d_args, d_base, nbatch);
+    else launch_refill_multi<LinkPass<16, false, 5, true, MULTI_WPS>>(total_blocks, s, d_args, d_base, nbatch);
+  } else if (ordered) {
+    if (thresh32) launch_refill_multi<LinkPass<32, false, 0, true, 4>>(total_blocks, s, d_args, d_base, nbatch);
+    else launch_refill_multi<LinkPass<16, false, 0, true, 4>>(total_blocks, s, d_args, d_base, nbatch);
   } else {
-    switch (thresh) {
-#ifdef TDTK_LAB
-      case 8:
-        if (ordered) hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 8, 4, false, 0, true>), g, b, 0, s, d_args, d_base, nbatch);
-        else hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 8, 4, false, 0>), g, b, 0, s, d_args, d_base, nbatch);
-        break;
-#endif
-      case 32:
-#ifdef TDTK_LAB
-        if (lum_sums && pipe_on()) hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 32, 4, false, 5, true, true>), g, b, 0, s, d_args, d_base, nbatch);
-        else
-#endif
-        if (lum_sums) hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 32, MULTI_WPS, false, 5, true>), g, b, 0, s, d_args, d_base, nbatch);
-        else if (ordered) hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 32, 4, false, 0, true>), g, b, 0, s, d_args, d_base, nbatch);
-        else hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 32, 4, false, 0>), g, b, 0, s, d_args, d_base, nbatch);
-        break;
-      default:
-#ifdef TDTK_LAB
-        if (lum_sums && pipe_on()) hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 16, 4, false, 5, true, true>), g, b, 0, s, d_args, d_base, nbatch);
-        else
-#endif
-        if (lum_sums) hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 16, MULTI_WPS, false, 5, true>), g, b, 0, s, d_args, d_base, nbatch);
-        else if (ordered) hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 16, 4, false, 0, true>), g, b, 0, s, d_args, d_base, nbatch);
-        else hipLaunchKernelGGL((k_search_refill_multi<128, MULTI_SD, 16, 4, false, 0>), g, b, 0, s, d_args, d_base, nbatch);
-        break;
-    }
+    if (thresh32) launch_refill_multi<LinkPass<32, false, 0, false, 4>>(total_blocks, s, d_args, d_base, nbatch);
+    else launch_refill_multi<LinkPass<16, false, 0, false, 4>>(total_blocks, s, d_args, d_base, nbatch);
   }
   return hipGetLastError();
 }

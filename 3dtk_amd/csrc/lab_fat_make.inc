@@ -1,5 +1,5 @@
-// LAB ONLY (lib3dtk_hip_lab.so): a stretch of kernels.hip that exists in the lab build alone (launch policies and helpers of
-// measured negatives, NEGATIVES.md), included under TDTK_LAB at the place it used to stand.
+// LAB ONLY (lib3dtk_hip_lab.so; a measured negative, NEGATIVES.md): the records of the two-levels-per-trip walks (KdFat: a node and
+// both its children in one record; lab_fat_walk.inc and lab_fat_small.inc read them), made from the finished tree.
 __global__ void __launch_bounds__(256) k_make_fat(const KdNode* __restrict__ nodes, size_t n, KdFat* __restrict__ fat)
 {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

@@ -261,4 +261,37 @@ __device__ __forceinline__ void loop_write_row(IcpLoopDev* lp, const int iter, c
   __hip_atomic_store(&row[ICP_ROW_READY], (double)(iter + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// The prologue of a small-batch launch inside the ICP loop that runs without the host (LOOP instantiations of k_search_g8, kernels.hip;
+// kernels.h, IcpLoopDev, has the scheme): this is launch k = a.loop_iter.  Launch 0 just searches.  Launch k > 0 makes
+// iteration k-1's solve -- every workgroup for itself, from the rows launch k-1 left in a.loop_prev -- and returns false when
+// the loop has ended (before this launch was even reached, or by this very solve); otherwise P is the transform to fuse.
+// Workgroup 0 writes the history slot of this launch and the record's row k-1.
+template <int BLOCK>
+__device__ __forceinline__ bool loop_prologue(const SearchArgs& a, const uint32_t bid, Mat4& P)
+{
+  static_assert(BLOCK == 256, "loop_reduce_rows plays k_final's 256 threads");
+  __shared__ double lp_red[4][ICP_LOOP_COLS];
+  __shared__ double lp_sums[ICP_LOOP_COLS];
+  const int k = a.loop_iter;
+  IcpLoopDev* const lp = a.loop;
+  const IcpLoopDev::Hist h = lp->h[(k - 1) & 1];
+  if (h.stop != 0) {                  // ended before this launch was reached: hand the flag on (the launch behind reads slot k & 1)
+    if (bid == 0 && threadIdx.x == 0) lp->h[k & 1] = h;
+    return false;
+  }
+  loop_reduce_rows(a.loop_prev, a.loop_rows, lp_red, lp_sums);
+  const LoopSolve o = loop_solve(lp_sums, a.shift, h.ret, h.prev_ret, a.loop_eps, k - 1, a.loop_max_iter);
+  if (bid == 0 && threadIdx.x == 0) {
+    IcpLoopDev::Hist n = h;
+    if (o.status != ICP_ROW_FEW_PAIRS && o.status != ICP_ROW_NEED_HOST) { n.prev_ret = h.ret; n.ret = o.rms; }
+    n.stop = o.status != ICP_ROW_CONTINUE;
+    lp->h[k & 1] = n;
+    loop_write_row(lp, k - 1, o, lp_sums);
+  }
+  if (o.status != ICP_ROW_CONTINUE) return false;
+#pragma unroll
+  for (int q = 0; q < 16; q++) P.m[q] = o.xf[q];
+  return true;
+}
+
 }  // namespace tdtk

@@ -1064,8 +1064,10 @@ def test_every_product_kernel_spills_nothing_and_search_kernels_keep_four_waves(
         # (round 5: the single-pass persistent-lane kernels the loops run are compiled for SIX waves per SIMD -- 80 registers --
         # and paid for it with the stack-overflow area's per-lane pointers in scratch; round 6: the overflow area is a
         # wave-uniform base + the lane's column (LaneStackQ::gcol) and nothing is spilled to memory anywhere any more)
-        six = re.search(r"k_search_refillILi128ELi[46]ELi(16|32)ELi6ELb0ELi[03]E", name) is not None
-        dfr = "k_search_refillI" in name and name.endswith("ELb1EEEvNS_10SearchArgsE")
+        # the persistent-lane kernels name their configuration (kernels.hip: RefillCfg holds the seventeen values' defaults); the
+        # product's single pass is k_search_refill<SinglePass<THRESH, COUNT, FUSE, DEFER>> and everything else follows from those four
+        single = re.search(r"k_search_refillINS_10SinglePassILi(\d+)ELb([01])ELi(\d+)ELb([01])EEEEEvNS_10SearchArgsE$", name)
+        dfr = single is not None and single.group(4) == "1"
         assert num("VGPRs Spill") == 0, name
         # scalar spills (into lanes of a vector register, not to memory) are left in two kernel families, by name and with
         # their present counts as caps: k_big_stitch -- one wave per (node, axis) walks the exact centroid chain and keeps
@@ -1088,17 +1090,16 @@ def test_every_product_kernel_spills_nothing_and_search_kernels_keep_four_waves(
             assert num("VGPRs") <= 128 and num(r"Occupancy \[waves/SIMD\]") >= 4, name
         for lab_only in ("k_search_step", "k_search_coop", "k_slab_bounds", "k_make_fat"):
             assert lab_only not in name, name
-        if "k_search_refillI" in name and "ELb0ELi" in name.split("k_search_refillI")[1][:40]:
+        if single and single.group(2) == "0":
             # round 5: the single-pass kernel as it is timed (not the instrumented instantiation: COUNT = false) filters buckets on
             # the 16-bit shadow (94 registers: five waves per SIMD) and is compiled for six -- its launch is sized for what the
             # runtime reports
-            a = re.search(r"k_search_refillILi128ELi[46]ELi(16|32)ELi[146]ELb([01])", name)
-            if a and a.group(2) == "0":
-                assert num("VGPRs") <= 80 and num(r"Occupancy \[waves/SIMD\]") >= 6, (name, num("VGPRs"))
-        if "k_search_refillI" in name:      # <BLOCK, SD, THRESH, WPS, COUNT, FUSE, DYN, PTS, PROBE, FAT, TOP, SHARE, PIPE>: product = 128 threads,
-            # FUSE 0 / 3, static slabs, plain walk, no upper levels in LDS, every wave its own slab, hand-outs that wait; with or
-            # without the deferred quick check (DEFER)
+            assert num("VGPRs") <= 80 and num(r"Occupancy \[waves/SIMD\]") >= 6, (name, num("VGPRs"))
+        if "k_search_refillI" in name:
+            # every single-pass kernel of the product is a SinglePass and nothing else: 128 threads, static slabs, plain walk, no
+            # upper levels in LDS, every wave its own slab, hand-outs that wait (SinglePass's static_asserts keep the lab's values
+            # out); THRESH 16 / 32, FUSE 0 / 3, with or without the deferred quick check (DEFER)
             # (round 6: six LDS levels of the traversal stack where the sums are added up behind the launch -- FUSE 0 --, four
             #  where they are added up inside it -- FUSE 3: kernels.hip, REFILL_SD)
-            assert re.search(r"ILi128ELi(4ELi(16|32)ELi[146]ELb[01]ELi3|6ELi(16|32)ELi[146]ELb[01]ELi0)ELb0ELi4ELi0ELb0ELi0ELb0ELb0ELb[01]EEE", name), name
+            assert single and single.group(1) in ("16", "32") and single.group(3) in ("0", "3"), name
     assert seen_refill >= 12
