@@ -1439,6 +1439,145 @@ __global__ void __launch_bounds__(256) k_ann_normals(const AnnNode* __restrict__
   }
 }
 
+// calculateNormalsAdaptiveApxKNN (normals.cc:116-213): k_ann_normals' search and PCA inside a per-lane loop over kidx = kmin ..
+// kmax.  Every step is a fresh annkSearch with k = kidx + 1 (the (1+eps)^2 pruning depends on the k-th key, so the list for k
+// is no prefix of the list for k + 1); the loop ends at the first list whose eigenvalues pass adaptive_k_accepts, or at kmax.
+// KMAX >= kmax + 1.  k is a per-lane value here: the slot tests go through an empty asm wherever they are used, so that they
+// are formed in vector registers at that place instead of being kept as lane masks across the search.
+// normals [n][3], k_used [n] (nullable), knn_out [n][kmax + 1] (nullable, -1 behind the chosen list), caller order.
+template <int KMAX>
+__global__ void __launch_bounds__(256) k_ann_adaptive(const AnnNode* __restrict__ nodes, uint32_t root_ref,
+                                                      const KdPoint* __restrict__ pts, uint32_t n, int kmin, int kmax,
+                                                      double max_err, const double* __restrict__ bb, double rx, double ry,
+                                                      double rz, uint32_t* __restrict__ spill_ref,
+                                                      double* __restrict__ spill_bd, double* __restrict__ normals,
+                                                      int32_t* __restrict__ k_used, int32_t* __restrict__ knn_out)
+{
+  __shared__ uint32_t s_ref[ANN_LDS_STACK][256];
+  __shared__ double s_bd[ANN_LDS_STACK][256];
+  const uint32_t T = gridDim.x * blockDim.x, tid = blockIdx.x * blockDim.x + threadIdx.x, tx = threadIdx.x;
+  const double blo[3] = {bb[0], bb[1], bb[2]}, bhi[3] = {bb[3], bb[4], bb[5]};
+  for (uint32_t qi = tid; qi < n; qi += T) {
+    const KdPoint qp = pts[qi];
+    const double q[3] = {qp.x, qp.y, qp.z};
+    // annBoxDistance (kd_util.cpp:127-150)
+    double bd0 = 0.0;
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+      if (q[d] < blo[d]) { const double t = blo[d] - q[d]; bd0 = bd0 + t * t; }
+      else if (q[d] > bhi[d]) { const double t = q[d] - bhi[d]; bd0 = bd0 + t * t; }
+    }
+    double key[KMAX];
+    uint32_t info[KMAX];
+    double z[3][3], D[3];
+    int kidx = kmin, k0;
+    for (;;) {
+      const int k = kidx + 1;
+      k0 = KMAX - k;
+      asm volatile("" : "+v"(k0));
+#pragma unroll
+      for (int j = 0; j < KMAX; j++) { key[j] = (j < k0) ? -1.0 : DBL_MAX; info[j] = 0xFFFFFFFFu; }
+      double bd = bd0;
+      uint32_t cur = root_ref;
+      int sp = 0;
+      for (;;) {
+        while (!(cur & A_LEAF)) {                      // ANNkd_split::ann_search (kd_search.cpp:128-170)
+          const AnnNode nd = nodes[cur & A_VAL];
+          const uint32_t cd = nd.c0 >> 30;
+          const double qd = (cd == 0) ? q[0] : ((cd == 1) ? q[1] : q[2]);
+          const double cut_diff = qd - nd.cut_val;
+          const bool low = cut_diff < 0;
+          double box_diff = low ? (nd.lo - qd) : (qd - nd.hi);
+          if (box_diff < 0) box_diff = 0;
+          const double fbd = bd + (cut_diff * cut_diff - box_diff * box_diff);
+          const uint32_t c0 = nd.c0 & (A_LEAF | A_VAL), c1 = nd.c1;
+          const uint32_t far = low ? c1 : c0;
+          if (fbd * max_err < key[KMAX - 1]) {         // (as k_ann_normals: the k-th key only ever shrinks)
+            if (sp < ANN_LDS_STACK) { s_ref[sp][tx] = far; s_bd[sp][tx] = fbd; }
+            else { spill_ref[(size_t)(sp - ANN_LDS_STACK) * T + tid] = far; spill_bd[(size_t)(sp - ANN_LDS_STACK) * T + tid] = fbd; }
+            sp++;
+          }
+          cur = low ? c0 : c1;
+        }
+        {                                              // ANNkd_leaf::ann_search, one point (kd_search.cpp:177-210)
+          const uint32_t pos = cur & A_VAL;
+          const KdPoint p = pts[pos];
+          const double t0 = q[0] - p.x, t1 = q[1] - p.y, t2 = q[2] - p.z;
+          const double dist = (t0 * t0 + t1 * t1) + t2 * t2;
+          if (!(dist > key[KMAX - 1])) {
+            // ANNmin_k::insert (pr_queue_k.h:100-114): behind every key <= dist, the last one drops out
+            double ck = dist;
+            uint32_t ci = pos;
+            bool shifting = false;
+#pragma unroll
+            for (int j = 0; j < KMAX; j++) {
+              shifting = shifting || (key[j] > ck);
+              if (shifting) {
+                const double tk = key[j]; key[j] = ck; ck = tk;
+                const uint32_t ti = info[j]; info[j] = ci; ci = ti;
+              }
+            }
+          }
+        }
+        bool done = false;
+        for (;;) {
+          if (sp == 0) { done = true; break; }
+          sp--;
+          if (sp < ANN_LDS_STACK) { cur = s_ref[sp][tx]; bd = s_bd[sp][tx]; }
+          else { cur = spill_ref[(size_t)(sp - ANN_LDS_STACK) * T + tid]; bd = spill_bd[(size_t)(sp - ANN_LDS_STACK) * T + tid]; }
+          if (bd * max_err < key[KMAX - 1]) break;
+        }
+        if (done) break;
+      }
+      // ---- normals.cc:154-182 ----
+      double mean[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+      for (int j = 0; j < KMAX; j++) {
+        int jl = j - k0;
+        asm volatile("" : "+v"(jl));
+        if (jl >= 0) {
+          const KdPoint p = pts[info[j] < n ? info[j] : 0u];     // (a slot no finite distance filled: never out of bounds)
+          mean[0] += p.x; mean[1] += p.y; mean[2] += p.z;
+        }
+      }
+      mean[0] /= k; mean[1] /= k; mean[2] /= k;
+      const double sc = 1.0 / k;
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) z[r][c] = 0.0;
+#pragma unroll
+      for (int j = 0; j < KMAX; j++) {
+        int jl = j - k0;
+        asm volatile("" : "+v"(jl));
+        if (jl >= 0) {
+          const KdPoint p = pts[info[j] < n ? info[j] : 0u];     // (a slot no finite distance filled: never out of bounds)
+          const double x[3] = {p.x - mean[0], p.y - mean[1], p.z - mean[2]};
+#pragma unroll
+          for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int c = 0; c <= r; c++) z[r][c] += (sc * x[c]) * x[r];
+        }
+      }
+      cov_eigen(z, D);
+      if (adaptive_k_accepts(D) || kidx >= kmax) break;
+      ++kidx;
+    }
+    orient_normal(z[0][0], z[1][0], z[2][0], q[0], q[1], q[2], rx, ry, rz, normals + 3 * (size_t)qp.orig);
+    if (k_used) k_used[qp.orig] = kidx;
+    if (knn_out) {
+      int32_t* row = knn_out + (size_t)qp.orig * (size_t)(kmax + 1);
+#pragma unroll
+      for (int j = 0; j < KMAX; j++) {
+        int jl = j - k0;
+        asm volatile("" : "+v"(jl));
+        if (jl >= 0) row[jl] = info[j] < n ? pts[info[j]].orig : -1;
+      }
+      for (int jl = kidx + 1; jl <= kmax; jl++) row[jl] = -1;
+    }
+  }
+}
+
 uint32_t ann_search_threads(size_t n)
 {
   const size_t blocks = (n + 255) / 256;
@@ -1471,6 +1610,26 @@ hipError_t launch_ann_normals(const AnnNode* nodes, uint32_t root_ref, const KdP
   else if (k <= 32) ANN_LAUNCH(32);
   else return hipErrorInvalidValue;
 #undef ANN_LAUNCH
+  return hipGetLastError();
+}
+
+// the same grid as launch_ann_normals: ann_spill_entries sizes the spill columns of both
+hipError_t launch_ann_adaptive(const AnnNode* nodes, uint32_t root_ref, const KdPoint* pts, size_t n, int kmin, int kmax,
+                               double eps, const double* d_bb, const double rPos[3], uint32_t* spill_ref, double* spill_bd,
+                               double* d_normals, int32_t* d_k_used, int32_t* d_knn, hipStream_t s)
+{
+  if (kmin < 0 || kmin > kmax || (size_t)kmax + 1 > n) return hipErrorInvalidValue;
+  const uint32_t T = ann_search_threads(n);
+  const double max_err = (1.0 + eps) * (1.0 + eps);
+  const dim3 grid(T / 256), block(256);
+#define ANN_ADAPT(KM)                                                                                                       \
+  hipLaunchKernelGGL((k_ann_adaptive<KM>), grid, block, 0, s, nodes, root_ref, pts, (uint32_t)n, kmin, kmax, max_err, d_bb, \
+                     rPos[0], rPos[1], rPos[2], spill_ref, spill_bd, d_normals, d_k_used, d_knn)
+  if (kmax + 1 <= 10) ANN_ADAPT(10);
+  else if (kmax + 1 <= 16) ANN_ADAPT(16);
+  else if (kmax + 1 <= 32) ANN_ADAPT(32);
+  else return hipErrorInvalidValue;
+#undef ANN_ADAPT
   return hipGetLastError();
 }
 

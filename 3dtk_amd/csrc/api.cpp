@@ -1693,6 +1693,49 @@ int tdtk_normals_range(const double* xyz, size_t n, double sqRad2, const double 
   return TDTK_OK;
 }
 
+// the argument checks the two adaptive-k estimators share (normals.cc:123-125, 569-571)
+static int adaptive_check_args(const double* xyz, size_t n, int kmin, int kmax, const double* rPos, const double* normals_out)
+{
+  if (!rPos) { set_error("rPos is NULL"); return TDTK_EINVAL; }
+  if (!xyz || n == 0) { set_error("Could not calculate normals, XYZ data is empty"); return TDTK_EINVAL; }
+  if (!normals_out) { set_error("NULL argument"); return TDTK_EINVAL; }
+  if (kmin > kmax) { set_error("kmin must not be larger than kmax"); return TDTK_EINVAL; }
+  if (kmin < 0) { set_error("kmin must be >= 0"); return TDTK_EINVAL; }
+  return TDTK_OK;
+}
+
+int tdtk_normals_adaptive_knn(const double* xyz, size_t n, int kmin, int kmax, const double rPos[3], int bucket, int device,
+                              double* normals_out, int32_t* k_used, int32_t* knn_out)
+{
+  int rc;
+  if ((rc = adaptive_check_args(xyz, n, kmin, kmax, rPos, normals_out))) return rc;
+  if ((rc = tree_check_args(n, bucket))) return rc;
+  if (kmax > KNN_MAX_K - 1) {
+    set_error("kmax + 1 = " + std::to_string((long long)kmax + 1) + " exceeds the supported list capacity of " + std::to_string(KNN_MAX_K));
+    return TDTK_EUNSUP;
+  }
+  Ctx* c;
+  if ((rc = get_ctx(device, &c))) return rc;
+  std::unique_ptr<tdtk_tree> t;
+  if ((rc = normals_tree(c, xyz, n, bucket, device, t))) return rc;
+  const size_t L = knn_out ? n * (size_t)(kmax + 1) : 0;       // WS_IDX: the lists | k_used
+  if ((rc = c->ws[WS_TMPB].ensure(3 * n * sizeof(double)))) return rc;
+  if ((rc = c->ws[WS_IDX].ensure((L + n) * sizeof(int32_t)))) return rc;
+  QueryArgs a;
+  if ((rc = query_prepare(c, t.get(), c->ws[WS_TMPA].as<double>(), n, a))) return rc;
+  a.kmin = kmin; a.kmax = kmax;
+  a.rx = rPos[0]; a.ry = rPos[1]; a.rz = rPos[2];
+  a.normals = c->ws[WS_TMPB].as<double>();
+  a.knn_out = knn_out ? c->ws[WS_IDX].as<int32_t>() : nullptr;
+  a.k_used = k_used ? c->ws[WS_IDX].as<int32_t>() + L : nullptr;
+  HIPCHK(launch_knn_adaptive(a, c->stream));
+  HIPCHK(hipMemcpyAsync(normals_out, a.normals, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (k_used) HIPCHK(hipMemcpyAsync(k_used, a.k_used, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (knn_out) HIPCHK(hipMemcpyAsync(knn_out, a.knn_out, L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return TDTK_OK;
+}
+
 int tdtk_find_closest_along_dir(const tdtk_tree* t, const double* q, const double* dir, size_t K,
                                 double maxdist2, int32_t* idx, double* d2)
 {
@@ -2053,8 +2096,15 @@ int tdtk_reduce_octree_nrpts(const double* xyz, size_t n, double voxel_size, int
 // ---- normals (Scan::calcNormals -> calculateNormalsApxKNN, scan.cc:398-427, normals.cc:35-111) ----------------
 // d_xyz: [n][3] in the caller's order (the ANN tree starts from the identity permutation, kd_tree.cpp:259-262);
 // d_normals [n][3] and d_knn (nullable, [n][k]) come back in the caller's order.
-static int normals_on_device(Ctx* c, const double* d_xyz, size_t n, int k, const double rPos[3], double eps,
-                             double* d_normals, int32_t* d_knn)
+// the build half: the ANN tree of d_xyz in WS_QX (nodes) / WS_QY (points) / WS_BOX (the root cell), and the search's spill
+// area in WS_OVF_REF / WS_OVF_M2 sized for ann_search_threads(n)
+struct AnnTreeDev {
+  AnnNode* nodes;
+  KdPoint* pts;
+  double* d_bb;
+  uint32_t root_ref, max_depth;
+};
+static int ann_tree_on_device(Ctx* c, const double* d_xyz, size_t n, AnnTreeDev& t)
 {
   int rc;
   hipStream_t s = c->stream;
@@ -2062,23 +2112,34 @@ static int normals_on_device(Ctx* c, const double* d_xyz, size_t n, int k, const
   if ((rc = c->ws[WS_QX].ensure((n ? n : 1) * sizeof(AnnNode)))) return rc;
   if ((rc = c->ws[WS_QY].ensure(n * sizeof(KdPoint)))) return rc;
   if ((rc = c->ws[WS_BOX].ensure(bbox_temp_bytes() + 8 * sizeof(double)))) return rc;
-  AnnNode* nodes = c->ws[WS_QX].as<AnnNode>();
-  KdPoint* pts = c->ws[WS_QY].as<KdPoint>();
-  double* d_bb = c->ws[WS_BOX].as<double>();
-  AnnBuildResult r = ann_build_tree(d_xyz, n, c->ws[WS_ARENA].p, nodes, pts, d_bb, s);
+  t.nodes = c->ws[WS_QX].as<AnnNode>();
+  t.pts = c->ws[WS_QY].as<KdPoint>();
+  t.d_bb = c->ws[WS_BOX].as<double>();
+  AnnBuildResult r = ann_build_tree(d_xyz, n, c->ws[WS_ARENA].p, t.nodes, t.pts, t.d_bb, s);
   if (r.err != hipSuccess) {
     if (r.degenerate) { set_error("non-finite coordinates"); return TDTK_EINVAL; }
     set_error(std::string("ann_build_tree: ") + hipGetErrorString(r.err));
     return TDTK_EDEVICE;
   }
+  t.root_ref = r.root_ref; t.max_depth = r.max_depth;
   const size_t spill = ann_spill_entries(n, r.max_depth);
   if ((rc = c->ws[WS_OVF_REF].ensure((spill + 1) * sizeof(uint32_t)))) return rc;
   if ((rc = c->ws[WS_OVF_M2].ensure((spill + 1) * sizeof(double)))) return rc;
+  return TDTK_OK;
+}
+
+static int normals_on_device(Ctx* c, const double* d_xyz, size_t n, int k, const double rPos[3], double eps,
+                             double* d_normals, int32_t* d_knn)
+{
+  int rc;
+  hipStream_t s = c->stream;
+  AnnTreeDev t;
+  if ((rc = ann_tree_on_device(c, d_xyz, n, t))) return rc;
   unsigned long long* d_cnt = nullptr;
   if (c->counting) { d_cnt = c->d_counters.as<unsigned long long>() + 4; c->counted_ann_queries += n; }
   HIPCHK(hipEventRecord(c->e4, s));
-  HIPCHK(launch_ann_normals(nodes, r.root_ref, pts, n, k, eps, d_bb, rPos, c->ws[WS_OVF_REF].as<uint32_t>(),
-                            c->ws[WS_OVF_M2].as<double>(), r.max_depth, d_normals, d_knn, d_cnt, s));
+  HIPCHK(launch_ann_normals(t.nodes, t.root_ref, t.pts, n, k, eps, t.d_bb, rPos, c->ws[WS_OVF_REF].as<uint32_t>(),
+                            c->ws[WS_OVF_M2].as<double>(), t.max_depth, d_normals, d_knn, d_cnt, s));
   HIPCHK(hipEventRecord(c->e5, s));
   c->ev4_pending = true;
   return TDTK_OK;
@@ -2113,6 +2174,35 @@ int tdtk_normals_apx_knn(const double* xyz, size_t n, int k, const double rPos[3
   if ((rc = normals_on_device(c, d_in, n, k, rPos, eps, d_nrm, d_knn))) return rc;
   HIPCHK(hipMemcpyAsync(normals_out, d_nrm, 3 * n * sizeof(double), hipMemcpyDeviceToHost, s));
   if (knn_out) HIPCHK(hipMemcpyAsync(knn_out, d_knn, n * (size_t)k * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return TDTK_OK;
+}
+
+int tdtk_normals_adaptive_apx_knn(const double* xyz, size_t n, int kmin, int kmax, const double rPos[3], double eps,
+                                  int device, double* normals_out, int32_t* k_used, int32_t* knn_out)
+{
+  int rc;
+  if ((rc = adaptive_check_args(xyz, n, kmin, kmax, rPos, normals_out))) return rc;
+  if (kmax > 31) { set_error("kmax + 1 = " + std::to_string((long long)kmax + 1) + " exceeds the supported list capacity of 32"); return TDTK_EUNSUP; }
+  if ((rc = normals_check_args(n, kmax + 1, rPos, eps))) return rc;     // kmax + 1 > n, eps, the size of the scan
+  Ctx* c;
+  if ((rc = get_ctx(device, &c))) return rc;
+  hipStream_t s = c->stream;
+  const size_t L = knn_out ? n * (size_t)(kmax + 1) : 0;       // WS_IDX: the lists | k_used
+  if ((rc = c->ws[WS_TMPA].ensure(6 * n * sizeof(double)))) return rc;   // points in | normals out
+  if ((rc = c->ws[WS_IDX].ensure((L + n) * sizeof(int32_t)))) return rc;
+  double* d_in = c->ws[WS_TMPA].as<double>();
+  double* d_nrm = d_in + 3 * n;
+  int32_t* d_knn = knn_out ? c->ws[WS_IDX].as<int32_t>() : nullptr;
+  int32_t* d_k = k_used ? c->ws[WS_IDX].as<int32_t>() + L : nullptr;
+  HIPCHK(hipMemcpyAsync(d_in, xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, s));
+  AnnTreeDev t;
+  if ((rc = ann_tree_on_device(c, d_in, n, t))) return rc;
+  HIPCHK(launch_ann_adaptive(t.nodes, t.root_ref, t.pts, n, kmin, kmax, eps, t.d_bb, rPos, c->ws[WS_OVF_REF].as<uint32_t>(),
+                             c->ws[WS_OVF_M2].as<double>(), d_nrm, d_k, d_knn, s));
+  HIPCHK(hipMemcpyAsync(normals_out, d_nrm, 3 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (k_used) HIPCHK(hipMemcpyAsync(k_used, d_k, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (knn_out) HIPCHK(hipMemcpyAsync(knn_out, d_knn, L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return TDTK_OK;
 }

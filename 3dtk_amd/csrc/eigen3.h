@@ -1,5 +1,6 @@
 // newmat's symmetric 3x3 eigensolver restated on the device, shared by ann.hip (k_ann_normals) and query.hip (the k-NN and
-// fixed-radius normals): the PCA step of calculateNormal (normals.cc:518-558) after the covariance.
+// fixed-radius normals, the adaptive-k normals of both): the PCA step of calculateNormal (normals.cc:518-558) after the
+// covariance.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cfloat>
@@ -131,16 +132,24 @@ static __device__ void eigen3_newmat(double z[3][3], double D[3])
   }
 }
 
-// calculateNormal's tail (normals.cc:518-558) with the orientation of its callers (normals.cc:64-105, 369-516): z holds the
-// covariance (lower triangle, c <= r, summed in list order); the eigenvector of the smallest eigenvalue, flipped so that
-// n . (q - rPos) >= 0, normalised -- newmat's "v / norm" is v * (1 / norm).  k_ann_normals and the query.hip normals.
-static __device__ __forceinline__ void normal_from_cov(double z[3][3], const double qx, const double qy, const double qz,
-                                                       const double rx, const double ry, const double rz, double* out)
+// calculateNormal's tail (normals.cc:518-558) with the orientation of its callers (normals.cc:64-105, 369-516), in two
+// parts.  The adaptive estimators (normals.cc:116-213, 563-682) read the eigenvalues between them.
+//
+// first part: z holds the covariance (lower triangle, c <= r, summed in list order) on entry, the eigenvectors (columns,
+// ascending eigenvalues D) on exit
+static __device__ __forceinline__ void cov_eigen(double z[3][3], double D[3])
 {
   z[0][1] = z[1][0]; z[0][2] = z[2][0]; z[1][2] = z[2][1];
-  double D[3];
   eigen3_newmat(z, D);
-  double nv[3] = {z[0][0], z[1][0], z[2][0]};
+}
+
+// second part: the eigenvector of the smallest eigenvalue (nx, ny, nz = column 0), flipped so that n . (q - rPos) >= 0,
+// normalised -- newmat's "v / norm" is v * (1 / norm)
+static __device__ __forceinline__ void orient_normal(const double nx, const double ny, const double nz, const double qx,
+                                                     const double qy, const double qz, const double rx, const double ry,
+                                                     const double rz, double* out)
+{
+  double nv[3] = {nx, ny, nz};
   double pv[3] = {qx - rx, qy - ry, qz - rz};
   const double pl = 1.0 / __dsqrt_rn((pv[0] * pv[0] + pv[1] * pv[1]) + pv[2] * pv[2]);
   pv[0] *= pl; pv[1] *= pl; pv[2] *= pl;
@@ -150,6 +159,23 @@ static __device__ __forceinline__ void normal_from_cov(double z[3][3], const dou
   out[0] = nv[0] * nl;
   out[1] = nv[1] * nl;
   out[2] = nv[2] * nl;
+}
+
+// both parts: k_ann_normals and the fixed-k query.hip normals
+static __device__ __forceinline__ void normal_from_cov(double z[3][3], const double qx, const double qy, const double qz,
+                                                       const double rx, const double ry, const double rz, double* out)
+{
+  double D[3];
+  cov_eigen(z, D);
+  orient_normal(z[0][0], z[1][0], z[2][0], qx, qy, qz, rx, ry, rz, out);
+}
+
+// the stopping rule of the adaptive estimators (normals.cc:189, 653), D ascending.  Kept in the reference's sense: with
+// e3 == 0 the quotient is NaN or inf and the test is false
+static __device__ __forceinline__ bool adaptive_k_accepts(const double D[3])
+{
+  const double e1 = D[0], e2 = D[1], e3 = D[2];
+  return (e1 > 0.25 * e2) && (fabs(1.0 - e2 / e3) < 0.25);
 }
 
 }  // namespace tdtk

@@ -278,6 +278,10 @@ hipError_t launch_ann_normals(const AnnNode* nodes, uint32_t root_ref, const KdP
                               const double* d_bb, const double rPos[3], uint32_t* spill_ref, double* spill_bd,
                               uint32_t max_depth, double* d_normals, int32_t* d_knn, unsigned long long* d_cnt,
                               hipStream_t s);
+// calculateNormalsAdaptiveApxKNN: kmax + 1 <= min(32, n); d_k_used [n] and d_knn [n][kmax + 1] nullable; same spill area
+hipError_t launch_ann_adaptive(const AnnNode* nodes, uint32_t root_ref, const KdPoint* pts, size_t n, int kmin, int kmax,
+                               double eps, const double* d_bb, const double rPos[3], uint32_t* spill_ref, double* spill_bd,
+                               double* d_normals, int32_t* d_k_used, int32_t* d_knn, hipStream_t s);
 
 hipError_t launch_pp_error(const AccumArgs& a, uint32_t grid, double scale, double* d_partial, double* d_out, hipStream_t s);
 hipError_t launch_found_flags(const int* kpos, const int32_t* order, size_t n, uint32_t* flags, hipStream_t s);

@@ -27,10 +27,13 @@ struct QueryArgs {
   const unsigned long long* offsets;   // range fill walk: [n + 1]
   double rx, ry, rz;           // normals: the scanner position
   double* normals;             // [n][3], caller order
-  int32_t* knn_out;            // k-NN normals: the lists [n][k] (nullable)
+  int32_t* knn_out;            // k-NN normals: the lists [n][k] (nullable); adaptive-k normals: [n][kmax + 1]
   // cylinder / box / segment queries (r2 is their maxdist2; idx / d2 of the nearest-point query: [n], caller order)
   const double* node_r;        // bounding-sphere radius per internal node
   const double *vx, *vy, *vz;  // the query's second vector (dir, p0 or the box's upper corner), sorted like x / y / z
+  // adaptive-k normals
+  int kmin, kmax;              // adaptive-k normals: every query tries k = kmin + 1 .. kmax + 1
+  int32_t* k_used;             // adaptive-k normals: [n] the kidx of the list the normal was computed from (nullable)
 };
 
 // the four list queries of the shape walks (launch_shape_count / launch_shape_fill)
@@ -38,6 +41,7 @@ enum ShapeMode { SHAPE_ALONG_DIR = 0, SHAPE_BETWEEN = 1, SHAPE_AABB = 2, SHAPE_S
 
 size_t query_overflow_entries(size_t n, uint32_t max_depth);
 hipError_t launch_knn(const QueryArgs& a, bool normals, hipStream_t s);
+hipError_t launch_knn_adaptive(const QueryArgs& a, hipStream_t s);            // kmax + 1 <= KNN_MAX_K; a.normals, a.k_used, a.knn_out
 hipError_t launch_range_count(const QueryArgs& a, hipStream_t s);
 hipError_t launch_range_fill(const QueryArgs& a, hipStream_t s);
 hipError_t launch_range_normals(const QueryArgs& a, hipStream_t s);

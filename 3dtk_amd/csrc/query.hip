@@ -30,6 +30,15 @@
 //   * myd = splitval - p[axis]; myd >= 0: child1 first, child2 after it only if myd*myd < r2; otherwise child2 first and
 //     child1 under the same condition.  r2 never changes, so the condition is tested when the far child is pushed.
 //   * leaf: every point with Dist2 < r2, in bucket order; the list is in visiting order.
+// Adaptive k (calculateNormalsAdaptiveKNN, normals.cc:563-682), per point, kidx = kmin .. kmax:
+//   * a FRESH k-NN walk with k = kidx + 1: new list, empty stack, the rules above.  Not one walk at kmax + 1 cut to
+//     prefixes: a node's box is fl((min+max)/2) +- fl((max-min)/2) and may exclude one of its own points by an ulp, so a
+//     point that walk(k) prunes can enter the first k slots of walk(k'), and the reference's answer is walk(k)'s.
+//   * nr = the slots with a distance >= 0 (< kidx + 1 only when the cloud has fewer points); mean and covariance over those
+//     nr entries in list order, / nr (list_cov); newmat's EigenValues: e1 <= e2 <= e3.
+//   * stop when (e1 > 0.25 * e2) && (fabs(1.0 - e2 / e3) < 0.25), in this sense: e3 == 0 gives NaN or inf and false, a list
+//     of one point gives the zero matrix and never stops.  No kidx stops: the list of kmax stands.
+//   * the normal is column 0 of the LAST eigenvector matrix computed, oriented and normalised as everywhere (orient_normal).
 // Dist2 (globals.icc:238) = (dx*dx + dy*dy) + dz*dz, dx = point - query; fp64 everywhere, FMA contraction off (Makefile).
 //
 // The cylinder, box and segment queries (kdIndexed.cc:164-213, 233-301; kdTreeImpl.h:432-577, 747-913).  p is the query
@@ -137,7 +146,8 @@ __device__ __forceinline__ void stack_init(LaneStackQ<BLOCK, Q_SD>& st, uint4 (*
 // the k0 slots in front hold -0.0, which is neither unset (-0.0 < 0.0 is false) nor larger than any distance, so an
 // insertion never stops there and never shifts them: the bubble below needs no per-slot test of k, and distances[k-1]
 // is always slot KC-1.
-template <int KC>
+// (CHAIN: the adaptive kernel's form of the search for pos, see there)
+template <int KC, bool CHAIN = false>
 struct ListReg {
   double d[KC];
   uint32_t s[KC];
@@ -158,7 +168,8 @@ struct ListReg {
 #pragma unroll
     for (int j = KC - 1; j >= 0; j--) {
       double mj = md;
-      asm volatile("" : "+v"(mj));
+      if (CHAIN) asm volatile("" : "+v"(mj), "+v"(pos));
+      else asm volatile("" : "+v"(mj));
       pos = (d[j] < 0.0 || d[j] > mj) ? j : pos;
     }
 #pragma unroll
@@ -282,8 +293,28 @@ __device__ void range_walk(const QueryArgs& a, const double qx, const double qy,
 
 // calculateNormal (normals.cc:518-558) over a list the caller enumerates: each(f) calls f(point) for the nr points of the
 // list in list order, and is called twice (mean, then covariance -- the arithmetic of k_ann_normals: mean / nr, then
-// A = (1/nr X^T) X summed in list order); eigen3.h's normal_from_cov does the rest.  nr is read after the first pass (the
+// A = (1/nr X^T) X summed in list order, lower triangle of z); eigen3.h does the rest.  nr is read after the first pass (the
 // range normals count their list there).
+template <class EACH>
+__device__ __forceinline__ void list_cov(EACH&& each, const int& nr, double z[3][3])
+{
+  double mean[3] = {0.0, 0.0, 0.0};
+  each([&](const KdPoint& p) { mean[0] += p.x; mean[1] += p.y; mean[2] += p.z; });
+  mean[0] /= nr; mean[1] /= nr; mean[2] /= nr;
+  const double sc = 1.0 / nr;
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+#pragma unroll
+    for (int c = 0; c <= r; c++) z[r][c] = 0.0;
+  each([&](const KdPoint& p) {
+    const double x[3] = {p.x - mean[0], p.y - mean[1], p.z - mean[2]};
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+      for (int c = 0; c <= r; c++) z[r][c] += (sc * x[c]) * x[r];
+  });
+}
+
 template <class EACH>
 __device__ __forceinline__ void list_normal(EACH&& each, const int& nr, const double qx, const double qy, const double qz,
                                             const QueryArgs& a, double* out)
@@ -402,6 +433,126 @@ __global__ void __launch_bounds__(Q_BLOCK_L) k_knn_lds(const QueryArgs a_)
       auto each = [&](auto&& f) { for (int j = 0; j < nr; j++) f(a.pts[L.slot(j)]); };
       list_normal(each, nr, qx, qy, qz, a, a.normals + 3 * o);
     }
+  }
+}
+
+// ---- adaptive-k normals (calculateNormalsAdaptiveKNN) --------------------------------------------------------------
+// Every query repeats the whole search for kidx = kmin .. kmax with a fresh list of kidx + 1 slots and an empty stack, runs
+// the PCA on each list and stops at the first whose eigenvalues pass adaptive_k_accepts, or at kmax (rules: the header
+// comment).  kidx is a per-lane value.  The two kernels are the two list forms of the k-NN kernels, with their block sizes
+// and grids (query_overflow_entries covers both).
+// Rows: normals [n][3], k_used [n] (nullable), knn_out [n][kmax + 1] (nullable): the chosen list, -1 behind its nr entries.
+//
+// ListReg<KC, true>: insert()'s search for pos carries pos through the empty asm of every slot, so that slot j's two
+// compares are consumed before slot j - 1's are issued.  Without it the scheduler, in this kernel, issues the compares of
+// many slots ahead of their selects, one lane mask in an SGPR pair each: 106 SGPRs and 8 spilled at KC = 32; with it 52 and
+// none.  (k_knn_reg keeps the plain form: there the compares stay in order as they are.)
+
+// the register-list form, kmax + 1 <= KC
+template <int KC>
+__global__ void __launch_bounds__(Q_BLOCK) k_knn_adaptive_reg(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  LaneStackQ<Q_BLOCK, Q_SD> st;
+  stack_init<Q_BLOCK>(st, s_stack, a);
+  ListReg<KC, true> L;
+  const size_t T = (size_t)gridDim.x * Q_BLOCK;
+  // one loop over (query, kidx) steps: a lane whose list passed the test goes on to its next query while its neighbours are
+  // still trying longer lists of theirs (as two nested loops the kernel carried two more loop masks beside insert()'s lane
+  // masks, and spilled SGPRs at KC = 32)
+  size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x;
+  int kidx = a.kmin;
+  while (i < a.n) {
+    const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
+    // (k0 through an empty asm at every use, as in k_knn_reg: the slot tests stay in vector registers)
+    int k0 = KC - (kidx + 1);
+    asm volatile("" : "+v"(k0));
+    L.init(k0);
+    st.sp = 0;
+    knn_walk<Q_BLOCK>(a, qx, qy, qz, L, st);
+    int nr = 0;
+#pragma unroll
+    for (int j = 0; j < KC; j++) {
+      int jl = j - k0;
+      asm volatile("" : "+v"(jl));
+      nr += (jl >= 0 && L.d[j] >= 0.0) ? 1 : 0;
+    }
+    auto each = [&](auto&& f) {
+#pragma unroll
+      for (int j = 0; j < KC; j++) {
+        int jl = j - k0;
+        asm volatile("" : "+v"(jl));
+        if (jl >= 0 && jl < nr) f(a.pts[L.s[j]]);
+      }
+    };
+    double z[3][3], D[3];
+    list_cov(each, nr, z);
+    cov_eigen(z, D);
+    const int kmax = a.kmax;
+    if (!adaptive_k_accepts(D) && kidx < kmax) { ++kidx; continue; }
+    const size_t o = a.order ? (size_t)a.order[i] : i;
+    orient_normal(z[0][0], z[1][0], z[2][0], qx, qy, qz, a.rx, a.ry, a.rz, a.normals + 3 * o);
+    if (a.k_used) a.k_used[o] = kidx;
+    if (a.knn_out) {
+      int32_t* row = a.knn_out + o * (size_t)(kmax + 1);
+#pragma unroll
+      for (int j = 0; j < KC; j++) {
+        int jl = j - k0;
+        asm volatile("" : "+v"(jl));
+        if (jl >= 0) {
+          const bool v = jl < nr;
+          row[jl] = v ? a.pts[v ? L.s[j] : 0u].orig : -1;     // (an unset slot's point is never loaded)
+        }
+      }
+      for (int jl = kidx + 1; jl <= kmax; jl++) row[jl] = -1;
+    }
+    i += T;
+    kidx = a.kmin;
+  }
+}
+
+// the LDS-list form (33 <= kmax + 1 <= 64; kmin + 1 may lie below 33), the same loop
+__global__ void __launch_bounds__(Q_BLOCK_L) k_knn_adaptive_lds(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK_L];
+  __shared__ double s_d[KNN_MAX_K][Q_BLOCK_L];
+  __shared__ uint32_t s_s[KNN_MAX_K][Q_BLOCK_L];
+  LaneStackQ<Q_BLOCK_L, Q_SD> st;
+  stack_init<Q_BLOCK_L>(st, s_stack, a);
+  ListLds<Q_BLOCK_L> L;
+  L.ld = &s_d[0][threadIdx.x];
+  L.ls = &s_s[0][threadIdx.x];
+  const size_t T = (size_t)gridDim.x * Q_BLOCK_L;
+  size_t i = (size_t)blockIdx.x * Q_BLOCK_L + threadIdx.x;
+  int kidx = a.kmin;
+  while (i < a.n) {
+    const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
+    const int k = kidx + 1;
+    L.init(k);
+    st.sp = 0;
+    knn_walk<Q_BLOCK_L>(a, qx, qy, qz, L, st);
+    int nr = 0;
+    for (int j = 0; j < k; j++) nr += (L.dist(j) >= 0.0) ? 1 : 0;   // kdIndexed.cc:152-156
+    auto each = [&](auto&& f) { for (int j = 0; j < nr; j++) f(a.pts[L.slot(j)]); };
+    double z[3][3], D[3];
+    list_cov(each, nr, z);
+    cov_eigen(z, D);
+    const int kmax = a.kmax;
+    if (!adaptive_k_accepts(D) && kidx < kmax) { ++kidx; continue; }
+    const size_t o = a.order ? (size_t)a.order[i] : i;
+    orient_normal(z[0][0], z[1][0], z[2][0], qx, qy, qz, a.rx, a.ry, a.rz, a.normals + 3 * o);
+    if (a.k_used) a.k_used[o] = kidx;
+    if (a.knn_out) {
+      int32_t* row = a.knn_out + o * (size_t)(kmax + 1);
+      for (int j = 0; j <= kmax; j++) {
+        const bool v = j < nr;
+        row[j] = v ? a.pts[v ? L.slot(j) : 0u].orig : -1;
+      }
+    }
+    i += T;
+    kidx = a.kmin;
   }
 }
 
@@ -754,6 +905,19 @@ hipError_t launch_knn(const QueryArgs& a, bool normals, hipStream_t s)
     else hipLaunchKernelGGL(k_knn_lds<false>, gl, bl, 0, s, a);
   }
 #undef KNN_REG
+  return hipGetLastError();
+}
+
+hipError_t launch_knn_adaptive(const QueryArgs& a, hipStream_t s)
+{
+  if (a.kmin < 0 || a.kmin > a.kmax || a.kmax + 1 > KNN_MAX_K) return hipErrorInvalidValue;
+  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
+  const int k = a.kmax + 1;      // the capacities of launch_knn, by the longest list
+  if (k <= 4) hipLaunchKernelGGL(k_knn_adaptive_reg<4>, g, b, 0, s, a);
+  else if (k <= 10) hipLaunchKernelGGL(k_knn_adaptive_reg<10>, g, b, 0, s, a);
+  else if (k <= 20) hipLaunchKernelGGL(k_knn_adaptive_reg<20>, g, b, 0, s, a);
+  else if (k <= 32) hipLaunchKernelGGL(k_knn_adaptive_reg<32>, g, b, 0, s, a);
+  else hipLaunchKernelGGL(k_knn_adaptive_lds, dim3(q_grid(a.n, Q_BLOCK_L)), dim3(Q_BLOCK_L), 0, s, a);
   return hipGetLastError();
 }
 

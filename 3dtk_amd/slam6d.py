@@ -726,6 +726,55 @@ def calculateNormalsRange(points, sqRad2, rPos, bucketSize=20, device=0):
     return out
 
 
+def _adaptive_result(out, k_used, knn, want_k, want_knn):
+    r = (out,) + ((k_used,) if want_k else ()) + ((knn,) if want_knn else ())
+    return r if len(r) > 1 else out
+
+
+def calculateNormalsAdaptiveKNN(points, kmin, kmax, rPos, bucketSize=20, device=0, want_k=False, want_knn=False):
+    """normals.cc:563-682 (calculateNormalsAdaptiveKNN(normals, points, kmin, kmax, rPos)) on the device: every point repeats
+    the exact search with k = kmin + 1 .. kmax + 1 until the eigenvalues of its list's covariance pass the reference's
+    test.  Returns the [n][3] normals in point order, then with want_k the [n] kidx each normal was computed from, then
+    with want_knn the [n][kmax + 1] lists (-1 behind the chosen list)."""
+    xyz = f64(points).reshape(-1, 3)
+    out = np.empty_like(xyz)
+    k_used = np.empty(len(xyz), np.int32) if want_k else None
+    knn = np.empty((len(xyz), max(int(kmax) + 1, 0)), np.int32) if want_knn else None
+    check(lib().tdtk_normals_adaptive_knn(dptr(xyz), len(xyz), int(kmin), int(kmax), dptr(f64(rPos)), int(bucketSize),
+                                          int(device), dptr(out), iptr(k_used), iptr(knn)))
+    return _adaptive_result(out, k_used, knn, want_k, want_knn)
+
+
+def calculateNormalsAdaptiveApxKNN(points, kmin, kmax, rPos, eps=0.0, device=0, want_k=False, want_knn=False):
+    """normals.cc:116-213 (calculateNormalsAdaptiveApxKNN(normals, points, kmin, kmax, rPos, eps)) on the device: the same
+    loop around the ANN search of calculateNormalsApxKNN.  Returns as calculateNormalsAdaptiveKNN."""
+    xyz = f64(points).reshape(-1, 3)
+    out = np.empty_like(xyz)
+    k_used = np.empty(len(xyz), np.int32) if want_k else None
+    knn = np.empty((len(xyz), max(int(kmax) + 1, 0)), np.int32) if want_knn else None
+    check(lib().tdtk_normals_adaptive_apx_knn(dptr(xyz), len(xyz), int(kmin), int(kmax), dptr(f64(rPos)), float(eps),
+                                              int(device), dptr(out), iptr(k_used), iptr(knn)))
+    return _adaptive_result(out, k_used, knn, want_k, want_knn)
+
+
+def calculateNormalsIndexedKNN(points, k, rPos, device=0):
+    """normals.cc:300-366 (calculateNormalsIndexedKNN(normals, points, k, rPos)): calculateNormalsKNN on one thread over a
+    KDtree of bucket size 20, so that the normals come in point order -- the order the device forms return anyway."""
+    return calculateNormalsKNN(points, k, rPos, 20, device)
+
+
+def flipNormals(normals):
+    """normals.cc:687-694, in place on an [n][3] array"""
+    normals *= -1.0
+    return normals
+
+
+def flipNormalsUp(normals):
+    """normals.cc:696-705, in place on an [n][3] array: every normal with y < 0 is negated"""
+    normals[normals[:, 1] < 0.0] *= -1.0
+    return normals
+
+
 def read_pose(path):
     rP = np.empty(3); rT = np.empty(3)
     check(lib().tdtk_io_read_pose(str(path).encode(), dptr(rP), dptr(rT)))

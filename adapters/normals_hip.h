@@ -59,6 +59,45 @@ inline void calculateNormalsRange_hip(std::vector<Point>& normals, const std::ve
   for (size_t i = 0; i < n; i++) normals.push_back(Point(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]));
 }
 
+// calculateNormalsIndexedKNN (normals.cc:300-366): calculateNormalsKNN on one thread over the default KDtree (bucket size
+// 20), normals in point order -- which calculateNormalsKNN_hip returns anyway.
+inline void calculateNormalsIndexedKNN_hip(std::vector<Point>& normals, const std::vector<Point>& points, const int k,
+                                           const double _rPos[3], int device = 0)
+{
+  calculateNormalsKNN_hip(normals, points, k, _rPos, 20, device);
+}
+
+// calculateNormalsAdaptiveKNN (normals.cc:563-682) and calculateNormalsAdaptiveApxKNN (normals.cc:116-213) on the GPU
+// (tdtk_normals_adaptive_knn / tdtk_normals_adaptive_apx_knn): per point the search repeated for kidx = kmin .. kmax until
+// the eigenvalue test holds, every normal bit-identical to the reference's, appended in point order.  kmin > kmax throws
+// the reference's std::invalid_argument; everything else the library refuses is a std::runtime_error (ANN itself aborts
+// the process when a point reaches kidx + 1 > n; the library refuses kmax + 1 > n up front).
+inline void calculateNormalsAdaptiveKNN_hip(std::vector<Point>& normals, const std::vector<Point>& points, const int kmin,
+                                            const int kmax, const double _rPos[3], int device = 0)
+{
+  if (kmin > kmax) throw std::invalid_argument("kmin must not be larger than kmax");
+  const size_t n = points.size();
+  std::vector<double> xyz(3 * n), nrm(3 * n);
+  for (size_t i = 0; i < n; i++) { xyz[3 * i] = points[i].x; xyz[3 * i + 1] = points[i].y; xyz[3 * i + 2] = points[i].z; }
+  if (tdtk_normals_adaptive_knn(xyz.data(), n, kmin, kmax, _rPos, 20, device, nrm.data(), 0, 0) != TDTK_OK)
+    throw std::runtime_error(tdtk_last_error());
+  normals.reserve(normals.size() + n);
+  for (size_t i = 0; i < n; i++) normals.push_back(Point(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]));
+}
+
+inline void calculateNormalsAdaptiveApxKNN_hip(std::vector<Point>& normals, const std::vector<Point>& points, const int kmin,
+                                               const int kmax, const double _rPos[3], const double eps = 0.0, int device = 0)
+{
+  if (kmin > kmax) throw std::invalid_argument("kmin must not be larger than kmax");
+  const size_t n = points.size();
+  std::vector<double> xyz(3 * n), nrm(3 * n);
+  for (size_t i = 0; i < n; i++) { xyz[3 * i] = points[i].x; xyz[3 * i + 1] = points[i].y; xyz[3 * i + 2] = points[i].z; }
+  if (tdtk_normals_adaptive_apx_knn(xyz.data(), n, kmin, kmax, _rPos, eps, device, nrm.data(), 0, 0) != TDTK_OK)
+    throw std::runtime_error(tdtk_last_error());
+  normals.reserve(normals.size() + n);
+  for (size_t i = 0; i < n; i++) normals.push_back(Point(nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]));
+}
+
 // Where the scan is already resident (adapters/graphSlam6D_hip.h, addition (2): Scan::hipResident()), skip the host
 // round trip: tdtk_scan_calc_normals(scan->hipResident(), K_NEIGHBOURS, scan->get_rPos(), 1.0) computes the normals
 // of the resident points in place and keeps them on the device as the scan's "normal reduced".

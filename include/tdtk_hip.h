@@ -218,6 +218,17 @@ int tdtk_normals_knn(const double* xyz, size_t n, int k, const double rPos[3], i
  * at sqRad2, in visiting order.  Errors: n == 0, bucket < 1, sqRad2 <= 0 (the reference would divide 0 by 0). */
 int tdtk_normals_range(const double* xyz, size_t n, double sqRad2, const double rPos[3], int bucket, int device,
                        double* normals_out);
+/* calculateNormalsAdaptiveKNN (normals.cc:563-682): a KDtree(points, bucket) (the reference's is 20) and, for every point,
+ * kidx = kmin .. kmax: a fresh search for its kidx + 1 nearest neighbours, their mean, covariance and eigenvalues e1 <=
+ * e2 <= e3; the loop stops at the first kidx with (e1 > 0.25 * e2) && (fabs(1.0 - e2 / e3) < 0.25), or at kmax.  The
+ * normal is the eigenvector of e1 of the last list computed, oriented and normalised as above.  The whole loop runs in
+ * one launch, per lane.  normals_out [n][3] in point order; k_used (nullable) [n]: the kidx of that list (kmax both when
+ * kmax passed the test and when nothing did); knn_out (nullable) [n][kmax + 1]: that list, -1 behind its entries.
+ * Errors, all before anything is launched or written: kmin > kmax ("kmin must not be larger than kmax", the reference's
+ * std::invalid_argument), kmin < 0, n == 0, NULL xyz / rPos / normals_out, bucket < 1 (TDTK_EINVAL); kmax + 1 > 64
+ * (TDTK_EUNSUP).                                                                                               */
+int tdtk_normals_adaptive_knn(const double* xyz, size_t n, int kmin, int kmax, const double rPos[3], int bucket,
+                              int device, double* normals_out, int32_t* k_used, int32_t* knn_out);
 
 /* ---- SearchTree::getPtPairs, DataXYZ overload (src/slam6d/searchTree.cc:92-189), fused
  * with the per-thread Si pass of icp6D::match (icp6D.cc:170-191) and the APX/NAPX/LUM
@@ -444,6 +455,14 @@ int tdtk_reduce_octree_nrpts(const double* xyz, size_t n, double voxel_size, int
  * non-finite coordinates.                                                                     */
 int tdtk_normals_apx_knn(const double* xyz, size_t n, int k, const double rPos[3], double eps, int device,
                          double* normals_out, int32_t* knn_out);
+/* calculateNormalsAdaptiveApxKNN (normals.cc:116-213): the adaptive loop of tdtk_normals_adaptive_knn around
+ * annkSearch(p, kidx + 1, eps) on the ANN tree above, each search started afresh (the list for k is no prefix of the
+ * list for k + 1 under the (1+eps) bound).  Outputs as tdtk_normals_adaptive_knn.  Errors, all before anything is launched
+ * or written: kmin > kmax, kmin < 0, n == 0, NULLs, eps < 0 or not finite, non-finite coordinates (TDTK_EINVAL); kmax + 1 > n
+ * ("Requesting more near neighbors than data points", TDTK_EINVAL -- a deviation: ANN aborts the process only when some
+ * point actually reaches such a kidx, this refuses the call); kmax + 1 > 32 (TDTK_EUNSUP).                       */
+int tdtk_normals_adaptive_apx_knn(const double* xyz, size_t n, int kmin, int kmax, const double rPos[3], double eps,
+                                  int device, double* normals_out, int32_t* k_used, int32_t* knn_out);
 /* the same for a resident scan, from its current points; the result becomes its "normal reduced" */
 int tdtk_scan_calc_normals(tdtk_scan* s, int k, const double rPos[3], double eps);
 

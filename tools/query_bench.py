@@ -9,8 +9,15 @@ scaled up to the whole cloud; labelled as such).  Prints one JSON line.
 a few point spacings long, maxdist2 (the box's half extent) chosen for about 20 entries per list, each next to the
 reference's method in the same host loop; --only-segments runs nothing else.
 
+--adaptive adds the adaptive-k normals at 1M points (queries = the points): the exact form at (9, 9) and (19, 19) next to
+calculateNormalsKNN k = 10 and 20 in the same run (the same walks plus one evaluation of the rule), at (5, 20) and (10, 20)
+with the histogram of k_used and the mean number of walks per point, the ANN form at (9, 9) next to calculateNormalsApxKNN
+k = 10 and at (5, 20) (eps = 1.0), and the reference: the fixture generator's loop (tests/golden/make_golden_adaptive.py:
+the reference library's searches and newmat's EigenValues, the glue in Python and therefore on one thread whatever
+--ref-threads says) on a fiftieth of --ref-queries points, scaled to the whole cloud; --only-adaptive runs nothing else.
+
 Kernel times: run the same command under `rocprofv3 --kernel-trace --stats` (k_knn_reg, k_range_count / k_range_fill,
-k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest)."""
+k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest, k_knn_adaptive_reg / k_knn_adaptive_lds, k_ann_adaptive)."""
 import argparse
 import importlib
 import json
@@ -137,6 +144,47 @@ def segment_legs(tdtk, pts, tag, rng, reps, nq, threads):
     return out
 
 
+def adaptive_legs(tdtk, pts, tag, rng, reps, nq, threads):
+    """calculateNormalsAdaptiveKNN / calculateNormalsAdaptiveApxKNN, end to end like the other normals legs (tree build
+    included), each next to the fixed-k estimator that walks the same lists"""
+    out = {}
+    rpos = [0.0, 0.0, 0.0]
+    for k in (10, 20):
+        out["normals_knn_k%d_%s" % (k, tag)] = timed(lambda: tdtk.calculateNormalsKNN(pts, k, rpos), reps)
+        out["adaptive_knn_%d_%d_%s" % (k - 1, k - 1, tag)] = timed(lambda: tdtk.calculateNormalsAdaptiveKNN(pts, k - 1, k - 1, rpos), reps)
+    for kmin, kmax in ((5, 20), (10, 20)):
+        key = "adaptive_knn_%d_%d_%s" % (kmin, kmax, tag)
+        out[key] = timed(lambda: tdtk.calculateNormalsAdaptiveKNN(pts, kmin, kmax, rpos), reps)
+        _, ku = tdtk.calculateNormalsAdaptiveKNN(pts, kmin, kmax, rpos, want_k=True)
+        out[key + "_k_used_hist"] = np.bincount(ku, minlength=kmax + 1)[kmin:].tolist()
+        out[key + "_mean_walks"] = round(float((ku - kmin + 1).mean()), 3)
+    out["normals_apxknn_k10_%s" % tag] = timed(lambda: tdtk.calculateNormalsApxKNN(pts, 10, rpos, 1.0), reps)
+    out["adaptive_apxknn_9_9_%s" % tag] = timed(lambda: tdtk.calculateNormalsAdaptiveApxKNN(pts, 9, 9, rpos, 1.0), reps)
+    key = "adaptive_apxknn_5_20_%s" % tag
+    out[key] = timed(lambda: tdtk.calculateNormalsAdaptiveApxKNN(pts, 5, 20, rpos, 1.0), reps)
+    _, ku = tdtk.calculateNormalsAdaptiveApxKNN(pts, 5, 20, rpos, 1.0, want_k=True)
+    out[key + "_k_used_hist"] = np.bincount(ku, minlength=21)[5:].tolist()
+    out[key + "_mean_walks"] = round(float((ku - 5 + 1).mean()), 3)
+    from oracle import orc
+    if not orc.have_ref() or nq <= 0:
+        return out
+    # the reference: the generator's loop (library searches and newmat from oracle/_ref, glue in Python).  One thread: the
+    # loop calls kNearestNeighbors with threadNum 0 and newmat keeps global state, so it cannot run on several Python
+    # threads, and the Python glue is most of its time anyway -- a yardstick for the order of magnitude, labelled as such
+    spec = importlib.util.spec_from_file_location("make_golden_adaptive",
+                                                  os.path.join(ROOT, "tests", "golden", "make_golden_adaptive.py"))
+    ma = importlib.util.module_from_spec(spec); spec.loader.exec_module(ma)
+    rows = rng.choice(len(pts), nq, replace=False)
+    label = "ref_loop_python_glue_1thread_%dq_scaled" % nq
+    t = ma.mgk.RefTree(pts, 20)
+    ann = orc.AnnTree(pts, "ref")
+    for name, lists in (("adaptive_knn_5_20", ma.exact_lists(t)), ("adaptive_apxknn_5_20", ma.ann_lists(ann, 1.0))):
+        t0 = time.perf_counter()
+        ma.reference_loop(orc, pts, rows, lists, 5, 20, rpos=np.zeros(3))
+        out["%s_%s_%s_ms" % (label, name, tag)] = round((time.perf_counter() - t0) * 1e3 * len(pts) / nq, 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000000,10000000")
@@ -145,6 +193,8 @@ def main():
     ap.add_argument("--ref-threads", type=int, default=16)
     ap.add_argument("--segments", action="store_true", help="add the cylinder / box / segment query legs (1M points)")
     ap.add_argument("--only-segments", action="store_true", help="those legs alone")
+    ap.add_argument("--adaptive", action="store_true", help="add the adaptive-k normals legs (1M points)")
+    ap.add_argument("--only-adaptive", action="store_true", help="those legs alone")
     args = ap.parse_args()
     tdtk = importlib.import_module("3dtk_amd")
     if tdtk.device_count() < 1:
@@ -156,6 +206,13 @@ def main():
         pts = np.random.default_rng(2025).uniform(-50, 50, (1_000_000, 3))
         out.update(segment_legs(tdtk, pts, "1M", np.random.default_rng(2026), args.reps, args.ref_queries, args.ref_threads))
         if args.only_segments:
+            print(json.dumps(out))
+            return
+    if args.adaptive or args.only_adaptive:
+        pts = np.random.default_rng(2027).uniform(-50, 50, (1_000_000, 3))
+        # (the reference loop is Python glue around the library, about 1.2 ms per point: a fiftieth of --ref-queries)
+        out.update(adaptive_legs(tdtk, pts, "1M", np.random.default_rng(2028), args.reps, args.ref_queries // 50, args.ref_threads))
+        if args.only_adaptive:
             print(json.dumps(out))
             return
     for M in [int(s) for s in args.sizes.split(",")]:
