@@ -329,6 +329,14 @@ def test_get_pt_pairs_vs_oracle(tdtk, orc, gpu, mode):
            (x * y).sum(), (x * z).sum(), (y * z).sum(), dx.sum(), dy.sum(), dz.sum(),
            (-z * dy + y * dz).sum(), (-y * dx + x * dy).sum(), (z * dx - x * dz).sum()]
     assert np.abs((np.array(got["lum"]) - lum) / (np.abs(lum) + np.abs(lum).max() * 1e-6)).max() < 1e-9
+    # ... and every quantity, the small columns included, against the extended-precision reference at the tolerance it
+    # derives for each of them (tests/pair_sums_ref.py)
+    import pair_sums_ref as R
+    want = tdtk.WANT_APX | tdtk.WANT_NAPX | tdtk.WANT_LUM
+    shift = R.shift_of(m, A)
+    fin = R.finished(ref["p1"], ref["p2"], ref["pn"], shift, want)
+    R.check_struct(got["_raw"], fin, R.discrimination(ref["p1"], ref["p2"], ref["pn"], shift, want, fin=fin),
+                   "k_accum<7,%d> + k_final, 38 900 queries" % mode)
 
 
 def test_get_pt_pairs_rnd_subsampling(tdtk, orc, gpu):
