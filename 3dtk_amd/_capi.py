@@ -62,7 +62,7 @@ EXPORTS = [
     "tdtk_last_error", "tdtk_device_count", "tdtk_pool_trim", "tdtk_build_respeculated", "tdtk_version", "tdtk_tree_create", "tdtk_tree_create_from_scan", "tdtk_tree_create_from_scans", "tdtk_scan_mark_original", "tdtk_scan_download_original", "tdtk_tree_destroy",
     "tdtk_tree_get_info", "tdtk_tree_verify", "tdtk_find_closest", "tdtk_find_closest_dev", "tdtk_find_closest_along_dir",
     "tdtk_knn_search", "tdtk_fixed_range_search", "tdtk_normals_knn", "tdtk_normals_range",
-    "tdtk_normals_adaptive_knn", "tdtk_normals_adaptive_apx_knn",
+    "tdtk_normals_adaptive_knn", "tdtk_normals_adaptive_apx_knn", "tdtk_knn_range_search", "tdtk_normals_knn_range",
     "tdtk_fixed_range_search_along_dir", "tdtk_fixed_range_search_between", "tdtk_aabb_search", "tdtk_segment_search_all",
     "tdtk_segment_search_nearest",
     "tdtk_get_pt_pairs", "tdtk_scan_create", "tdtk_scan_destroy", "tdtk_scan_size",
@@ -152,6 +152,7 @@ def lib():
                                         C.c_void_p, C.c_int, C.c_void_p]
     L.tdtk_find_closest_along_dir.argtypes = [C.c_void_p, _dp, _dp, C.c_size_t, C.c_double, _ip, _dp]
     L.tdtk_knn_search.argtypes = [C.c_void_p, _dp, C.c_size_t, C.c_int, _ip, _dp]
+    L.tdtk_knn_range_search.argtypes = [C.c_void_p, _dp, C.c_size_t, C.c_int, C.c_double, _ip, _dp, _ip]
     L.tdtk_fixed_range_search.argtypes = [C.c_void_p, _dp, C.c_size_t, C.c_double, _u64p, _ip, _dp, C.c_size_t, _u64p]
     for name in ("tdtk_fixed_range_search_along_dir", "tdtk_fixed_range_search_between", "tdtk_segment_search_all"):
         getattr(L, name).argtypes = [C.c_void_p, _dp, _dp, C.c_size_t, C.c_double, _u64p, _ip, C.c_size_t, _u64p]
@@ -159,6 +160,7 @@ def lib():
     L.tdtk_segment_search_nearest.argtypes = [C.c_void_p, _dp, _dp, C.c_size_t, C.c_double, _ip, _dp]
     L.tdtk_normals_knn.argtypes = [_dp, C.c_size_t, C.c_int, _dp, C.c_int, C.c_int, _dp, _ip]
     L.tdtk_normals_range.argtypes = [_dp, C.c_size_t, C.c_double, _dp, C.c_int, C.c_int, _dp]
+    L.tdtk_normals_knn_range.argtypes = [_dp, C.c_size_t, C.c_int, C.c_double, _dp, C.c_int, C.c_int, _dp, _ip, _ip]
     L.tdtk_normals_adaptive_knn.argtypes = [_dp, C.c_size_t, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, _ip, _ip]
     L.tdtk_normals_adaptive_apx_knn.argtypes = [_dp, C.c_size_t, C.c_int, C.c_int, _dp, C.c_double, C.c_int, _dp, _ip, _ip]
     L.tdtk_get_pt_pairs.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_size_t, C.c_size_t, C.c_int, C.c_int,

@@ -1481,6 +1481,42 @@ int tdtk_knn_search(const tdtk_tree* t, const double* q, size_t K, int k, int32_
   return TDTK_OK;
 }
 
+int tdtk_knn_range_search(const tdtk_tree* t, const double* q, size_t K, int k, double sqRad2, int32_t* idx, double* d2,
+                          int32_t* counts)
+{
+  if (!t || (!q && K) || (!idx && K)) { set_error("NULL argument"); return TDTK_EINVAL; }
+  int rc;
+  if ((rc = knn_check_k(k))) return rc;
+  if (!std::isfinite(sqRad2)) { set_error("sqRad2 must be finite"); return TDTK_EINVAL; }
+  Ctx* c;
+  if ((rc = get_ctx(t->device, &c))) return rc;
+  if (K == 0) return TDTK_OK;
+  const size_t L = K * (size_t)k;
+  if (sqRad2 <= 0) {     // no Dist2 is below it: every list is empty, nothing to walk
+    std::fill(idx, idx + L, -1);
+    if (d2) std::fill(d2, d2 + L, -1.0);
+    if (counts) std::fill(counts, counts + K, 0);
+    return TDTK_OK;
+  }
+  if ((rc = c->ws[WS_TMPA].ensure(3 * K * sizeof(double)))) return rc;
+  if ((rc = c->ws[WS_IDX].ensure((L + K) * sizeof(int32_t)))) return rc;       // WS_IDX: the lists | counts
+  if (d2 && (rc = c->ws[WS_TMPB].ensure(L * sizeof(double)))) return rc;
+  HIPCHK(hipMemcpyAsync(c->ws[WS_TMPA].p, q, 3 * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  QueryArgs a;
+  if ((rc = query_prepare(c, t, c->ws[WS_TMPA].as<double>(), K, a))) return rc;
+  a.k = k;
+  a.r2 = sqRad2;
+  a.idx = c->ws[WS_IDX].as<int32_t>();
+  a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
+  a.nr_out = counts ? a.idx + L : nullptr;
+  HIPCHK(launch_knn_range(a, false, c->stream));
+  HIPCHK(hipMemcpyAsync(idx, a.idx, L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (counts) HIPCHK(hipMemcpyAsync(counts, a.nr_out, K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return TDTK_OK;
+}
+
 int tdtk_fixed_range_search(const tdtk_tree* t, const double* q, size_t K, double sqRad2, uint64_t* offsets, int32_t* idx,
                             double* d2, size_t cap, uint64_t* total)
 {
@@ -1689,6 +1725,41 @@ int tdtk_normals_range(const double* xyz, size_t n, double sqRad2, const double 
   a.normals = c->ws[WS_TMPB].as<double>();
   HIPCHK(launch_range_normals(a, c->stream));
   HIPCHK(hipMemcpyAsync(normals_out, a.normals, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return TDTK_OK;
+}
+
+int tdtk_normals_knn_range(const double* xyz, size_t n, int k, double sqRad2, const double rPos[3], int bucket, int device,
+                           double* normals_out, int32_t* knn_out, int32_t* counts_out)
+{
+  if (!rPos) { set_error("rPos is NULL"); return TDTK_EINVAL; }
+  if (!xyz || n == 0) { set_error("Could not calculate normals, XYZ data is empty"); return TDTK_EINVAL; }
+  if (!normals_out) { set_error("NULL argument"); return TDTK_EINVAL; }
+  if (k < 1) { set_error("k must be >= 1"); return TDTK_EINVAL; }
+  int rc;
+  if ((rc = tree_check_args(n, bucket))) return rc;
+  if ((rc = knn_check_k(k))) return rc;
+  if (!std::isfinite(sqRad2)) { set_error("sqRad2 must be finite"); return TDTK_EINVAL; }
+  if (!(sqRad2 > 0)) { set_error("sqRad2 must be > 0 (an empty neighbourhood has no mean)"); return TDTK_EINVAL; }
+  Ctx* c;
+  if ((rc = get_ctx(device, &c))) return rc;
+  std::unique_ptr<tdtk_tree> t;
+  if ((rc = normals_tree(c, xyz, n, bucket, device, t))) return rc;
+  const size_t L = knn_out ? n * (size_t)k : 0;       // WS_IDX: the lists | counts
+  if ((rc = c->ws[WS_TMPB].ensure(3 * n * sizeof(double)))) return rc;
+  if ((rc = c->ws[WS_IDX].ensure((L + n) * sizeof(int32_t)))) return rc;
+  QueryArgs a;
+  if ((rc = query_prepare(c, t.get(), c->ws[WS_TMPA].as<double>(), n, a))) return rc;
+  a.k = k;
+  a.r2 = sqRad2;
+  a.rx = rPos[0]; a.ry = rPos[1]; a.rz = rPos[2];
+  a.normals = c->ws[WS_TMPB].as<double>();
+  a.knn_out = knn_out ? c->ws[WS_IDX].as<int32_t>() : nullptr;
+  a.nr_out = counts_out ? c->ws[WS_IDX].as<int32_t>() + L : nullptr;
+  HIPCHK(launch_knn_range(a, true, c->stream));
+  HIPCHK(hipMemcpyAsync(normals_out, a.normals, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (knn_out) HIPCHK(hipMemcpyAsync(knn_out, a.knn_out, L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (counts_out) HIPCHK(hipMemcpyAsync(counts_out, a.nr_out, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return TDTK_OK;
 }

@@ -1,4 +1,5 @@
-// Argument block and launchers of query.hip: k nearest neighbours, fixed-radius search, the normals built on them, and the
+// Argument block and launchers of query.hip: k nearest neighbours, fixed-radius and k-nearest-within-radius search, the normals
+// built on them, and the
 // cylinder / box / segment queries.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -7,7 +8,7 @@
 
 namespace tdtk {
 
-constexpr int KNN_MAX_K = 64;   // largest k of tdtk_knn_search / tdtk_normals_knn (the LDS-list kernel's capacity)
+constexpr int KNN_MAX_K = 64;   // largest k of tdtk_knn_search / tdtk_knn_range_search and their normals (the LDS-list kernel's capacity)
 
 struct QueryArgs {
   const KdNode* nodes;
@@ -34,6 +35,8 @@ struct QueryArgs {
   // adaptive-k normals
   int kmin, kmax;              // adaptive-k normals: every query tries k = kmin + 1 .. kmax + 1
   int32_t* k_used;             // adaptive-k normals: [n] the kidx of the list the normal was computed from (nullable)
+  // k nearest within a radius (k, r2, idx / d2 / normals / knn_out as the k-NN kernels')
+  int32_t* nr_out;             // [n] the length of every list, caller order (nullable)
 };
 
 // the four list queries of the shape walks (launch_shape_count / launch_shape_fill)
@@ -41,6 +44,7 @@ enum ShapeMode { SHAPE_ALONG_DIR = 0, SHAPE_BETWEEN = 1, SHAPE_AABB = 2, SHAPE_S
 
 size_t query_overflow_entries(size_t n, uint32_t max_depth);
 hipError_t launch_knn(const QueryArgs& a, bool normals, hipStream_t s);
+hipError_t launch_knn_range(const QueryArgs& a, bool normals, hipStream_t s);  // launch_knn within a.r2; a.nr_out
 hipError_t launch_knn_adaptive(const QueryArgs& a, hipStream_t s);            // kmax + 1 <= KNN_MAX_K; a.normals, a.k_used, a.knn_out
 hipError_t launch_range_count(const QueryArgs& a, hipStream_t s);
 hipError_t launch_range_fill(const QueryArgs& a, hipStream_t s);

@@ -1,6 +1,6 @@
-// lib3dtk_hip.so -- k nearest neighbours and fixed-radius search on the resident kd-tree, the two normal estimators built
-// on them, and the cylinder, box and segment queries: KDTreeImpl::_KNNSearch (kdTreeImpl.h:627-682), _FixedRangeSearch
-// (kdTreeImpl.h:585-625), calculateNormalsKNN / calculateNormalsRange with calculateNormal's PCA (normals.cc:369-439,
+// lib3dtk_hip.so -- k nearest neighbours, fixed-radius search and k-nearest-within-radius search on the resident kd-tree,
+// the normal estimators built on them, and the cylinder, box and segment queries: KDTreeImpl::_KNNSearch (kdTreeImpl.h:627-682),
+// _FixedRangeSearch (kdTreeImpl.h:585-625), _KNNRangeSearch (kdTreeImpl.h:684-745), calculateNormalsKNN / calculateNormalsRange with calculateNormal's PCA (normals.cc:369-439,
 // 442-516, 518-558), _fixedRangeSearchAlongDir / _fixedRangeSearchBetween2Points / _AABBSearch / _segmentSearch_all /
 // _segmentSearch_1NearestPoint (kdTreeImpl.h:432-577, 747-913).
 //
@@ -30,6 +30,18 @@
 //   * myd = splitval - p[axis]; myd >= 0: child1 first, child2 after it only if myd*myd < r2; otherwise child2 first and
 //     child1 under the same condition.  r2 never changes, so the condition is tested when the far child is pushed.
 //   * leaf: every point with Dist2 < r2, in bucket order; the list is in visiting order.
+// k nearest within a radius (KDtree::kNearestRangeSearch, kd.cc:137-171; _KNNRangeSearch, kdTreeImpl.h:684-745), in the
+// pointer flavour: the list's pointers come from calloc, so closest_neighbors[k-1] == 0 is "the list is not full", which is
+// distances[k-1] == -1 (a slot gets its pointer and its distance together).  r2 (sqRad2) is fixed for the whole walk:
+//   * the k-NN list: k slots, distances start at -1, a point goes in before the first slot that is unset or strictly larger.
+//   * leaf: scanned whenever it is reached, in bucket order.  A point is skipped when Dist2 >= r2, in that sense (a NaN
+//     distance is NOT skipped); otherwise it is inserted.
+//   * internal node: a is computed on EVERY entry, not only when the list is full.  List not full: prune when a >= 0 &&
+//     a*a >= r2.  List full: prune when a >= 0 && a*a >= distances[k-1].
+//   * myd = splitval - p[axis]; myd >= 0: child1 first, otherwise child2 -- the range search's rule, not _KNNSearch's strict
+//     p < splitval.  The far child only if myd*myd < r2: the radius, never the k-th distance, so the test is made at the
+//     push.  When the far child is popped it meets its own box test with the list as it is then.
+//   * result: the slots with a distance >= 0, in list order, and their number (0 .. k).
 // Adaptive k (calculateNormalsAdaptiveKNN, normals.cc:563-682), per point, kidx = kmin .. kmax:
 //   * a FRESH k-NN walk with k = kidx + 1: new list, empty stack, the rules above.  Not one walk at kmax + 1 cut to
 //     prefixes: a node's box is fl((min+max)/2) +- fl((max-min)/2) and may exclude one of its own points by an ulp, so a
@@ -291,6 +303,44 @@ __device__ void range_walk(const QueryArgs& a, const double qx, const double qy,
   }
 }
 
+// k nearest within r2 (_KNNRangeSearch): knn_walk's list under range_walk's child order and plane test
+template <int BLOCK, class LIST>
+__device__ void knn_range_walk(const QueryArgs& a, const double qx, const double qy, const double qz, const double r2, LIST& L,
+                               LaneStackQ<BLOCK, Q_SD>& st)
+{
+  uint32_t cur = a.root_ref;
+  for (;;) {
+    if (cur & REF_LEAF) {
+      uint32_t start, count;
+      leaf_span(a, cur, start, count);
+      for (uint32_t i = 0; i < count; i++) {
+        const KdPoint p = a.pts[start + i];
+        const double md = dist2(p, qx, qy, qz);
+        if (md >= r2) continue;
+        L.insert(md, start + i);
+      }
+    } else {
+      const KdNode nd = a.nodes[cur & REF_VAL];
+      const double ap = box_dist(nd, qx, qy, qz);
+      const double bound = L.full() ? L.kth : r2;
+      if (!(ap >= 0.0 && ap * ap >= bound)) {
+        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
+        const double qa = (axis == 0) ? qx : ((axis == 1) ? qy : qz);
+        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2c = nd.c2 & ~REF_AXIS;
+        const double myd = nd.splitval - qa;
+        const bool first = myd >= 0.0;
+        if (myd * myd < r2) st.push(first ? r2c : r1, 0.0);
+        cur = first ? r1 : r2c;
+        continue;
+      }
+    }
+    if (st.sp == 0) break;
+    --st.sp;
+    double unused;
+    st.top(cur, unused);
+  }
+}
+
 // calculateNormal (normals.cc:518-558) over a list the caller enumerates: each(f) calls f(point) for the nr points of the
 // list in list order, and is called twice (mean, then covariance -- the arithmetic of k_ann_normals: mean / nr, then
 // A = (1/nr X^T) X summed in list order, lower triangle of z); eigen3.h does the rest.  nr is read after the first pass (the
@@ -421,6 +471,106 @@ __global__ void __launch_bounds__(Q_BLOCK_L) k_knn_lds(const QueryArgs a_)
     knn_walk<Q_BLOCK_L>(a, qx, qy, qz, L, st);
     int nr = 0;
     for (int j = 0; j < k; j++) nr += (L.dist(j) >= 0.0) ? 1 : 0;   // kdIndexed.cc:152-156
+    int32_t* row = NORMALS ? a.knn_out : a.idx;
+    row = row ? row + o * k : nullptr;
+    double* drow = (!NORMALS && a.d2) ? a.d2 + o * k : nullptr;
+    for (int j = 0; j < k; j++) {
+      const bool v = j < nr;
+      if (row) row[j] = v ? a.pts[v ? L.slot(j) : 0u].orig : -1;
+      if (drow) drow[j] = v ? L.dist(j) : -1.0;
+    }
+    if (NORMALS) {
+      auto each = [&](auto&& f) { for (int j = 0; j < nr; j++) f(a.pts[L.slot(j)]); };
+      list_normal(each, nr, qx, qy, qz, a, a.normals + 3 * o);
+    }
+  }
+}
+
+// ---- k nearest within a radius (kNearestRangeSearch) and the normals over its lists ------------------------------------
+// k_knn_reg and k_knn_lds with knn_range_walk in place of knn_walk (their empty-asm idiom for k0 / jl is explained there),
+// and one more output: nr_out [n], the length of every list (nullable).  A list may be empty here (no point within r2 of a
+// query); list_normal on it gives NaN, calculateNormal's 0 / 0 -- the normals' own queries always find themselves, except
+// under k_range_normals' caveat.
+
+// the register-list form
+template <int KC, bool NORMALS>
+__global__ void __launch_bounds__(Q_BLOCK) k_knnr_reg(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  LaneStackQ<Q_BLOCK, Q_SD> st;
+  stack_init<Q_BLOCK>(st, s_stack, a);
+  ListReg<KC> L;
+  const int k = a.k;
+  const size_t T = (size_t)gridDim.x * Q_BLOCK;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+    const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
+    const size_t o = a.order ? (size_t)a.order[i] : i;
+    int k0 = KC - k;
+    asm volatile("" : "+v"(k0));
+    L.init(k0);
+    st.sp = 0;
+    knn_range_walk<Q_BLOCK>(a, qx, qy, qz, a.r2, L, st);
+    // entries: the slots with a distance >= 0 (kd.cc:158-165), which are the first nr
+    int nr = 0;
+#pragma unroll
+    for (int j = 0; j < KC; j++) {
+      int jl = j - k0;
+      asm volatile("" : "+v"(jl));
+      nr += (jl >= 0 && L.d[j] >= 0.0) ? 1 : 0;
+    }
+    if (NORMALS) {
+      auto each = [&](auto&& f) {
+#pragma unroll
+        for (int j = 0; j < KC; j++) {
+          int jl = j - k0;
+          asm volatile("" : "+v"(jl));
+          if (jl >= 0 && jl < nr) f(a.pts[L.s[j]]);
+        }
+      };
+      list_normal(each, nr, qx, qy, qz, a, a.normals + 3 * o);
+    }
+    if (a.nr_out) a.nr_out[o] = nr;
+    int32_t* row = NORMALS ? a.knn_out : a.idx;
+    row = row ? row + o * k : nullptr;
+    double* drow = (!NORMALS && a.d2) ? a.d2 + o * k : nullptr;
+#pragma unroll
+    for (int j = 0; j < KC; j++) {
+      int jl = j - k0;
+      asm volatile("" : "+v"(jl));
+      if (jl >= 0) {
+        const bool v = jl < nr;
+        if (row) row[jl] = v ? a.pts[v ? L.s[j] : 0u].orig : -1;     // (an unset slot's point is never loaded)
+        if (drow) drow[jl] = v ? L.d[j] : -1.0;
+      }
+    }
+  }
+}
+
+// the LDS-list form (33 <= k <= 64)
+template <bool NORMALS>
+__global__ void __launch_bounds__(Q_BLOCK_L) k_knnr_lds(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK_L];
+  __shared__ double s_d[KNN_MAX_K][Q_BLOCK_L];
+  __shared__ uint32_t s_s[KNN_MAX_K][Q_BLOCK_L];
+  LaneStackQ<Q_BLOCK_L, Q_SD> st;
+  stack_init<Q_BLOCK_L>(st, s_stack, a);
+  ListLds<Q_BLOCK_L> L;
+  L.ld = &s_d[0][threadIdx.x];
+  L.ls = &s_s[0][threadIdx.x];
+  const int k = a.k;
+  const size_t T = (size_t)gridDim.x * Q_BLOCK_L;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK_L + threadIdx.x; i < a.n; i += T) {
+    const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
+    const size_t o = a.order ? (size_t)a.order[i] : i;
+    L.init(k);
+    st.sp = 0;
+    knn_range_walk<Q_BLOCK_L>(a, qx, qy, qz, a.r2, L, st);
+    int nr = 0;
+    for (int j = 0; j < k; j++) nr += (L.dist(j) >= 0.0) ? 1 : 0;   // kd.cc:158-165
+    if (a.nr_out) a.nr_out[o] = nr;
     int32_t* row = NORMALS ? a.knn_out : a.idx;
     row = row ? row + o * k : nullptr;
     double* drow = (!NORMALS && a.d2) ? a.d2 + o * k : nullptr;
@@ -905,6 +1055,29 @@ hipError_t launch_knn(const QueryArgs& a, bool normals, hipStream_t s)
     else hipLaunchKernelGGL(k_knn_lds<false>, gl, bl, 0, s, a);
   }
 #undef KNN_REG
+  return hipGetLastError();
+}
+
+hipError_t launch_knn_range(const QueryArgs& a, bool normals, hipStream_t s)
+{
+  if (a.k < 1 || a.k > KNN_MAX_K) return hipErrorInvalidValue;
+  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
+#define KNNR_REG(KC)                                                                        \
+  do {                                                                                      \
+    if (normals) hipLaunchKernelGGL((k_knnr_reg<KC, true>), g, b, 0, s, a);                 \
+    else hipLaunchKernelGGL((k_knnr_reg<KC, false>), g, b, 0, s, a);                        \
+  } while (0)
+  // launch_knn's capacities
+  if (a.k <= 4) KNNR_REG(4);
+  else if (a.k <= 10) KNNR_REG(10);
+  else if (a.k <= 20) KNNR_REG(20);
+  else if (a.k <= 32) KNNR_REG(32);
+  else {
+    const dim3 gl(q_grid(a.n, Q_BLOCK_L)), bl(Q_BLOCK_L);
+    if (normals) hipLaunchKernelGGL(k_knnr_lds<true>, gl, bl, 0, s, a);
+    else hipLaunchKernelGGL(k_knnr_lds<false>, gl, bl, 0, s, a);
+  }
+#undef KNNR_REG
   return hipGetLastError();
 }
 

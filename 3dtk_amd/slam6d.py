@@ -247,6 +247,22 @@ class KDtree:
         check(lib().tdtk_knn_search(self._h, dptr(q), len(q), int(k), iptr(idx), dptr(d2)))
         return idx, d2
 
+    def kNearestRangeSearch(self, p, k, sqRad2, threadNum=0):
+        """kd.cc:137-171 (py3dtk.cc:538-545).  Returns the indices of the at most k nearest points with Dist2 < sqRad2,
+        nearest first (the reference returns their coordinates)."""
+        idx, _, counts = self.kNearestRangeSearchBatch(np.asarray(p, dtype=np.float64).reshape(1, 3), k, sqRad2)
+        return [int(i) for i in idx[0, :counts[0]]]
+
+    def kNearestRangeSearchBatch(self, q, k, sqRad2):
+        """tdtk_knn_range_search: (idx [K][k], d2 [K][k], counts [K]); -1 / -1.0 behind a row's counts[i] entries"""
+        q = f64(q).reshape(-1, 3)
+        idx = np.empty((len(q), int(k)), np.int32)
+        d2 = np.empty((len(q), int(k)), np.float64)
+        counts = np.empty(len(q), np.int32)
+        check(lib().tdtk_knn_range_search(self._h, dptr(q), len(q), int(k), float(sqRad2), iptr(idx), dptr(d2),
+                                          iptr(counts)))
+        return idx, d2, counts
+
     def fixedRangeSearch(self, p, sqRad2, threadNum=0):
         """kdIndexed.cc:215-230.  Returns the indices of every point with Dist2 < sqRad2, in the reference's order."""
         _, idx, _ = self.fixedRangeSearchBatch(np.asarray(p, dtype=np.float64).reshape(1, 3), sqRad2)
@@ -724,6 +740,20 @@ def calculateNormalsRange(points, sqRad2, rPos, bucketSize=20, device=0):
     check(lib().tdtk_normals_range(dptr(xyz), len(xyz), float(sqRad2), dptr(f64(rPos)), int(bucketSize), int(device),
                                    dptr(out)))
     return out
+
+
+def calculateNormalsKNNRange(points, k, sqRad2, rPos, bucketSize=20, device=0, want_knn=False):
+    """calculateNormalsKNN (normals.cc:442-516) over kNearestRangeSearch lists (kd.cc:137-171) on the device -- the reference
+    has the search and the PCA, not this combination: every point's normal from its at most k nearest neighbours within
+    sqRad2.  Returns the [n][3] normals in point order and, with want_knn, the [n][k] lists (-1 behind their entries) and
+    their [n] lengths."""
+    xyz = f64(points).reshape(-1, 3)
+    out = np.empty_like(xyz)
+    knn = np.empty((len(xyz), max(int(k), 0)), np.int32) if want_knn else None
+    counts = np.empty(len(xyz), np.int32) if want_knn else None
+    check(lib().tdtk_normals_knn_range(dptr(xyz), len(xyz), int(k), float(sqRad2), dptr(f64(rPos)), int(bucketSize),
+                                       int(device), dptr(out), iptr(knn), iptr(counts)))
+    return (out, knn, counts) if want_knn else out
 
 
 def _adaptive_result(out, k_used, knn, want_k, want_knn):

@@ -172,6 +172,15 @@ int tdtk_find_closest_along_dir(const tdtk_tree* t, const double* q, const doubl
  * distances.  A tree of M < k points gives M entries per row, the rest -1 / -1.0.  Errors: k < 1 (TDTK_EINVAL),
  * k > 64 (TDTK_EUNSUP: the device lists hold at most 64 entries).                                          */
 int tdtk_knn_search(const tdtk_tree* t, const double* q, size_t K, int k, int32_t* idx, double* d2);
+/* batched KDtree::kNearestRangeSearch (kd.cc:137-171; _KNNRangeSearch kdTreeImpl.h:684-745, the pointer flavour the Python
+ * binding offers, py3dtk.cc:538-545): of the points with Dist2 < sqRad2 the k nearest, nearest first, ties in the walk's
+ * visiting order.  idx [K][k], -1 behind a row's entries; d2 (nullable) [K][k], -1.0 there; counts (nullable) [K] the
+ * number of entries, 0 .. k.  The reference returns the points' coordinates, this call their indices.  Errors, in this
+ * order and before anything is launched or written: NULL t / q / idx, k < 1 (TDTK_EINVAL); k > 64 (TDTK_EUNSUP); a
+ * non-finite sqRad2 (TDTK_EINVAL -- a deviation: the reference would walk with comparisons that are all false).
+ * sqRad2 <= 0 gives empty rows and launches nothing; K == 0 is a no-op.                                      */
+int tdtk_knn_range_search(const tdtk_tree* t, const double* q, size_t K, int k, double sqRad2, int32_t* idx, double* d2,
+                          int32_t* counts);
 /* batched KDtreeIndexed::fixedRangeSearch (kdIndexed.cc:215-230; _FixedRangeSearch kdTreeImpl.h:585-625): every point
  * with Dist2 < sqRad2, in the reference's visiting order, as CSR lists.  offsets [K+1] is always filled (query i owns
  * idx[offsets[i] .. offsets[i+1])) and *total = offsets[K].  When cap < *total nothing else is written and the call
@@ -218,6 +227,15 @@ int tdtk_normals_knn(const double* xyz, size_t n, int k, const double rPos[3], i
  * at sqRad2, in visiting order.  Errors: n == 0, bucket < 1, sqRad2 <= 0 (the reference would divide 0 by 0). */
 int tdtk_normals_range(const double* xyz, size_t n, double sqRad2, const double rPos[3], int bucket, int device,
                        double* normals_out);
+/* calculateNormalsKNN (normals.cc:442-516) with kNearestRangeSearch (kd.cc:137-171) in place of kNearestNeighbors: the PCA
+ * of calculateNormal (normals.cc:518-558) over at most k neighbours, none at Dist2 >= sqRad2, in list order (every point's
+ * list holds the point itself).  The reference has NO such estimator: the search and the PCA are its own, their
+ * combination is this library's.  normals_out [n][3] in point order; knn_out (nullable) [n][k] the lists, -1 behind their
+ * entries; counts_out (nullable) [n] their lengths.  A list of one or two points gives what calculateNormal gives on it.
+ * Errors, in this order and before anything is launched or written: NULL xyz / rPos / normals_out, n == 0, k < 1,
+ * bucket < 1 (TDTK_EINVAL); k > 64 (TDTK_EUNSUP); sqRad2 non-finite or <= 0 (TDTK_EINVAL, as tdtk_normals_range). */
+int tdtk_normals_knn_range(const double* xyz, size_t n, int k, double sqRad2, const double rPos[3], int bucket, int device,
+                           double* normals_out, int32_t* knn_out, int32_t* counts_out);
 /* calculateNormalsAdaptiveKNN (normals.cc:563-682): a KDtree(points, bucket) (the reference's is 20) and, for every point,
  * kidx = kmin .. kmax: a fresh search for its kidx + 1 nearest neighbours, their mean, covariance and eigenvalues e1 <=
  * e2 <= e3; the loop stops at the first kidx with (e1 > 0.25 * e2) && (fabs(1.0 - e2 / e3) < 0.25), or at kmax.  The

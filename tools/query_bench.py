@@ -16,8 +16,12 @@ k = 10 and at (5, 20) (eps = 1.0), and the reference: the fixture generator's lo
 the reference library's searches and newmat's EigenValues, the glue in Python and therefore on one thread whatever
 --ref-threads says) on a fiftieth of --ref-queries points, scaled to the whole cloud; --only-adaptive runs nothing else.
 
+--hybrid adds k nearest within a radius at 1M points (queries = the points, k = 10 and 20, the fixed-radius leg's radius of
+about 20.6 neighbours): the walk and the normals over its lists, next to the k-NN walk / normals at the same k and the
+fixed-radius walk / normals at the same radius in the same run, and the mean list length; --only-hybrid runs nothing else.
+
 Kernel times: run the same command under `rocprofv3 --kernel-trace --stats` (k_knn_reg, k_range_count / k_range_fill,
-k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest, k_knn_adaptive_reg / k_knn_adaptive_lds, k_ann_adaptive)."""
+k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest, k_knn_adaptive_reg / k_knn_adaptive_lds, k_ann_adaptive, k_knnr_reg / k_knnr_lds)."""
 import argparse
 import importlib
 import json
@@ -185,6 +189,24 @@ def adaptive_legs(tdtk, pts, tag, rng, reps, nq, threads):
     return out
 
 
+def hybrid_legs(tdtk, pts, tag, reps):
+    """kNearestRangeSearch and calculateNormalsKNNRange, end to end like the other legs, each next to the k-NN and the
+    fixed-radius form it combines (their kernels, same cloud, same run)"""
+    out = {}
+    rpos = [0.0, 0.0, 0.0]
+    r2 = (20.0 * 3 / (4 * np.pi)) ** (2.0 / 3.0)                   # the fixed-radius leg's: ~20.6 neighbours per query
+    kd = tdtk.KDtree(pts, 20)
+    out["range_20nn_%s" % tag] = timed(lambda: kd.fixedRangeSearchBatch(pts, r2), reps)
+    out["normals_range_%s" % tag] = timed(lambda: tdtk.calculateNormalsRange(pts, r2, rpos), reps)
+    for k in (10, 20):
+        out["knn_k%d_%s" % (k, tag)] = timed(lambda: kd.kNearestNeighborsBatch(pts, k), reps)
+        out["knn_range_k%d_%s" % (k, tag)] = timed(lambda: kd.kNearestRangeSearchBatch(pts, k, r2), reps)
+        out["knn_range_k%d_%s_mean_list" % (k, tag)] = round(float(kd.kNearestRangeSearchBatch(pts, k, r2)[2].mean()), 2)
+        out["normals_knn_k%d_%s" % (k, tag)] = timed(lambda: tdtk.calculateNormalsKNN(pts, k, rpos), reps)
+        out["normals_knn_range_k%d_%s" % (k, tag)] = timed(lambda: tdtk.calculateNormalsKNNRange(pts, k, r2, rpos), reps)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000000,10000000")
@@ -195,6 +217,8 @@ def main():
     ap.add_argument("--only-segments", action="store_true", help="those legs alone")
     ap.add_argument("--adaptive", action="store_true", help="add the adaptive-k normals legs (1M points)")
     ap.add_argument("--only-adaptive", action="store_true", help="those legs alone")
+    ap.add_argument("--hybrid", action="store_true", help="add the k-nearest-within-radius legs (1M points)")
+    ap.add_argument("--only-hybrid", action="store_true", help="those legs alone")
     args = ap.parse_args()
     tdtk = importlib.import_module("3dtk_amd")
     if tdtk.device_count() < 1:
@@ -213,6 +237,12 @@ def main():
         # (the reference loop is Python glue around the library, about 1.2 ms per point: a fiftieth of --ref-queries)
         out.update(adaptive_legs(tdtk, pts, "1M", np.random.default_rng(2028), args.reps, args.ref_queries // 50, args.ref_threads))
         if args.only_adaptive:
+            print(json.dumps(out))
+            return
+    if args.hybrid or args.only_hybrid:
+        pts = np.random.default_rng(2029).uniform(-50, 50, (1_000_000, 3))
+        out.update(hybrid_legs(tdtk, pts, "1M", args.reps))
+        if args.only_hybrid:
             print(json.dumps(out))
             return
     for M in [int(s) for s in args.sizes.split(",")]:
