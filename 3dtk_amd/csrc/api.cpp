@@ -1392,7 +1392,11 @@ int tdtk_find_closest(const tdtk_tree* t, const double* q, size_t K, double maxd
 // tree's walk arguments and the stack overflow area
 // (d_v: a second vector per query [K][3], carried through the bin into WS_DX / WS_DY / WS_DZ -- the cylinder, box and
 // segment queries)
-static int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K, QueryArgs& a, const double* d_v = nullptr)
+// (box: 6 doubles, the lower and upper corner the bin's grid spans instead of the tree's root box; n_walks: the number of
+// walks the overflow area is sized for, where that is not K -- the collision kernels bin their model and walk once per
+// (frame, model point))
+static int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K, QueryArgs& a, const double* d_v = nullptr,
+                         const double* box = nullptr, size_t n_walks = 0)
 {
   int rc;
   int ids[] = {WS_QX, WS_QY, WS_QZ};
@@ -1409,8 +1413,8 @@ static int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K
   BinArgs b{};
   b.q = d_q; b.dir = d_v; b.n = K;
   for (int ax = 0; ax < 3; ax++) {
-    b.lo[ax] = t->bbmin[ax];
-    const double ext = t->bbmax[ax] - t->bbmin[ax];
+    b.lo[ax] = box ? box[ax] : t->bbmin[ax];
+    const double ext = (box ? box[3 + ax] : t->bbmax[ax]) - b.lo[ax];
     b.scale[ax] = (ext > 0) ? 32.0 / ext : 0.0;
   }
   b.hist = c->ws[WS_HIST].as<uint32_t>();
@@ -1424,7 +1428,7 @@ static int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K
   a.nodes = t->dev.nodes; a.pts = t->dev.pts; a.leaf_tab = t->dev.leaf_tab;
   a.root_ref = t->dev.root_ref; a.cb = t->dev.cb; a.cmask = t->dev.cmask;
   a.x = b.sx; a.y = b.sy; a.z = b.sz; a.order = b.order; a.n = K;
-  const size_t ovf = query_overflow_entries(K, t->info.max_depth);
+  const size_t ovf = query_overflow_entries(n_walks ? n_walks : K, t->info.max_depth);
   if (ovf) {
     if ((rc = c->ws[WS_OVF_M2].ensure(ovf * sizeof(double)))) return rc;
     if ((rc = c->ws[WS_OVF_REF].ensure(ovf * sizeof(uint32_t)))) return rc;
@@ -1669,6 +1673,156 @@ int tdtk_segment_search_nearest(const tdtk_tree* t, const double* p, const doubl
   HIPCHK(launch_segment_nearest(a, s));
   HIPCHK(hipMemcpyAsync(idx, a.idx, K * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, K * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return TDTK_OK;
+}
+
+}  // extern "C"
+
+// ---- collision detection along a trajectory (query.hip, "collision detection") ------------------------------------------
+// the checks the marking and the axis depth share; F * P items at most
+static int collide_check_args(const double* model, size_t P, const double* frames, size_t F, double radius)
+{
+  if (!model || (!frames && F)) { set_error("NULL argument"); return TDTK_EINVAL; }
+  if (P == 0) { set_error("the point model is empty"); return TDTK_EINVAL; }
+  if (!std::isfinite(radius) || !(radius > 0)) { set_error("radius must be finite and > 0"); return TDTK_EINVAL; }
+  size_t items;
+  if (__builtin_mul_overflow(F, P, &items)) { set_error("frames x model points exceeds size_t"); return TDTK_EINVAL; }
+  return TDTK_OK;
+}
+
+// the model [P][3] and the frames [F][16] side by side in WS_TMPB, the model binned on its own bounding box (a non-finite
+// coordinate takes no part in the box and lands in a border cell) into WS_QX / WS_QY / WS_QZ; `items` walks
+static int collide_prepare(Ctx* c, const tdtk_tree* t, const double* model, size_t P, const double* frames, size_t F,
+                           size_t items, double radius, QueryArgs& a)
+{
+  int rc;
+  if ((rc = c->ws[WS_TMPB].ensure((3 * P + 16 * F) * sizeof(double)))) return rc;
+  double* d_model = c->ws[WS_TMPB].as<double>();
+  double* d_frames = d_model + 3 * P;
+  HIPCHK(hipMemcpyAsync(d_model, model, 3 * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (F) HIPCHK(hipMemcpyAsync(d_frames, frames, 16 * F * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  double box[6] = {0, 0, 0, 0, 0, 0};
+  for (int ax = 0; ax < 3; ax++) {
+    bool any = false;
+    for (size_t i = 0; i < P; i++) {
+      const double v = model[3 * i + ax];
+      if (!std::isfinite(v)) continue;
+      if (!any || v < box[ax]) box[ax] = v;
+      if (!any || v > box[3 + ax]) box[3 + ax] = v;
+      any = true;
+    }
+  }
+  if ((rc = query_prepare(c, t, d_model, P, a, nullptr, box, items))) return rc;
+  a.order = nullptr;
+  a.n = items;
+  a.P = P;
+  a.frames = d_frames;
+  a.r2 = radius * radius;
+  return TDTK_OK;
+}
+
+// the points of env_xyz [M][3] whose mask byte is (take != 0) or is not (take == 0) set, in ascending index
+static std::vector<double> collide_compact(const double* env_xyz, size_t M, const uint8_t* colliding, int take)
+{
+  std::vector<double> out;
+  for (size_t i = 0; i < M; i++)
+    if ((colliding[i] != 0) == (take != 0)) out.insert(out.end(), env_xyz + 3 * i, env_xyz + 3 * i + 3);
+  return out;
+}
+
+extern "C" {
+
+int tdtk_collision_mark(const tdtk_tree* env, const double* model, size_t P, const double* frames, size_t F, double radius,
+                        int cmethod, uint8_t* colliding, uint64_t* num_colliding)
+{
+  if (!env || !colliding || !num_colliding) { set_error("NULL argument"); return TDTK_EINVAL; }
+  int rc;
+  if ((rc = collide_check_args(model, P, frames, F, radius))) return rc;
+  if (cmethod != 1 && cmethod != 2) { set_error("cmethod must be 1 (spheres) or 2 (segments)"); return TDTK_EINVAL; }
+  if (cmethod == 2 && F == 0) { set_error("the segment method needs a trajectory of at least one frame"); return TDTK_EINVAL; }
+  Ctx* c;
+  if ((rc = get_ctx(env->device, &c))) return rc;
+  hipStream_t s = c->stream;
+  const size_t M = env->M;
+  const size_t items = (cmethod == 1 ? F : F - 1) * P;
+  // WS_IDX: the count (8 bytes) | the mask
+  if ((rc = c->ws[WS_IDX].ensure(8 + M))) return rc;
+  unsigned long long* d_count = c->ws[WS_IDX].as<unsigned long long>();
+  uint8_t* d_mask = c->ws[WS_IDX].as<uint8_t>() + 8;
+  HIPCHK(hipMemsetAsync(c->ws[WS_IDX].p, 0, 8 + M, s));
+  if (items) {
+    QueryArgs a;
+    if ((rc = collide_prepare(c, env, model, P, frames, F, items, radius, a))) return rc;
+    a.mask = d_mask;
+    HIPCHK(launch_collide_mark(a, cmethod, s));
+    HIPCHK(launch_collide_count(d_mask, M, d_count, s));
+  }
+  unsigned long long count = 0;
+  HIPCHK(hipMemcpyAsync(colliding, d_mask, M, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *num_colliding = count;
+  return TDTK_OK;
+}
+
+int tdtk_collision_depth_closest(const double* env_xyz, size_t M, const uint8_t* colliding, int bucket, int device,
+                                 float* dist, uint64_t* n_unreached)
+{
+  if (!env_xyz || !colliding || !dist) { set_error("NULL argument"); return TDTK_EINVAL; }
+  size_t nc = 0;
+  for (size_t i = 0; i < M; i++) nc += colliding[i] != 0;
+  if (nc == 0) { set_error("no colliding point"); return TDTK_EINVAL; }
+  if (nc == M) { set_error("no non-colliding point (the tree would be empty)"); return TDTK_EINVAL; }
+  int rc;
+  if ((rc = tree_check_args(M - nc, bucket))) return rc;
+  Ctx* c;
+  if ((rc = get_ctx(device, &c))) return rc;
+  const std::vector<double> rest = collide_compact(env_xyz, M, colliding, 0);
+  const std::vector<double> hit = collide_compact(env_xyz, M, colliding, 1);
+  std::unique_ptr<tdtk_tree> t;
+  if ((rc = normals_tree(c, rest.data(), M - nc, bucket, device, t))) return rc;
+  std::vector<int32_t> idx(nc);
+  std::vector<double> d2(nc);
+  if ((rc = tdtk_find_closest(t.get(), hit.data(), nc, 1000000.0, idx.data(), d2.data()))) return rc;
+  uint64_t unreached = 0;
+  for (size_t i = 0; i < nc; i++) {
+    if (idx[i] < 0) { dist[i] = 1000.0f; ++unreached; }
+    else dist[i] = (float)std::sqrt(d2[i]);
+  }
+  if (n_unreached) *n_unreached = unreached;
+  return TDTK_OK;
+}
+
+int tdtk_collision_depth_axis(const double* env_xyz, size_t M, const uint8_t* colliding, const double* model, size_t P,
+                              const double* frames, size_t F, double radius, int bucket, int device, float* dist)
+{
+  if (!env_xyz || !colliding || !dist) { set_error("NULL argument"); return TDTK_EINVAL; }
+  int rc;
+  if ((rc = collide_check_args(model, P, frames, F, radius))) return rc;
+  size_t nc = 0;
+  for (size_t i = 0; i < M; i++) nc += colliding[i] != 0;
+  if (nc == 0) { set_error("no colliding point (the tree would be empty)"); return TDTK_EINVAL; }
+  if ((rc = tree_check_args(nc, bucket))) return rc;
+  Ctx* c;
+  if ((rc = get_ctx(device, &c))) return rc;
+  hipStream_t s = c->stream;
+  const std::vector<double> hit = collide_compact(env_xyz, M, colliding, 1);
+  std::unique_ptr<tdtk_tree> t;
+  if ((rc = normals_tree(c, hit.data(), nc, bucket, device, t))) return rc;
+  // WS_D2: the minima (the bits of fp64 squared distances); WS_IDX: the depths
+  if ((rc = c->ws[WS_D2].ensure(nc * sizeof(unsigned long long)))) return rc;
+  if ((rc = c->ws[WS_IDX].ensure(nc * sizeof(float)))) return rc;
+  unsigned long long* d_min = c->ws[WS_D2].as<unsigned long long>();
+  HIPCHK(launch_collide_depth_init(d_min, nc, s));
+  if (F) {
+    QueryArgs a;
+    if ((rc = collide_prepare(c, t.get(), model, P, frames, F, F * P, radius, a))) return rc;
+    a.dmin = d_min;
+    HIPCHK(launch_collide_depth_axis(a, s));
+  }
+  HIPCHK(launch_collide_depth_finish(d_min, nc, c->ws[WS_IDX].as<float>(), s));
+  HIPCHK(hipMemcpyAsync(dist, c->ws[WS_IDX].p, nc * sizeof(float), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return TDTK_OK;
 }

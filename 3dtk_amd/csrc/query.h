@@ -37,6 +37,12 @@ struct QueryArgs {
   int32_t* k_used;             // adaptive-k normals: [n] the kidx of the list the normal was computed from (nullable)
   // k nearest within a radius (k, r2, idx / d2 / normals / knn_out as the k-NN kernels')
   int32_t* nr_out;             // [n] the length of every list, caller order (nullable)
+  // collision detection along a trajectory: x / y / z are the P model points (spatially sorted), n the number of
+  // (frame, model point) or (segment, model point) items, r2 the squared radius
+  const double* frames;        // [F][16], column-major
+  size_t P;                    // model points
+  uint8_t* mask;               // marking: [M], 1 where the model touches the tree's point (input order)
+  unsigned long long* dmin;    // depth along the model's axis: [M] the bits of the smallest squared distance
 };
 
 // the four list queries of the shape walks (launch_shape_count / launch_shape_fill)
@@ -52,6 +58,12 @@ hipError_t launch_range_normals(const QueryArgs& a, hipStream_t s);
 hipError_t launch_shape_count(const QueryArgs& a, int mode, hipStream_t s);   // a.counts, as launch_range_count
 hipError_t launch_shape_fill(const QueryArgs& a, int mode, hipStream_t s);    // a.idx at a.offsets, as launch_range_fill
 hipError_t launch_segment_nearest(const QueryArgs& a, hipStream_t s);         // a.idx [n], a.d2 [n] (nullable)
+// collision detection (a.x / y / z the model, a.frames, a.P, a.n items, a.r2)
+hipError_t launch_collide_mark(const QueryArgs& a, int cmethod, hipStream_t s);   // a.mask (cleared by the caller); 1: spheres, 2: segments
+hipError_t launch_collide_count(const uint8_t* mask, size_t M, unsigned long long* count, hipStream_t s);   // *count += set bytes
+hipError_t launch_collide_depth_init(unsigned long long* dmin, size_t M, hipStream_t s);
+hipError_t launch_collide_depth_axis(const QueryArgs& a, hipStream_t s);          // a.dmin
+hipError_t launch_collide_depth_finish(const unsigned long long* dmin, size_t M, float* dist, hipStream_t s);
 size_t range_scan_temp_bytes(size_t n);
 hipError_t launch_range_scan(const uint32_t* counts, unsigned long long* offsets, size_t n, void* tmp, size_t tmp_bytes,
                              hipStream_t s);

@@ -2,7 +2,8 @@
 // the normal estimators built on them, and the cylinder, box and segment queries: KDTreeImpl::_KNNSearch (kdTreeImpl.h:627-682),
 // _FixedRangeSearch (kdTreeImpl.h:585-625), _KNNRangeSearch (kdTreeImpl.h:684-745), calculateNormalsKNN / calculateNormalsRange with calculateNormal's PCA (normals.cc:369-439,
 // 442-516, 518-558), _fixedRangeSearchAlongDir / _fixedRangeSearchBetween2Points / _AABBSearch / _segmentSearch_all /
-// _segmentSearch_1NearestPoint (kdTreeImpl.h:432-577, 747-913).
+// _segmentSearch_1NearestPoint (kdTreeImpl.h:432-577, 747-913); and collision_model's marking and axis depth fused over the
+// range and segment walks (collision_model.cc:312-430, 714-800; "collision detection along a trajectory" below).
 //
 // Layout of every kernel here: one query per lane, the queries spatially binned first (launch_bin) so that the lanes of a
 // wave walk neighbouring parts of the tree, a grid-stride loop over the sorted queries, results written straight to the
@@ -1019,6 +1020,156 @@ __global__ void __launch_bounds__(Q_BLOCK) k_segment_nearest(const QueryArgs a_)
   }
 }
 
+// ---- collision detection along a trajectory (collision_model.cc) ----------------------------------------------------------
+// A point model moves through the tree's cloud along F frames (4x4, column-major).  Marking: every tree point within the
+// radius of a moved model point (method 1, handle_pointcloud CTYPE1, collision_model.cc:338-367: fixedRangeSearch) or of the
+// segment a model point sweeps between two consecutive frames (method 2, CTYPE2, :368-410: segmentSearch_all) gets a 1 in
+// a byte mask.  Depth along the model's axis (calculate_collidingdist2, :714-800): per (frame, model point) the nearest tree
+// point c1 of the segment from the moved point to its projection on the model's y axis, and every tree point within the
+// radius of c1 takes the minimum of Dist2(moved point, c1).  Both results are sets / minima, so they do not depend on the
+// order of the queries: item i is (frame or segment i / P, model point i % P), generated in the lane -- nothing of size
+// F x P exists anywhere.  The model is uploaded once in spatial order; consecutive lanes take consecutive model points of
+// one frame, and a rigid motion keeps neighbours neighbours, so a wave's lanes walk nearby parts of the tree.  The walks are
+// range_walk, shape_walk<SHAPE_SEGMENT> and segment_nearest_walk as they stand, under emitters that mark or minimise.
+
+// transform3 (globals.icc:1454-1463) of (x, y, z) by the frame T: (x*T0 + y*T4 + z*T8) + T12, and so on
+__device__ __forceinline__ void transform3(const double* T, const double x, const double y, const double z, double& ox,
+                                           double& oy, double& oz)
+{
+  const double xn = x * T[0] + y * T[4] + z * T[8];
+  const double yn = x * T[1] + y * T[5] + z * T[9];
+  const double zn = x * T[2] + y * T[6] + z * T[10];
+  ox = xn + T[12]; oy = yn + T[13]; oz = zn + T[14];
+}
+
+// the marking emitter of both list walks: fill_colliding (collision_model.cc:305-310).  Many lanes may store the same 1 to
+// the same byte: plain stores, no atomics.  Stored without a look at the byte first ("collision": the test
+// costs a dependent load per listed point and saves nothing that was measured)
+struct MarkEmit {
+  uint8_t* mask;
+  __device__ __forceinline__ void operator()(const KdPoint& p) const { mask[p.orig] = 1; }
+  __device__ __forceinline__ void operator()(const KdPoint& p, uint32_t, double) const { mask[p.orig] = 1; }
+};
+
+// the minimising emitter of the depth walk: "if (dist2 < dist[k]) dist[k] = dist2" for every k of the sphere around c1.
+// Non-negative doubles order as their bit patterns do, so the minimum is a 64-bit unsigned atomicMin; the caller passes
+// only d2 < 1000.0 (the entries' initial value), so neither a NaN nor a negative zero's sign bit ever gets in
+struct DepthEmit {
+  unsigned long long* dmin;
+  unsigned long long bits;
+  __device__ __forceinline__ void operator()(const KdPoint& p, uint32_t, double) const { atomicMin(&dmin[p.orig], bits); }
+};
+
+// marking, method 1: item i is model point i % P under frame i / P
+template <int BLOCK>
+__device__ __forceinline__ void collide_sphere_item(const QueryArgs& a, const size_t i, LaneStackQ<BLOCK, Q_SD>& st)
+{
+  const size_t f = i / a.P, m = i - f * a.P;
+  double px, py, pz;
+  transform3(a.frames + 16 * f, a.x[m], a.y[m], a.z[m], px, py, pz);
+  MarkEmit emit{a.mask};
+  st.sp = 0;
+  range_walk<BLOCK>(a, px, py, pz, a.r2, st, emit);
+}
+
+// marking, method 2: item i is the segment model point i % P sweeps from frame i / P to the next one (the reference carries
+// point2 over as the next point1: the same value as transforming afresh).  Two identical frames give p == p0 and nothing
+template <int BLOCK>
+__device__ __forceinline__ void collide_segment_item(const QueryArgs& a, const size_t i, LaneStackQ<BLOCK, Q_SD>& st)
+{
+  const size_t f = i / a.P, m = i - f * a.P;
+  const double x = a.x[m], y = a.y[m], z = a.z[m];
+  double px, py, pz, ex, ey, ez;
+  transform3(a.frames + 16 * f, x, y, z, px, py, pz);
+  transform3(a.frames + 16 * (f + 1), x, y, z, ex, ey, ez);
+  MarkEmit emit{a.mask};
+  st.sp = 0;
+  shape_walk<SHAPE_SEGMENT, BLOCK>(a, px, py, pz, ex, ey, ez, st, emit);
+}
+
+// depth along the model's axis: item i is model point i % P under frame i / P; the tree holds the colliding points only.
+// dist2 = Dist2(point1, pa[c1]) is the walk's closest_d2: the last newdist2 it took, Dist2(p, point) of that very point
+template <int BLOCK>
+__device__ __forceinline__ void collide_depth_axis_item(const QueryArgs& a, const size_t i, LaneStackQ<BLOCK, Q_SD>& st)
+{
+  const size_t f = i / a.P, m = i - f * a.P;
+  const double* T = a.frames + 16 * f;
+  const double y = a.y[m];
+  double px, py, pz, ex, ey, ez;
+  transform3(T, a.x[m], y, a.z[m], px, py, pz);
+  transform3(T, 0.0, y, 0.0, ex, ey, ez);
+  Segment sg;
+  sg.init(px, py, pz, ex, ey, ez);
+  const double b0 = __dsqrt_rn(sg.len2) + __dsqrt_rn(a.r2);
+  double best = b0 * b0;
+  uint32_t bslot = 0xFFFFFFFFu;
+  st.sp = 0;
+  segment_nearest_walk<BLOCK>(a, sg, st, best, bslot);
+  if (bslot == 0xFFFFFFFFu) return;       // found nothing
+  if (!(best < 1000.0)) return;           // no entry is above its initial 1000: the reference's comparison is never true
+  const KdPoint c1 = a.pts[bslot];
+  DepthEmit emit{a.dmin, (unsigned long long)__double_as_longlong(best)};
+  st.sp = 0;
+  range_walk<BLOCK>(a, c1.x, c1.y, c1.z, a.r2, st, emit);
+}
+
+// the last step of the depth: the minimum as the float the reference stored, and its root in float
+__device__ __forceinline__ float collide_depth_value(const unsigned long long bits)
+{
+  const float d2 = (float)__longlong_as_double((long long)bits);
+  return (float)__dsqrt_rn((double)d2);      // == sqrtf(d2): 53 bits are more than twice 24 plus two
+}
+
+template <int METHOD>
+__global__ void __launch_bounds__(Q_BLOCK) k_collide_mark(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  LaneStackQ<Q_BLOCK, Q_SD> st;
+  stack_init<Q_BLOCK>(st, s_stack, a);
+  const size_t T = (size_t)gridDim.x * Q_BLOCK;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+    if (METHOD == 1) collide_sphere_item<Q_BLOCK>(a, i, st);
+    else collide_segment_item<Q_BLOCK>(a, i, st);
+  }
+}
+
+__global__ void __launch_bounds__(Q_BLOCK) k_collide_depth_axis(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  LaneStackQ<Q_BLOCK, Q_SD> st;
+  stack_init<Q_BLOCK>(st, s_stack, a);
+  const size_t T = (size_t)gridDim.x * Q_BLOCK;
+  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) collide_depth_axis_item<Q_BLOCK>(a, i, st);
+}
+
+// num_colliding: the set bytes of the mask, one atomic per wave
+__global__ void __launch_bounds__(256) k_collide_count(const uint8_t* __restrict__ mask, const size_t M,
+                                                       unsigned long long* __restrict__ count)
+{
+  unsigned long long c = 0;
+  const size_t T = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += T) c += mask[i] ? 1u : 0u;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += (unsigned long long)__shfl_xor((long long)c, off, 64);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
+}
+
+__global__ void __launch_bounds__(256) k_collide_depth_init(unsigned long long* __restrict__ dmin, const size_t M)
+{
+  const size_t T = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += T)
+    dmin[i] = (unsigned long long)__double_as_longlong(1000.0);
+}
+
+__global__ void __launch_bounds__(256) k_collide_depth_finish(const unsigned long long* __restrict__ dmin, const size_t M,
+                                                              float* __restrict__ dist)
+{
+  const size_t T = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += T) dist[i] = collide_depth_value(dmin[i]);
+}
+
 // ---- launchers -------------------------------------------------------------------------------------------------
 static uint32_t q_grid(size_t n, int block)
 {
@@ -1141,6 +1292,44 @@ hipError_t launch_shape_fill(const QueryArgs& a, int mode, hipStream_t s)
 hipError_t launch_segment_nearest(const QueryArgs& a, hipStream_t s)
 {
   hipLaunchKernelGGL(k_segment_nearest, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_collide_mark(const QueryArgs& a, int cmethod, hipStream_t s)
+{
+  if (!a.n) return hipSuccess;
+  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
+  if (cmethod == 1) hipLaunchKernelGGL(k_collide_mark<1>, g, b, 0, s, a);
+  else if (cmethod == 2) hipLaunchKernelGGL(k_collide_mark<2>, g, b, 0, s, a);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+hipError_t launch_collide_depth_axis(const QueryArgs& a, hipStream_t s)
+{
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_collide_depth_axis, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_collide_count(const uint8_t* mask, size_t M, unsigned long long* count, hipStream_t s)
+{
+  if (!M) return hipSuccess;
+  hipLaunchKernelGGL(k_collide_count, dim3(q_grid(M, 256)), dim3(256), 0, s, mask, M, count);
+  return hipGetLastError();
+}
+
+hipError_t launch_collide_depth_init(unsigned long long* dmin, size_t M, hipStream_t s)
+{
+  if (!M) return hipSuccess;
+  hipLaunchKernelGGL(k_collide_depth_init, dim3(q_grid(M, 256)), dim3(256), 0, s, dmin, M);
+  return hipGetLastError();
+}
+
+hipError_t launch_collide_depth_finish(const unsigned long long* dmin, size_t M, float* dist, hipStream_t s)
+{
+  if (!M) return hipSuccess;
+  hipLaunchKernelGGL(k_collide_depth_finish, dim3(q_grid(M, 256)), dim3(256), 0, s, dmin, M, dist);
   return hipGetLastError();
 }
 

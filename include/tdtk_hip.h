@@ -215,6 +215,33 @@ int tdtk_segment_search_all(const tdtk_tree* t, const double* p, const double* p
  * its squared distance to p or -1.0. */
 int tdtk_segment_search_nearest(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
                                 int32_t* idx, double* d2);
+/* collision_model's handle_pointcloud (collision_model.cc:312-430): the point model [P][3] moves through the tree's cloud
+ * along the trajectory frames [F][16] (column-major, as read_trajectory leaves them); colliding [M] (the tree's input
+ * order) gets 1 for every point the model touches and 0 elsewhere, num_colliding their number.  cmethod 1 (CTYPE1,
+ * :338-367): the points of fixedRangeSearch(transform3(T_j, m), radius^2) for every frame j and model point m; cmethod 2
+ * (CTYPE2, :368-410): the points of segmentSearch_all(transform3(T_j, m), transform3(T_j+1, m), radius^2) for every pair
+ * of consecutive frames -- two identical frames give a segment of length zero, which lists nothing.  The queries are
+ * generated on the device; nothing of size F x P is stored.  F == 0 with cmethod 1 and F == 1 with cmethod 2 mark nothing;
+ * non-finite model or frame entries are not errors (their queries list what the reference's walks list: nothing).
+ * TDTK_EINVAL, before anything is launched or written: a NULL, P == 0, radius non-finite or <= 0, cmethod not 1 or 2,
+ * cmethod 2 with F == 0 (the reference dereferences an empty vector). */
+int tdtk_collision_mark(const tdtk_tree* env, const double* model, size_t P, const double* frames, size_t F, double radius,
+                        int cmethod, uint8_t* colliding, uint64_t* num_colliding);
+/* calculate_collidingdist (collision_model.cc:637-712): a KDtreeIndexed(bucket) over the non-colliding points of env_xyz
+ * [M][3] in ascending index, and for every colliding point, in ascending index, dist = (float)sqrt(Dist2(point, nearest))
+ * of FindClosest(point, 1000000).  dist [number of set bytes of colliding].  A colliding point with no non-colliding
+ * point within maxdist2 (the reference indexes out of bounds there) keeps 1000.0f; n_unreached (nullable): how many.
+ * TDTK_EINVAL: a NULL, no colliding point, no non-colliding point (the reference's tree constructor throws), bucket < 1. */
+int tdtk_collision_depth_closest(const double* env_xyz, size_t M, const uint8_t* colliding, int bucket, int device,
+                                 float* dist, uint64_t* n_unreached);
+/* calculate_collidingdist2 (collision_model.cc:714-800): a KDtreeIndexed(bucket) over the colliding points in ascending
+ * index; for every frame and model point (x, y, z): p1 = transform3(T, (x, y, z)), p2 = transform3(T, (0, y, 0)), c1 =
+ * segmentSearch_1NearestPoint(p1, p2, radius^2), and every point of fixedRangeSearch(c1, radius^2) takes the minimum of
+ * Dist2(p1, c1).  dist [number of set bytes of colliding], by compact index: (float)sqrt of the float the reference
+ * keeps, sqrtf(1000.0f) where no query reached the point.  The minimum does not depend on the order of the updates, so the
+ * result is the reference's at any number of threads.  TDTK_EINVAL as tdtk_collision_mark, and with no colliding point. */
+int tdtk_collision_depth_axis(const double* env_xyz, size_t M, const uint8_t* colliding, const double* model, size_t P,
+                              const double* frames, size_t F, double radius, int bucket, int device, float* dist);
 /* calculateNormalsKNN (normals.cc:442-516; calculateNormal :518-558): a KDtree(points, bucket) and, for every point, its
  * k nearest neighbours (itself included), their mean and covariance, the eigenvector of the smallest eigenvalue
  * (newmat EigenValues), oriented so that n . (p - rPos) >= 0, normalised.  normals_out [n][3] in point order (the

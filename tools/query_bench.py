@@ -20,8 +20,15 @@ the reference library's searches and newmat's EigenValues, the glue in Python an
 about 20.6 neighbours): the walk and the normals over its lists, next to the k-NN walk / normals at the same k and the
 fixed-radius walk / normals at the same radius in the same run, and the mean list length; --only-hybrid runs nothing else.
 
+--collision adds collision detection along a trajectory: a 1M-point environment (density 1 per unit volume), a model of
+10,000 points in a box of 40 x 16 x 16, 300 frames along a curve through the cloud, radius 1 -- 3M (frame, point) items.
+Marking with both methods on the resident tree, and both depth calls end to end (host compaction and the tree over the
+sub-cloud included); next to them collision_model's loops over the reference library (tools/ref_query_loop.cc) on
+--ref-threads threads, whole, where oracle/_ref exists; --only-collision runs nothing else.
+
 Kernel times: run the same command under `rocprofv3 --kernel-trace --stats` (k_knn_reg, k_range_count / k_range_fill,
-k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest, k_knn_adaptive_reg / k_knn_adaptive_lds, k_ann_adaptive, k_knnr_reg / k_knnr_lds)."""
+k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest, k_knn_adaptive_reg / k_knn_adaptive_lds, k_ann_adaptive, k_knnr_reg / k_knnr_lds,
+k_collide_mark, k_collide_depth_axis)."""
 import argparse
 import importlib
 import json
@@ -207,6 +214,69 @@ def hybrid_legs(tdtk, pts, tag, reps):
     return out
 
 
+def collision_legs(tdtk, reps, threads):
+    """handle_pointcloud (both methods), calculate_collidingdist and calculate_collidingdist2 on the device, and the same
+    loops over the reference library"""
+    import ctypes as C
+    spec = importlib.util.spec_from_file_location("make_golden_collision",
+                                                  os.path.join(ROOT, "tests", "golden", "make_golden_collision.py"))
+    mg = importlib.util.module_from_spec(spec); spec.loader.exec_module(mg)
+    rng = np.random.default_rng(2031)
+    env = rng.uniform(-50, 50, (1_000_000, 3))
+    model = rng.uniform(-1.0, 1.0, (10_000, 3)) * np.array([20.0, 8.0, 8.0])
+    frames = mg.curve(300, (-35, -30, -32), (34, 31, 30), 8.0)
+    radius = 1.0
+    out = {"collision_items": len(model) * len(frames)}
+    kd = tdtk.KDtree(env, 20)
+    masks = {}
+    for cm in (1, 2):
+        out["collision_mark_m%d_1M" % cm] = timed(lambda: tdtk.handle_pointcloud(model, kd, frames, radius, cm), reps)
+        masks[cm], out["collision_mark_m%d_1M_num" % cm] = tdtk.handle_pointcloud(model, kd, frames, radius, cm)
+    mask = masks[1]
+    out["collision_depth_closest_1M"] = timed(lambda: tdtk.calculate_collidingdist(env, mask), reps)
+    out["collision_depth_axis_1M"] = timed(lambda: tdtk.calculate_collidingdist2(model, env, frames, mask, radius), reps)
+    d1 = tdtk.calculate_collidingdist(env, mask)
+    d2 = tdtk.calculate_collidingdist2(model, env, frames, mask, radius)
+    from oracle import orc
+    if not orc.have_ref():
+        return out
+    Lq = _ref_loop_lib()
+    dp = C.c_void_p
+    Lq.ref_collision_mark_loop.restype = C.c_double
+    Lq.ref_collision_mark_loop.argtypes = [dp, dp, dp, dp, C.c_size_t, dp, C.c_size_t, C.c_double, C.c_int, C.c_int, dp]
+    Lq.ref_collision_depth_axis_loop.restype = C.c_double
+    Lq.ref_collision_depth_axis_loop.argtypes = [dp, dp, dp, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_size_t, C.c_double,
+                                                 C.c_int, dp]
+    label = "ref_host_%dthreads" % threads
+    t = mg.ColRef(env, 20)
+    fn = {k: C.cast(f, C.c_void_p) for k, f in (("range", t.c_range), ("segall", t.c_segall), ("near", t.c_near))}
+    model_c, frames_c = np.ascontiguousarray(model), np.ascontiguousarray(frames)
+    for cm in (1, 2):
+        m8 = np.zeros(len(env), np.uint8)
+        ms = Lq.ref_collision_mark_loop(fn["range"], fn["segall"], t.kdi, model_c.ctypes.data, len(model), frames_c.ctypes.data,
+                                        len(frames), radius * radius, cm, threads, m8.ctypes.data)
+        out["%s_collision_mark_m%d_1M_ms" % (label, cm)] = round(ms, 1)
+        out["collision_mark_m%d_1M_equal" % cm] = bool(np.array_equal(m8.astype(bool), masks[cm]))
+    hit, rest = np.ascontiguousarray(env[mask]), np.ascontiguousarray(env[~mask])
+    t0 = time.perf_counter()
+    tr = mg.ColRef(rest, 20)
+    idx = np.empty(len(hit), np.int32)
+    tr.R.ref_kdi_find_closest(tr.h, hit.ctypes.data_as(C.POINTER(C.c_double)), len(hit), mg.MAXDIST2,
+                              idx.ctypes.data_as(C.POINTER(C.c_int32)), threads)
+    r1 = np.sqrt(mg._dist2(hit, rest[idx])).astype(np.float32)
+    out["%s_collision_depth_closest_1M_ms" % label] = round((time.perf_counter() - t0) * 1e3, 1)
+    out["collision_depth_closest_1M_equal"] = bool(np.array_equal(r1, d1))
+    t0 = time.perf_counter()
+    th = mg.ColRef(hit, 20)
+    fh = {k: C.cast(f, C.c_void_p) for k, f in (("range", th.c_range), ("near", th.c_near))}
+    r2 = np.empty(len(hit), np.float32)
+    Lq.ref_collision_depth_axis_loop(fh["near"], fh["range"], th.kdi, th.pts.ctypes.data, len(hit), model_c.ctypes.data,
+                                     len(model), frames_c.ctypes.data, len(frames), radius * radius, threads, r2.ctypes.data)
+    out["%s_collision_depth_axis_1M_ms" % label] = round((time.perf_counter() - t0) * 1e3, 1)
+    out["collision_depth_axis_1M_equal"] = bool(np.array_equal(r2, d2))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000000,10000000")
@@ -219,6 +289,8 @@ def main():
     ap.add_argument("--only-adaptive", action="store_true", help="those legs alone")
     ap.add_argument("--hybrid", action="store_true", help="add the k-nearest-within-radius legs (1M points)")
     ap.add_argument("--only-hybrid", action="store_true", help="those legs alone")
+    ap.add_argument("--collision", action="store_true", help="add the collision-detection legs (1M points, 3M items)")
+    ap.add_argument("--only-collision", action="store_true", help="those legs alone")
     args = ap.parse_args()
     tdtk = importlib.import_module("3dtk_amd")
     if tdtk.device_count() < 1:
@@ -243,6 +315,11 @@ def main():
         pts = np.random.default_rng(2029).uniform(-50, 50, (1_000_000, 3))
         out.update(hybrid_legs(tdtk, pts, "1M", args.reps))
         if args.only_hybrid:
+            print(json.dumps(out))
+            return
+    if args.collision or args.only_collision:
+        out.update(collision_legs(tdtk, args.reps, args.ref_threads))
+        if args.only_collision:
             print(json.dumps(out))
             return
     for M in [int(s) for s in args.sizes.split(",")]:
