@@ -1458,6 +1458,66 @@ static int normals_tree(Ctx* c, const double* xyz, size_t n, int bucket, int dev
   return tree_finish(c, t.get(), n);
 }
 
+// the K queries at q [K][3] uploaded to WS_TMPA -- with v, their second vectors [K][3] side by side behind them -- and
+// query_prepare over them
+static int query_begin(Ctx* c, const tdtk_tree* t, const double* q, const double* v, size_t K, QueryArgs& a)
+{
+  int rc;
+  if ((rc = c->ws[WS_TMPA].ensure((v ? 6 : 3) * K * sizeof(double)))) return rc;
+  double* dq = c->ws[WS_TMPA].as<double>();
+  double* dv = v ? dq + 3 * K : nullptr;
+  HIPCHK(hipMemcpyAsync(dq, q, 3 * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (v) HIPCHK(hipMemcpyAsync(dv, v, 3 * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  return query_prepare(c, t, dq, K, a, dv);
+}
+
+// The list queries -- the fixed radius (mode < 0; d2 nullable) and the four shape walks of query.hip (mode: ShapeMode, v
+// their second vector) -- in two walks: the count walk into WS_KPOS, the scan into WS_D2 (WS_ARENA its scratch), the offsets
+// to the host, and, where the caller's capacity holds the total, the fill walk into WS_IDX (and WS_TMPB for d2).
+// `noun`: what the capacity error counts
+static int list_query(const char* name, const char* noun, int mode, const tdtk_tree* t, const double* q, const double* v,
+                      size_t K, double r2, uint64_t* offsets, int32_t* idx, double* d2, size_t cap, uint64_t* total)
+{
+  Ctx* c;
+  int rc;
+  if ((rc = get_ctx(t->device, &c))) return rc;
+  offsets[0] = 0; *total = 0;
+  if (K == 0) return TDTK_OK;
+  hipStream_t s = c->stream;
+  const size_t tmpb = range_scan_temp_bytes(K);
+  QueryArgs a;
+  if ((rc = query_begin(c, t, q, v, K, a))) return rc;
+  if ((rc = c->ws[WS_KPOS].ensure((K + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = c->ws[WS_D2].ensure((K + 1) * sizeof(unsigned long long)))) return rc;
+  if ((rc = c->ws[WS_ARENA].ensure(tmpb + 256))) return rc;
+  a.r2 = r2;
+  a.counts = c->ws[WS_KPOS].as<uint32_t>();
+  unsigned long long* d_off = c->ws[WS_D2].as<unsigned long long>();
+  HIPCHK(hipMemsetAsync(a.counts + K, 0, sizeof(uint32_t), s));
+  HIPCHK(mode < 0 ? launch_range_count(a, s) : launch_shape_count(a, mode, s));
+  HIPCHK(launch_range_scan(a.counts, d_off, K, c->ws[WS_ARENA].p, tmpb, s));
+  HIPCHK(hipMemcpyAsync(offsets, d_off, (K + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const uint64_t tot = offsets[K];
+  *total = tot;
+  if (cap < tot) {
+    set_error(std::string(name) + ": " + std::to_string(tot) + " " + noun + ", capacity " + std::to_string(cap) + " (offsets and total are filled)");
+    return TDTK_EINVAL;
+  }
+  if (tot == 0) return TDTK_OK;
+  if (!idx) { set_error("idx is NULL"); return TDTK_EINVAL; }
+  if ((rc = c->ws[WS_IDX].ensure(tot * sizeof(int32_t)))) return rc;
+  if (d2 && (rc = c->ws[WS_TMPB].ensure(tot * sizeof(double)))) return rc;
+  a.offsets = d_off;
+  a.idx = c->ws[WS_IDX].as<int32_t>();
+  a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
+  HIPCHK(mode < 0 ? launch_range_fill(a, s) : launch_shape_fill(a, mode, s));
+  HIPCHK(hipMemcpyAsync(idx, a.idx, tot * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, tot * sizeof(double), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return TDTK_OK;
+}
+
 extern "C" {
 
 int tdtk_knn_search(const tdtk_tree* t, const double* q, size_t K, int k, int32_t* idx, double* d2)
@@ -1469,12 +1529,10 @@ int tdtk_knn_search(const tdtk_tree* t, const double* q, size_t K, int k, int32_
   if ((rc = get_ctx(t->device, &c))) return rc;
   if (K == 0) return TDTK_OK;
   const size_t L = K * (size_t)k;
-  if ((rc = c->ws[WS_TMPA].ensure(3 * K * sizeof(double)))) return rc;
+  QueryArgs a;
+  if ((rc = query_begin(c, t, q, nullptr, K, a))) return rc;
   if ((rc = c->ws[WS_IDX].ensure(L * sizeof(int32_t)))) return rc;
   if (d2 && (rc = c->ws[WS_TMPB].ensure(L * sizeof(double)))) return rc;
-  HIPCHK(hipMemcpyAsync(c->ws[WS_TMPA].p, q, 3 * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  QueryArgs a;
-  if ((rc = query_prepare(c, t, c->ws[WS_TMPA].as<double>(), K, a))) return rc;
   a.k = k;
   a.idx = c->ws[WS_IDX].as<int32_t>();
   a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
@@ -1502,12 +1560,10 @@ int tdtk_knn_range_search(const tdtk_tree* t, const double* q, size_t K, int k, 
     if (counts) std::fill(counts, counts + K, 0);
     return TDTK_OK;
   }
-  if ((rc = c->ws[WS_TMPA].ensure(3 * K * sizeof(double)))) return rc;
+  QueryArgs a;
+  if ((rc = query_begin(c, t, q, nullptr, K, a))) return rc;
   if ((rc = c->ws[WS_IDX].ensure((L + K) * sizeof(int32_t)))) return rc;       // WS_IDX: the lists | counts
   if (d2 && (rc = c->ws[WS_TMPB].ensure(L * sizeof(double)))) return rc;
-  HIPCHK(hipMemcpyAsync(c->ws[WS_TMPA].p, q, 3 * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  QueryArgs a;
-  if ((rc = query_prepare(c, t, c->ws[WS_TMPA].as<double>(), K, a))) return rc;
   a.k = k;
   a.r2 = sqRad2;
   a.idx = c->ws[WS_IDX].as<int32_t>();
@@ -1525,111 +1581,21 @@ int tdtk_fixed_range_search(const tdtk_tree* t, const double* q, size_t K, doubl
                             double* d2, size_t cap, uint64_t* total)
 {
   if (!t || (!q && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
-  Ctx* c;
-  int rc;
-  if ((rc = get_ctx(t->device, &c))) return rc;
-  offsets[0] = 0; *total = 0;
-  if (K == 0) return TDTK_OK;
-  hipStream_t s = c->stream;
-  const size_t tmpb = range_scan_temp_bytes(K);
-  if ((rc = c->ws[WS_TMPA].ensure(3 * K * sizeof(double)))) return rc;
-  if ((rc = c->ws[WS_KPOS].ensure((K + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = c->ws[WS_D2].ensure((K + 1) * sizeof(unsigned long long)))) return rc;
-  if ((rc = c->ws[WS_ARENA].ensure(tmpb + 256))) return rc;
-  HIPCHK(hipMemcpyAsync(c->ws[WS_TMPA].p, q, 3 * K * sizeof(double), hipMemcpyHostToDevice, s));
-  QueryArgs a;
-  if ((rc = query_prepare(c, t, c->ws[WS_TMPA].as<double>(), K, a))) return rc;
-  a.r2 = sqRad2;
-  a.counts = c->ws[WS_KPOS].as<uint32_t>();
-  unsigned long long* d_off = c->ws[WS_D2].as<unsigned long long>();
-  HIPCHK(hipMemsetAsync(a.counts + K, 0, sizeof(uint32_t), s));
-  HIPCHK(launch_range_count(a, s));
-  HIPCHK(launch_range_scan(a.counts, d_off, K, c->ws[WS_ARENA].p, tmpb, s));
-  HIPCHK(hipMemcpyAsync(offsets, d_off, (K + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const uint64_t tot = offsets[K];
-  *total = tot;
-  if (cap < tot) {
-    set_error("fixedRangeSearch: " + std::to_string(tot) + " neighbours, capacity " + std::to_string(cap) + " (offsets and total are filled)");
-    return TDTK_EINVAL;
-  }
-  if (tot == 0) return TDTK_OK;
-  if (!idx) { set_error("idx is NULL"); return TDTK_EINVAL; }
-  if ((rc = c->ws[WS_IDX].ensure(tot * sizeof(int32_t)))) return rc;
-  if (d2 && (rc = c->ws[WS_TMPB].ensure(tot * sizeof(double)))) return rc;
-  a.offsets = d_off;
-  a.idx = c->ws[WS_IDX].as<int32_t>();
-  a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
-  HIPCHK(launch_range_fill(a, s));
-  HIPCHK(hipMemcpyAsync(idx, a.idx, tot * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, tot * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return TDTK_OK;
+  return list_query("fixedRangeSearch", "neighbours", -1, t, q, nullptr, K, sqRad2, offsets, idx, d2, cap, total);
 }
-
-}  // extern "C"
-
-// the four list queries of query.hip's shape walks: tdtk_fixed_range_search's contract and workspaces (WS_KPOS the counts,
-// WS_D2 the offsets, WS_ARENA the scan's, WS_IDX the lists), the queries and their second vectors side by side in WS_TMPA
-static int shape_list_query(const char* name, int mode, const tdtk_tree* t, const double* p, const double* v, size_t K,
-                            double maxdist2, uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total)
-{
-  Ctx* c;
-  int rc;
-  if ((rc = get_ctx(t->device, &c))) return rc;
-  offsets[0] = 0; *total = 0;
-  if (K == 0) return TDTK_OK;
-  hipStream_t s = c->stream;
-  const size_t tmpb = range_scan_temp_bytes(K);
-  if ((rc = c->ws[WS_TMPA].ensure(6 * K * sizeof(double)))) return rc;
-  if ((rc = c->ws[WS_KPOS].ensure((K + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = c->ws[WS_D2].ensure((K + 1) * sizeof(unsigned long long)))) return rc;
-  if ((rc = c->ws[WS_ARENA].ensure(tmpb + 256))) return rc;
-  double* dp = c->ws[WS_TMPA].as<double>();
-  double* dv = dp + 3 * K;
-  HIPCHK(hipMemcpyAsync(dp, p, 3 * K * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(dv, v, 3 * K * sizeof(double), hipMemcpyHostToDevice, s));
-  QueryArgs a;
-  if ((rc = query_prepare(c, t, dp, K, a, dv))) return rc;
-  a.r2 = maxdist2;
-  a.counts = c->ws[WS_KPOS].as<uint32_t>();
-  unsigned long long* d_off = c->ws[WS_D2].as<unsigned long long>();
-  HIPCHK(hipMemsetAsync(a.counts + K, 0, sizeof(uint32_t), s));
-  HIPCHK(launch_shape_count(a, mode, s));
-  HIPCHK(launch_range_scan(a.counts, d_off, K, c->ws[WS_ARENA].p, tmpb, s));
-  HIPCHK(hipMemcpyAsync(offsets, d_off, (K + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const uint64_t tot = offsets[K];
-  *total = tot;
-  if (cap < tot) {
-    set_error(std::string(name) + ": " + std::to_string(tot) + " points, capacity " + std::to_string(cap) + " (offsets and total are filled)");
-    return TDTK_EINVAL;
-  }
-  if (tot == 0) return TDTK_OK;
-  if (!idx) { set_error("idx is NULL"); return TDTK_EINVAL; }
-  if ((rc = c->ws[WS_IDX].ensure(tot * sizeof(int32_t)))) return rc;
-  a.offsets = d_off;
-  a.idx = c->ws[WS_IDX].as<int32_t>();
-  HIPCHK(launch_shape_fill(a, mode, s));
-  HIPCHK(hipMemcpyAsync(idx, a.idx, tot * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return TDTK_OK;
-}
-
-extern "C" {
 
 int tdtk_fixed_range_search_along_dir(const tdtk_tree* t, const double* p, const double* dir, size_t K, double maxdist2,
                                       uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total)
 {
   if (!t || ((!p || !dir) && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
-  return shape_list_query("fixedRangeSearchAlongDir", SHAPE_ALONG_DIR, t, p, dir, K, maxdist2, offsets, idx, cap, total);
+  return list_query("fixedRangeSearchAlongDir", "points", SHAPE_ALONG_DIR, t, p, dir, K, maxdist2, offsets, idx, nullptr, cap, total);
 }
 
 int tdtk_fixed_range_search_between(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
                                     uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total)
 {
   if (!t || ((!p || !p0) && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
-  return shape_list_query("fixedRangeSearchBetween2Points", SHAPE_BETWEEN, t, p, p0, K, maxdist2, offsets, idx, cap, total);
+  return list_query("fixedRangeSearchBetween2Points", "points", SHAPE_BETWEEN, t, p, p0, K, maxdist2, offsets, idx, nullptr, cap, total);
 }
 
 int tdtk_aabb_search(const tdtk_tree* t, const double* lo, const double* hi, size_t K, uint64_t* offsets, int32_t* idx,
@@ -1639,14 +1605,14 @@ int tdtk_aabb_search(const tdtk_tree* t, const double* lo, const double* hi, siz
   // kdIndexed.cc:237-238, the comparison in the reference's sense (a NaN corner passes it); nothing is written or launched
   for (size_t i = 0; i < 3 * K; i++)
     if (lo[i] > hi[i]) { set_error("invalid bbox"); return TDTK_EINVAL; }
-  return shape_list_query("AABBSearch", SHAPE_AABB, t, lo, hi, K, 0.0, offsets, idx, cap, total);
+  return list_query("AABBSearch", "points", SHAPE_AABB, t, lo, hi, K, 0.0, offsets, idx, nullptr, cap, total);
 }
 
 int tdtk_segment_search_all(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
                             uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total)
 {
   if (!t || ((!p || !p0) && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
-  return shape_list_query("segmentSearch_all", SHAPE_SEGMENT, t, p, p0, K, maxdist2, offsets, idx, cap, total);
+  return list_query("segmentSearch_all", "points", SHAPE_SEGMENT, t, p, p0, K, maxdist2, offsets, idx, nullptr, cap, total);
 }
 
 int tdtk_segment_search_nearest(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
@@ -1658,15 +1624,10 @@ int tdtk_segment_search_nearest(const tdtk_tree* t, const double* p, const doubl
   if ((rc = get_ctx(t->device, &c))) return rc;
   if (K == 0) return TDTK_OK;
   hipStream_t s = c->stream;
-  if ((rc = c->ws[WS_TMPA].ensure(6 * K * sizeof(double)))) return rc;
+  QueryArgs a;
+  if ((rc = query_begin(c, t, p, p0, K, a))) return rc;
   if ((rc = c->ws[WS_IDX].ensure(K * sizeof(int32_t)))) return rc;
   if (d2 && (rc = c->ws[WS_TMPB].ensure(K * sizeof(double)))) return rc;
-  double* dp = c->ws[WS_TMPA].as<double>();
-  double* dv = dp + 3 * K;
-  HIPCHK(hipMemcpyAsync(dp, p, 3 * K * sizeof(double), hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(dv, p0, 3 * K * sizeof(double), hipMemcpyHostToDevice, s));
-  QueryArgs a;
-  if ((rc = query_prepare(c, t, dp, K, a, dv))) return rc;
   a.r2 = maxdist2;
   a.idx = c->ws[WS_IDX].as<int32_t>();
   a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
@@ -1829,6 +1790,43 @@ int tdtk_collision_depth_axis(const double* env_xyz, size_t M, const uint8_t* co
 
 }  // extern "C"
 
+// The four tree-based normal estimators between their argument checks and their launch, and after it.  Begin: the context,
+// the tree over xyz (the points stay in WS_TMPA and are the queries), WS_TMPB for the normals, WS_IDX for `ints` int32 of
+// lists and per-point values (0: none), query_prepare, the scanner position.  Finish: the normals, the lists (a.knn_out, L
+// int32) and one int32 per point from d_per_point to the host, each where the caller gave an array; then the synchronise
+struct NormalsRun {
+  Ctx* c;
+  std::unique_ptr<tdtk_tree> t;
+  QueryArgs a;
+  int32_t* ints;
+};
+
+static int normals_begin(NormalsRun& r, const double* xyz, size_t n, int bucket, int device, const double rPos[3], size_t ints)
+{
+  int rc;
+  if ((rc = get_ctx(device, &r.c))) return rc;
+  Ctx* c = r.c;
+  if ((rc = normals_tree(c, xyz, n, bucket, device, r.t))) return rc;
+  if ((rc = c->ws[WS_TMPB].ensure(3 * n * sizeof(double)))) return rc;
+  if (ints && (rc = c->ws[WS_IDX].ensure(ints * sizeof(int32_t)))) return rc;
+  if ((rc = query_prepare(c, r.t.get(), c->ws[WS_TMPA].as<double>(), n, r.a))) return rc;
+  r.a.rx = rPos[0]; r.a.ry = rPos[1]; r.a.rz = rPos[2];
+  r.a.normals = c->ws[WS_TMPB].as<double>();
+  r.ints = ints ? c->ws[WS_IDX].as<int32_t>() : nullptr;
+  return TDTK_OK;
+}
+
+static int normals_finish(NormalsRun& r, size_t n, double* normals_out, int32_t* lists_out, size_t L, int32_t* per_point_out,
+                          const int32_t* d_per_point)
+{
+  hipStream_t s = r.c->stream;
+  HIPCHK(hipMemcpyAsync(normals_out, r.a.normals, 3 * n * sizeof(double), hipMemcpyDeviceToHost, s));
+  if (lists_out) HIPCHK(hipMemcpyAsync(lists_out, r.a.knn_out, L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  if (per_point_out) HIPCHK(hipMemcpyAsync(per_point_out, d_per_point, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return TDTK_OK;
+}
+
 extern "C" {
 
 int tdtk_normals_knn(const double* xyz, size_t n, int k, const double rPos[3], int bucket, int device, double* normals_out,
@@ -1839,24 +1837,13 @@ int tdtk_normals_knn(const double* xyz, size_t n, int k, const double rPos[3], i
   if (!normals_out) { set_error("NULL argument"); return TDTK_EINVAL; }
   int rc;
   if ((rc = knn_check_k(k))) return rc;
-  Ctx* c;
-  if ((rc = get_ctx(device, &c))) return rc;
-  std::unique_ptr<tdtk_tree> t;
-  if ((rc = normals_tree(c, xyz, n, bucket, device, t))) return rc;
-  const size_t L = n * (size_t)k;
-  if ((rc = c->ws[WS_TMPB].ensure(3 * n * sizeof(double)))) return rc;
-  if (knn_out && (rc = c->ws[WS_IDX].ensure(L * sizeof(int32_t)))) return rc;
-  QueryArgs a;
-  if ((rc = query_prepare(c, t.get(), c->ws[WS_TMPA].as<double>(), n, a))) return rc;
-  a.k = k;
-  a.rx = rPos[0]; a.ry = rPos[1]; a.rz = rPos[2];
-  a.normals = c->ws[WS_TMPB].as<double>();
-  a.knn_out = knn_out ? c->ws[WS_IDX].as<int32_t>() : nullptr;
-  HIPCHK(launch_knn(a, true, c->stream));
-  HIPCHK(hipMemcpyAsync(normals_out, a.normals, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (knn_out) HIPCHK(hipMemcpyAsync(knn_out, a.knn_out, L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return TDTK_OK;
+  const size_t L = knn_out ? n * (size_t)k : 0;
+  NormalsRun r;
+  if ((rc = normals_begin(r, xyz, n, bucket, device, rPos, L))) return rc;
+  r.a.k = k;
+  r.a.knn_out = knn_out ? r.ints : nullptr;
+  HIPCHK(launch_knn(r.a, true, r.c->stream));
+  return normals_finish(r, n, normals_out, knn_out, L, nullptr, nullptr);
 }
 
 int tdtk_normals_range(const double* xyz, size_t n, double sqRad2, const double rPos[3], int bucket, int device,
@@ -1867,20 +1854,11 @@ int tdtk_normals_range(const double* xyz, size_t n, double sqRad2, const double 
   if (!normals_out) { set_error("NULL argument"); return TDTK_EINVAL; }
   if (!(sqRad2 > 0)) { set_error("sqRad2 must be > 0 (an empty neighbourhood has no mean)"); return TDTK_EINVAL; }
   int rc;
-  Ctx* c;
-  if ((rc = get_ctx(device, &c))) return rc;
-  std::unique_ptr<tdtk_tree> t;
-  if ((rc = normals_tree(c, xyz, n, bucket, device, t))) return rc;
-  if ((rc = c->ws[WS_TMPB].ensure(3 * n * sizeof(double)))) return rc;
-  QueryArgs a;
-  if ((rc = query_prepare(c, t.get(), c->ws[WS_TMPA].as<double>(), n, a))) return rc;
-  a.r2 = sqRad2;
-  a.rx = rPos[0]; a.ry = rPos[1]; a.rz = rPos[2];
-  a.normals = c->ws[WS_TMPB].as<double>();
-  HIPCHK(launch_range_normals(a, c->stream));
-  HIPCHK(hipMemcpyAsync(normals_out, a.normals, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return TDTK_OK;
+  NormalsRun r;
+  if ((rc = normals_begin(r, xyz, n, bucket, device, rPos, 0))) return rc;
+  r.a.r2 = sqRad2;
+  HIPCHK(launch_range_normals(r.a, r.c->stream));
+  return normals_finish(r, n, normals_out, nullptr, 0, nullptr, nullptr);
 }
 
 int tdtk_normals_knn_range(const double* xyz, size_t n, int k, double sqRad2, const double rPos[3], int bucket, int device,
@@ -1895,27 +1873,15 @@ int tdtk_normals_knn_range(const double* xyz, size_t n, int k, double sqRad2, co
   if ((rc = knn_check_k(k))) return rc;
   if (!std::isfinite(sqRad2)) { set_error("sqRad2 must be finite"); return TDTK_EINVAL; }
   if (!(sqRad2 > 0)) { set_error("sqRad2 must be > 0 (an empty neighbourhood has no mean)"); return TDTK_EINVAL; }
-  Ctx* c;
-  if ((rc = get_ctx(device, &c))) return rc;
-  std::unique_ptr<tdtk_tree> t;
-  if ((rc = normals_tree(c, xyz, n, bucket, device, t))) return rc;
   const size_t L = knn_out ? n * (size_t)k : 0;       // WS_IDX: the lists | counts
-  if ((rc = c->ws[WS_TMPB].ensure(3 * n * sizeof(double)))) return rc;
-  if ((rc = c->ws[WS_IDX].ensure((L + n) * sizeof(int32_t)))) return rc;
-  QueryArgs a;
-  if ((rc = query_prepare(c, t.get(), c->ws[WS_TMPA].as<double>(), n, a))) return rc;
-  a.k = k;
-  a.r2 = sqRad2;
-  a.rx = rPos[0]; a.ry = rPos[1]; a.rz = rPos[2];
-  a.normals = c->ws[WS_TMPB].as<double>();
-  a.knn_out = knn_out ? c->ws[WS_IDX].as<int32_t>() : nullptr;
-  a.nr_out = counts_out ? c->ws[WS_IDX].as<int32_t>() + L : nullptr;
-  HIPCHK(launch_knn_range(a, true, c->stream));
-  HIPCHK(hipMemcpyAsync(normals_out, a.normals, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (knn_out) HIPCHK(hipMemcpyAsync(knn_out, a.knn_out, L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (counts_out) HIPCHK(hipMemcpyAsync(counts_out, a.nr_out, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return TDTK_OK;
+  NormalsRun r;
+  if ((rc = normals_begin(r, xyz, n, bucket, device, rPos, L + n))) return rc;
+  r.a.k = k;
+  r.a.r2 = sqRad2;
+  r.a.knn_out = knn_out ? r.ints : nullptr;
+  r.a.nr_out = counts_out ? r.ints + L : nullptr;
+  HIPCHK(launch_knn_range(r.a, true, r.c->stream));
+  return normals_finish(r, n, normals_out, knn_out, L, counts_out, r.a.nr_out);
 }
 
 // the argument checks the two adaptive-k estimators share (normals.cc:123-125, 569-571)
@@ -1939,26 +1905,14 @@ int tdtk_normals_adaptive_knn(const double* xyz, size_t n, int kmin, int kmax, c
     set_error("kmax + 1 = " + std::to_string((long long)kmax + 1) + " exceeds the supported list capacity of " + std::to_string(KNN_MAX_K));
     return TDTK_EUNSUP;
   }
-  Ctx* c;
-  if ((rc = get_ctx(device, &c))) return rc;
-  std::unique_ptr<tdtk_tree> t;
-  if ((rc = normals_tree(c, xyz, n, bucket, device, t))) return rc;
   const size_t L = knn_out ? n * (size_t)(kmax + 1) : 0;       // WS_IDX: the lists | k_used
-  if ((rc = c->ws[WS_TMPB].ensure(3 * n * sizeof(double)))) return rc;
-  if ((rc = c->ws[WS_IDX].ensure((L + n) * sizeof(int32_t)))) return rc;
-  QueryArgs a;
-  if ((rc = query_prepare(c, t.get(), c->ws[WS_TMPA].as<double>(), n, a))) return rc;
-  a.kmin = kmin; a.kmax = kmax;
-  a.rx = rPos[0]; a.ry = rPos[1]; a.rz = rPos[2];
-  a.normals = c->ws[WS_TMPB].as<double>();
-  a.knn_out = knn_out ? c->ws[WS_IDX].as<int32_t>() : nullptr;
-  a.k_used = k_used ? c->ws[WS_IDX].as<int32_t>() + L : nullptr;
-  HIPCHK(launch_knn_adaptive(a, c->stream));
-  HIPCHK(hipMemcpyAsync(normals_out, a.normals, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (k_used) HIPCHK(hipMemcpyAsync(k_used, a.k_used, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (knn_out) HIPCHK(hipMemcpyAsync(knn_out, a.knn_out, L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return TDTK_OK;
+  NormalsRun r;
+  if ((rc = normals_begin(r, xyz, n, bucket, device, rPos, L + n))) return rc;
+  r.a.kmin = kmin; r.a.kmax = kmax;
+  r.a.knn_out = knn_out ? r.ints : nullptr;
+  r.a.k_used = k_used ? r.ints + L : nullptr;
+  HIPCHK(launch_knn_adaptive(r.a, r.c->stream));
+  return normals_finish(r, n, normals_out, knn_out, L, k_used, r.a.k_used);
 }
 
 int tdtk_find_closest_along_dir(const tdtk_tree* t, const double* q, const double* dir, size_t K,

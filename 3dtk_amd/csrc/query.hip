@@ -3,97 +3,10 @@
 // _FixedRangeSearch (kdTreeImpl.h:585-625), _KNNRangeSearch (kdTreeImpl.h:684-745), calculateNormalsKNN / calculateNormalsRange with calculateNormal's PCA (normals.cc:369-439,
 // 442-516, 518-558), _fixedRangeSearchAlongDir / _fixedRangeSearchBetween2Points / _AABBSearch / _segmentSearch_all /
 // _segmentSearch_1NearestPoint (kdTreeImpl.h:432-577, 747-913); and collision_model's marking and axis depth fused over the
-// range and segment walks (collision_model.cc:312-430, 714-800; "collision detection along a trajectory" below).
+// range and segment walks (collision_model.cc:312-430, 714-800).
 //
-// Layout of every kernel here: one query per lane, the queries spatially binned first (launch_bin) so that the lanes of a
-// wave walk neighbouring parts of the tree, a grid-stride loop over the sorted queries, results written straight to the
-// caller's position (order[]).  The walk is a DFS with an explicit per-lane stack (LaneStackQ: LDS levels + an HBM overflow
-// column sized from the tree's depth); the node records are the fp64 KdNode ones, so every decision below is the reference's
-// own expression on the reference's own values -- no fp32 shortcut, nothing to prove under rounding.
-//
-// The two walks, rule by rule (each is easy to get subtly wrong):
-//
-// k-NN (_KNNSearch):
-//   * list of k slots (distance, point), distances start at -1 ("unset").  "full" = distances[k-1] != -1.
-//   * internal node, on entering it: ONLY when the list is full, the box check
-//       a = max(max(|p0-cx|-hx, |p1-cy|-hy), |p2-cz|-hz);  prune when a >= 0 && a*a >= distances[k-1]
-//     (a node entered while the list is not full is never pruned, however far away it is).
-//   * near child first when p[axis] < splitval -- a STRICT '<' (FindClosest and the range search use splitval - p >= 0,
-//     so on a split plane the two rules pick different sides).  The far child is never pruned by its plane: it is pushed
-//     unconditionally and meets only its own box check when it is popped (with the list as it is then).
-//   * a leaf has no box: it is scanned whenever it is reached, in bucket order, over its real count (padded group slots
-//     are never looked at).  Each point goes in before the first slot that is unset or holds a strictly larger distance;
-//     the last slot drops out.  Equal distances keep their visiting order, a point equal to the k-th distance of a full
-//     list is dropped.  Once the list is full, "kth <= d2" therefore means "no slot is larger": skipped without a scan.
-//   * fewer than k points in the tree: the list holds M entries, the rest is reported as -1 / -1.0.
-// Fixed radius (_FixedRangeSearch), r2 fixed for the whole walk:
-//   * internal node: prune when a >= 0 && a*a >= r2 (a as above).
-//   * myd = splitval - p[axis]; myd >= 0: child1 first, child2 after it only if myd*myd < r2; otherwise child2 first and
-//     child1 under the same condition.  r2 never changes, so the condition is tested when the far child is pushed.
-//   * leaf: every point with Dist2 < r2, in bucket order; the list is in visiting order.
-// k nearest within a radius (KDtree::kNearestRangeSearch, kd.cc:137-171; _KNNRangeSearch, kdTreeImpl.h:684-745), in the
-// pointer flavour: the list's pointers come from calloc, so closest_neighbors[k-1] == 0 is "the list is not full", which is
-// distances[k-1] == -1 (a slot gets its pointer and its distance together).  r2 (sqRad2) is fixed for the whole walk:
-//   * the k-NN list: k slots, distances start at -1, a point goes in before the first slot that is unset or strictly larger.
-//   * leaf: scanned whenever it is reached, in bucket order.  A point is skipped when Dist2 >= r2, in that sense (a NaN
-//     distance is NOT skipped); otherwise it is inserted.
-//   * internal node: a is computed on EVERY entry, not only when the list is full.  List not full: prune when a >= 0 &&
-//     a*a >= r2.  List full: prune when a >= 0 && a*a >= distances[k-1].
-//   * myd = splitval - p[axis]; myd >= 0: child1 first, otherwise child2 -- the range search's rule, not _KNNSearch's strict
-//     p < splitval.  The far child only if myd*myd < r2: the radius, never the k-th distance, so the test is made at the
-//     push.  When the far child is popped it meets its own box test with the list as it is then.
-//   * result: the slots with a distance >= 0, in list order, and their number (0 .. k).
-// Adaptive k (calculateNormalsAdaptiveKNN, normals.cc:563-682), per point, kidx = kmin .. kmax:
-//   * a FRESH k-NN walk with k = kidx + 1: new list, empty stack, the rules above.  Not one walk at kmax + 1 cut to
-//     prefixes: a node's box is fl((min+max)/2) +- fl((max-min)/2) and may exclude one of its own points by an ulp, so a
-//     point that walk(k) prunes can enter the first k slots of walk(k'), and the reference's answer is walk(k)'s.
-//   * nr = the slots with a distance >= 0 (< kidx + 1 only when the cloud has fewer points); mean and covariance over those
-//     nr entries in list order, / nr (list_cov); newmat's EigenValues: e1 <= e2 <= e3.
-//   * stop when (e1 > 0.25 * e2) && (fabs(1.0 - e2 / e3) < 0.25), in this sense: e3 == 0 gives NaN or inf and false, a list
-//     of one point gives the zero matrix and never stops.  No kidx stops: the list of kmax stands.
-//   * the normal is column 0 of the LAST eigenvector matrix computed, oriented and normalised as everywhere (orient_normal).
-// Dist2 (globals.icc:238) = (dx*dx + dy*dy) + dz*dz, dx = point - query; fp64 everywhere, FMA contraction off (Makefile).
-//
-// The cylinder, box and segment queries (kdIndexed.cc:164-213, 233-301; kdTreeImpl.h:432-577, 747-913).  p is the query
-// the lanes are binned by, v its second vector (dir, p0 or the box's upper corner); maxdist2 is one value per call.  Len2(x)
-// = (x0*x0 + x1*x1) + x2*x2, Dot(x, y) = (x0*y0 + x1*y1) + x2*y2, sqr(x) = x*x (globals.icc:197-213, 1374), r = the node's
-// bounding-sphere radius (node_r).  Every comparison is kept in the reference's sense ("skip when >=" is not "take when <"
-// once a NaN is involved).  Four of them return lists (count walk, scan, fill walk, as the fixed radius does), one a point.
-//
-// fixedRangeSearchAlongDir (_fixedRangeSearchAlongDir), dir as given -- never normalised:
-//   * internal node: p2c = p - centre; prune when Len2(p2c) - sqr(Dot(p2c, dir)) > sqr(r + sqrt(maxdist2)).
-//   * BOTH children, child1 first when p[axis] < splitval (strict); no plane test: the far child is always pushed.
-//   * leaf: p2p = p - point; every point with Len2(p2p) - sqr(Dot(p2p, dir)) < maxdist2, in bucket order.
-// fixedRangeSearchBetween2Points (_fixedRangeSearchBetween2Points): dist = sqrt(Dist2(p, p0)), dir = p0 - p divided by
-//   sqrt(d0*d0 + d1*d1 + d2*d2) (Normalize3 -- the same value as dist); p == p0 gives a NaN dir and an empty list.
-//   * the method's own node code runs ONLY on the node the walk starts at: it recurses into _fixedRangeSearchAlongDir.  So
-//     the root gets the cylinder test above and then two more, as written in the reference (a squared length plus a
-//     length in the first):  prune when dist > Len2(p0 - centre) + r,  prune when dist > sqrt(Len2(p - centre)) + r.
-//   * everything below the root, and a root that is a leaf: the cylinder walk.
-// AABBSearch (_AABBSearch), box [p, v]; a box with p[i] > v[i] is refused on the host before anything is launched:
-//   * internal node: prune when cx+hx < p0 || cy+hy < p1 || cz+hz < p2 || cx-hx > v0 || cy-hy > v1 || cz-hz > v2.
-//   * splitval > p[axis]: child1, and child2 after it only if splitval < v[axis]; otherwise child2 ALONE.  This is not the
-//     geometric set: a point on the split plane that went to child1 is missed by a box whose lower face lies on the plane,
-//     and the answer depends on the bucket size.  It is the reference's answer.
-//   * leaf: x >= p0 && x <= v0 && y >= p1 && y <= v1 && z >= p2 && z <= v2, in bucket order.
-// The segment queries share their set-up (kdIndexed.cc:252-301): segment_dir = p0 - p, segment_len2 = Len2(dir), segment_n
-//   = dir / len2 (NOT a unit vector: p + t * n is the projection for t = Dot(x - p, dir)), maxdist_d = sqrt(maxdist2).
-//   The comparison point of x (a bucket point or a node centre): t = Dot(x - p, dir);  t < 0: p;  t > len2: p0;  otherwise
-//   p + t * n.  comp_d2(x) = Dist2(comp, x).  With p == p0, n is 0/0: t is 0, the third case applies and comp_d2 is NaN.
-// segmentSearch_all (_segmentSearch_all): segment_center = p + dir*0.5, segment_r2 = sqr(0.5*sqrt(len2) + sqrt(maxdist2)).
-//   * internal node: the box test of segment_center, prune when a >= 0 && a*a >= segment_r2 (a as in the k-NN walk); then
-//     prune when comp_d2(centre) > sqr(r + maxdist_d).
-//   * both children, child1 first when p[axis] < splitval (strict), no plane test.
-//   * leaf: every point with comp_d2(point) < maxdist2 (a NaN comp_d2 takes nothing: p == p0 gives an empty list).
-// segmentSearch_1NearestPoint (_segmentSearch_1NearestPoint): closest_d2 starts at sqr(sqrt(Dist2(p, p0)) + sqrt(maxdist2)).
-//   * internal node: the box test of p, prune when a >= 0 && a*a >= closest_d2 (its value at that moment); then the same
-//     comp_d2(centre) > sqr(r + maxdist_d).
-//   * myd = splitval - p[axis]; myd >= 0: child1 first, otherwise child2; the far child only if sqr(myd) < closest_d2 WHEN
-//     THE NEAR CHILD HAS RETURNED: myd*myd goes on the stack and is tested against the then-current closest_d2 at the pop.
-//   * leaf: a point is skipped when comp_d2(point) >= maxdist2 (a NaN comp_d2 is NOT skipped: p == p0 still finds the nearest
-//     point within the initial closest_d2 = sqr(0 + sqrt(maxdist2))); then newdist2 = Dist2(p, point), taken when < closest_d2 (strict: the
-//     first visited point wins a tie).
-//   * nothing found: index -1 and d2 -1.0 (the reference returns size_t max).
+// This file holds what needs the device: the kernarg block, the lane stack's set-up, the register list, list_normal, the
+// kernels and the launchers.  The walks and everything else a lane does, with the rules of every walk, are in query_lane.h.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 
@@ -101,6 +14,7 @@
 #include "lane_stack.h"
 #include "eigen3.h"
 #include "query.h"
+#include "query_lane.h"
 
 namespace tdtk {
 
@@ -120,29 +34,6 @@ __device__ __forceinline__ const QueryArgs& q_args()
   return *(const QueryArgs*)p;
 }
 
-// one node's box test (kdTreeImpl.h:606-612 / 662-668): std::max(std::max(ax, ay), az)
-__device__ __forceinline__ double box_dist(const KdNode& nd, const double qx, const double qy, const double qz)
-{
-  const double ax = fabs(qx - nd.cx) - nd.hx;
-  const double ay = fabs(qy - nd.cy) - nd.hy;
-  const double az = fabs(qz - nd.cz) - nd.hz;
-  const double ab = (ax < ay) ? ay : ax;
-  return (ab < az) ? az : ab;
-}
-
-__device__ __forceinline__ void leaf_span(const QueryArgs& a, const uint32_t ref, uint32_t& start, uint32_t& count)
-{
-  const uint32_t v = ref & REF_VAL;
-  if (a.leaf_tab) { const LeafEntry e = a.leaf_tab[v]; start = (uint32_t)e.start; count = (uint32_t)e.count; }
-  else { start = v >> a.cb; count = v & a.cmask; }
-}
-
-__device__ __forceinline__ double dist2(const KdPoint& p, const double qx, const double qy, const double qz)
-{
-  const double dx = p.x - qx, dy = p.y - qy, dz = p.z - qz;
-  return (dx * dx + dy * dy) + dz * dz;
-}
-
 template <int BLOCK>
 __device__ __forceinline__ void stack_init(LaneStackQ<BLOCK, Q_SD>& st, uint4 (*lds)[BLOCK], const QueryArgs& a)
 {
@@ -154,8 +45,23 @@ __device__ __forceinline__ void stack_init(LaneStackQ<BLOCK, Q_SD>& st, uint4 (*
   st.sp = 0;
 }
 
-// ---- the k-NN list ----------------------------------------------------------------------------------------------
-// in registers, KC slots, every index static (nothing goes to scratch).  The list is the LAST k slots, k0 = KC - k;
+// the opening of every kernel: the lane's stack and its grid-stride position i over the sorted queries (step T).  The loop
+// itself stays in the kernel, for (LaneQueries<B> q(a, s_stack); q.i < a.n; q.i += q.T): handed over as a lambda the same
+// body costs two to six vector registers in most kernels ("layout of the query code")
+template <int BLOCK>
+struct LaneQueries {
+  LaneStackQ<BLOCK, Q_SD> st;
+  size_t i, T;
+  __device__ __forceinline__ LaneQueries(const QueryArgs& a, uint4 (*lds)[BLOCK])
+  {
+    stack_init<BLOCK>(st, lds, a);
+    T = (size_t)gridDim.x * BLOCK;
+    i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  }
+};
+
+// ---- the k-NN list, in registers (the LDS form: ListLds, query_lane.h) ---------------------------------------------
+// KC slots, every index static (nothing goes to scratch).  The list is the LAST k slots, k0 = KC - k;
 // the k0 slots in front hold -0.0, which is neither unset (-0.0 < 0.0 is false) nor larger than any distance, so an
 // insertion never stops there and never shifts them: the bubble below needs no per-slot test of k, and distances[k-1]
 // is always slot KC-1.
@@ -200,172 +106,10 @@ struct ListReg {
   }
 };
 
-// in LDS, [slot][lane] (a wave's accesses to one slot are 64 consecutive 8-byte words: no bank conflict)
-template <int BLOCK>
-struct ListLds {
-  double* ld;
-  uint32_t* ls;
-  int k, cnt;
-  double kth;
-  __device__ __forceinline__ void init(int kk)
-  {
-    k = kk; cnt = 0; kth = -1.0;
-    for (int j = 0; j < k; j++) { ld[j * BLOCK] = -1.0; ls[j * BLOCK] = 0xFFFFFFFFu; }
-  }
-  __device__ __forceinline__ bool full() const { return kth != -1.0; }
-  __device__ __forceinline__ void insert(const double md, const uint32_t slot)
-  {
-    if (kth != -1.0 && kth <= md) return;
-    int j = 0;
-    for (; j < cnt; j++) if (ld[j * BLOCK] > md) break;     // slots >= cnt are unset
-    if (j >= k) return;
-    // the reference moves slots j .. k-2 up by one; beyond cnt they are unset and stay so
-    for (int l = (cnt < k - 1 ? cnt : k - 1); l > j; --l) { ld[l * BLOCK] = ld[(l - 1) * BLOCK]; ls[l * BLOCK] = ls[(l - 1) * BLOCK]; }
-    ld[j * BLOCK] = md;
-    ls[j * BLOCK] = slot;
-    if (cnt < k) ++cnt;
-    if (cnt == k) kth = ld[(k - 1) * BLOCK];
-  }
-  __device__ __forceinline__ double dist(int j) const { return ld[j * BLOCK]; }
-  __device__ __forceinline__ uint32_t slot(int j) const { return ls[j * BLOCK]; }
-};
-
-// ---- the walks -------------------------------------------------------------------------------------------------
-template <int BLOCK, class LIST>
-__device__ void knn_walk(const QueryArgs& a, const double qx, const double qy, const double qz, LIST& L,
-                         LaneStackQ<BLOCK, Q_SD>& st)
-{
-  uint32_t cur = a.root_ref;
-  for (;;) {
-    if (cur & REF_LEAF) {
-      uint32_t start, count;
-      leaf_span(a, cur, start, count);
-      for (uint32_t i = 0; i < count; i++) {
-        const KdPoint p = a.pts[start + i];
-        L.insert(dist2(p, qx, qy, qz), start + i);
-      }
-    } else {
-      const KdNode nd = a.nodes[cur & REF_VAL];
-      bool pruned = false;
-      if (L.full()) {
-        const double ap = box_dist(nd, qx, qy, qz);
-        pruned = (ap >= 0.0 && ap * ap >= L.kth);
-      }
-      if (!pruned) {
-        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
-        const double qa = (axis == 0) ? qx : ((axis == 1) ? qy : qz);
-        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2 = nd.c2 & ~REF_AXIS;
-        const bool first = qa < nd.splitval;
-        st.push(first ? r2 : r1, 0.0);
-        cur = first ? r1 : r2;
-        continue;
-      }
-    }
-    if (st.sp == 0) break;
-    --st.sp;
-    double unused;
-    st.top(cur, unused);
-  }
-}
-
-// EMIT(point, slot, d2) for every point of the radius list, in the reference's visiting order
-template <int BLOCK, class EMIT>
-__device__ void range_walk(const QueryArgs& a, const double qx, const double qy, const double qz, const double r2,
-                           LaneStackQ<BLOCK, Q_SD>& st, EMIT& emit)
-{
-  uint32_t cur = a.root_ref;
-  for (;;) {
-    if (cur & REF_LEAF) {
-      uint32_t start, count;
-      leaf_span(a, cur, start, count);
-      for (uint32_t i = 0; i < count; i++) {
-        const KdPoint p = a.pts[start + i];
-        const double md = dist2(p, qx, qy, qz);
-        if (md < r2) emit(p, start + i, md);
-      }
-    } else {
-      const KdNode nd = a.nodes[cur & REF_VAL];
-      const double ap = box_dist(nd, qx, qy, qz);
-      if (!(ap >= 0.0 && ap * ap >= r2)) {
-        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
-        const double qa = (axis == 0) ? qx : ((axis == 1) ? qy : qz);
-        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2c = nd.c2 & ~REF_AXIS;
-        const double myd = nd.splitval - qa;
-        const bool first = myd >= 0.0;
-        if (myd * myd < r2) st.push(first ? r2c : r1, 0.0);
-        cur = first ? r1 : r2c;
-        continue;
-      }
-    }
-    if (st.sp == 0) break;
-    --st.sp;
-    double unused;
-    st.top(cur, unused);
-  }
-}
-
-// k nearest within r2 (_KNNRangeSearch): knn_walk's list under range_walk's child order and plane test
-template <int BLOCK, class LIST>
-__device__ void knn_range_walk(const QueryArgs& a, const double qx, const double qy, const double qz, const double r2, LIST& L,
-                               LaneStackQ<BLOCK, Q_SD>& st)
-{
-  uint32_t cur = a.root_ref;
-  for (;;) {
-    if (cur & REF_LEAF) {
-      uint32_t start, count;
-      leaf_span(a, cur, start, count);
-      for (uint32_t i = 0; i < count; i++) {
-        const KdPoint p = a.pts[start + i];
-        const double md = dist2(p, qx, qy, qz);
-        if (md >= r2) continue;
-        L.insert(md, start + i);
-      }
-    } else {
-      const KdNode nd = a.nodes[cur & REF_VAL];
-      const double ap = box_dist(nd, qx, qy, qz);
-      const double bound = L.full() ? L.kth : r2;
-      if (!(ap >= 0.0 && ap * ap >= bound)) {
-        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
-        const double qa = (axis == 0) ? qx : ((axis == 1) ? qy : qz);
-        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2c = nd.c2 & ~REF_AXIS;
-        const double myd = nd.splitval - qa;
-        const bool first = myd >= 0.0;
-        if (myd * myd < r2) st.push(first ? r2c : r1, 0.0);
-        cur = first ? r1 : r2c;
-        continue;
-      }
-    }
-    if (st.sp == 0) break;
-    --st.sp;
-    double unused;
-    st.top(cur, unused);
-  }
-}
-
-// calculateNormal (normals.cc:518-558) over a list the caller enumerates: each(f) calls f(point) for the nr points of the
-// list in list order, and is called twice (mean, then covariance -- the arithmetic of k_ann_normals: mean / nr, then
-// A = (1/nr X^T) X summed in list order, lower triangle of z); eigen3.h does the rest.  nr is read after the first pass (the
-// range normals count their list there).
-template <class EACH>
-__device__ __forceinline__ void list_cov(EACH&& each, const int& nr, double z[3][3])
-{
-  double mean[3] = {0.0, 0.0, 0.0};
-  each([&](const KdPoint& p) { mean[0] += p.x; mean[1] += p.y; mean[2] += p.z; });
-  mean[0] /= nr; mean[1] /= nr; mean[2] /= nr;
-  const double sc = 1.0 / nr;
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int c = 0; c <= r; c++) z[r][c] = 0.0;
-  each([&](const KdPoint& p) {
-    const double x[3] = {p.x - mean[0], p.y - mean[1], p.z - mean[2]};
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-      for (int c = 0; c <= r; c++) z[r][c] += (sc * x[c]) * x[r];
-  });
-}
-
+// list_cov and normal_from_cov in one: the same arithmetic (cov_eigen fills the upper triangle itself), kept as a second
+// copy because of what the compiler makes of the composition in the register kernels with normals -- 116 -> 121, 170 -> 181
+// and 242 -> 254 vector registers, and SGPR spills at KC = 32 (11 in k_knn_reg, 32 in k_knnr_reg); zeroing all nine entries
+// in list_cov does not help
 template <class EACH>
 __device__ __forceinline__ void list_normal(EACH&& each, const int& nr, const double qx, const double qy, const double qz,
                                             const QueryArgs& a, double* out)
@@ -386,22 +130,25 @@ __device__ __forceinline__ void list_normal(EACH&& each, const int& nr, const do
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------
-// Both k-NN kernels end alike: the list as a caller-order row (idx and d2, or knn_out for the normals: -1 / -1.0 beyond nr
-// entries) and, for the normals, list_normal over it.  They differ in how a list slot is reached: a register list only by
-// static indices (every loop fully unrolled over the capacity), the LDS list by a run-time index.
+// Every kernel's only parameter is the argument block (q_args); a __global__ function here declares the LDS arrays and
+// hands them to its body.
+//
+// k nearest neighbours (RANGE = false: knn_walk) and k nearest within a radius (RANGE = true: knn_range_walk, and one more
+// output: nr_out [n], the length of every list, nullable), one body per list form.  Both end alike: the list as a
+// caller-order row (idx and d2, or knn_out for the normals) and, for the normals, list_normal over it.  Under RANGE a list
+// may be empty (no point within r2 of a query); list_normal on it gives NaN, calculateNormal's 0 / 0 -- the normals' own
+// queries always find themselves, except under k_range_normals' caveat.
 
 // the register-list form: list slot jl is register slot j = k0 + jl
-template <int KC, bool NORMALS>
-__global__ void __launch_bounds__(Q_BLOCK) k_knn_reg(const QueryArgs a_)
+template <int KC, bool NORMALS, bool RANGE>
+__device__ __forceinline__ void knn_reg_body(uint4 (*s_stack)[Q_BLOCK])
 {
   const QueryArgs& a = q_args();
-  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
-  LaneStackQ<Q_BLOCK, Q_SD> st;
-  stack_init<Q_BLOCK>(st, s_stack, a);
+  LaneQueries<Q_BLOCK> q(a, s_stack);
   ListReg<KC> L;
   const int k = a.k;
-  const size_t T = (size_t)gridDim.x * Q_BLOCK;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+  for (; q.i < a.n; q.i += q.T) {
+    const size_t i = q.i;
     const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
     const size_t o = a.order ? (size_t)a.order[i] : i;
     // (k0 through an empty asm, per query: as a loop invariant the list's initial values and the slot tests below would be
@@ -409,10 +156,11 @@ __global__ void __launch_bounds__(Q_BLOCK) k_knn_reg(const QueryArgs a_)
     int k0 = KC - k;
     asm volatile("" : "+v"(k0));
     L.init(k0);
-    st.sp = 0;
-    knn_walk<Q_BLOCK>(a, qx, qy, qz, L, st);
-    // entries: the slots with a distance >= 0 (kdIndexed.cc:152-156), which are the first nr -- fewer than k only when the
-    // tree has fewer than k points.  (jl through an empty asm per slot, for the reason above.)
+    q.st.sp = 0;
+    if (RANGE) knn_range_walk(a, qx, qy, qz, a.r2, L, q.st);
+    else knn_walk(a, qx, qy, qz, L, q.st);
+    // entries: the slots with a distance >= 0 (kdIndexed.cc:152-156, kd.cc:158-165), which are the first nr -- fewer than k
+    // only when the walk met fewer than k points.  (jl through an empty asm per slot, for the reason above.)
     int nr = 0;
 #pragma unroll
     for (int j = 0; j < KC; j++) {
@@ -431,6 +179,7 @@ __global__ void __launch_bounds__(Q_BLOCK) k_knn_reg(const QueryArgs a_)
       };
       list_normal(each, nr, qx, qy, qz, a, a.normals + 3 * o);
     }
+    if (RANGE && a.nr_out) a.nr_out[o] = nr;
     // (the row after the normal: written first, its loads of the points were kept live across the PCA -- 170 registers
     // instead of 134 at k = 20)
     int32_t* row = NORMALS ? a.knn_out : a.idx;
@@ -449,129 +198,41 @@ __global__ void __launch_bounds__(Q_BLOCK) k_knn_reg(const QueryArgs a_)
   }
 }
 
-// the LDS-list form (33 <= k <= 64)
-template <bool NORMALS>
-__global__ void __launch_bounds__(Q_BLOCK_L) k_knn_lds(const QueryArgs a_)
+template <int KC, bool NORMALS>
+__global__ void __launch_bounds__(Q_BLOCK) k_knn_reg(const QueryArgs a_)
 {
-  const QueryArgs& a = q_args();
-  __shared__ uint4 s_stack[Q_SD][Q_BLOCK_L];
-  __shared__ double s_d[KNN_MAX_K][Q_BLOCK_L];
-  __shared__ uint32_t s_s[KNN_MAX_K][Q_BLOCK_L];
-  LaneStackQ<Q_BLOCK_L, Q_SD> st;
-  stack_init<Q_BLOCK_L>(st, s_stack, a);
-  ListLds<Q_BLOCK_L> L;
-  L.ld = &s_d[0][threadIdx.x];
-  L.ls = &s_s[0][threadIdx.x];
-  const int k = a.k;
-  const size_t T = (size_t)gridDim.x * Q_BLOCK_L;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK_L + threadIdx.x; i < a.n; i += T) {
-    const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
-    const size_t o = a.order ? (size_t)a.order[i] : i;
-    L.init(k);
-    st.sp = 0;
-    knn_walk<Q_BLOCK_L>(a, qx, qy, qz, L, st);
-    int nr = 0;
-    for (int j = 0; j < k; j++) nr += (L.dist(j) >= 0.0) ? 1 : 0;   // kdIndexed.cc:152-156
-    int32_t* row = NORMALS ? a.knn_out : a.idx;
-    row = row ? row + o * k : nullptr;
-    double* drow = (!NORMALS && a.d2) ? a.d2 + o * k : nullptr;
-    for (int j = 0; j < k; j++) {
-      const bool v = j < nr;
-      if (row) row[j] = v ? a.pts[v ? L.slot(j) : 0u].orig : -1;
-      if (drow) drow[j] = v ? L.dist(j) : -1.0;
-    }
-    if (NORMALS) {
-      auto each = [&](auto&& f) { for (int j = 0; j < nr; j++) f(a.pts[L.slot(j)]); };
-      list_normal(each, nr, qx, qy, qz, a, a.normals + 3 * o);
-    }
-  }
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  knn_reg_body<KC, NORMALS, false>(s_stack);
 }
 
-// ---- k nearest within a radius (kNearestRangeSearch) and the normals over its lists ------------------------------------
-// k_knn_reg and k_knn_lds with knn_range_walk in place of knn_walk (their empty-asm idiom for k0 / jl is explained there),
-// and one more output: nr_out [n], the length of every list (nullable).  A list may be empty here (no point within r2 of a
-// query); list_normal on it gives NaN, calculateNormal's 0 / 0 -- the normals' own queries always find themselves, except
-// under k_range_normals' caveat.
-
-// the register-list form
 template <int KC, bool NORMALS>
 __global__ void __launch_bounds__(Q_BLOCK) k_knnr_reg(const QueryArgs a_)
 {
-  const QueryArgs& a = q_args();
   __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
-  LaneStackQ<Q_BLOCK, Q_SD> st;
-  stack_init<Q_BLOCK>(st, s_stack, a);
-  ListReg<KC> L;
-  const int k = a.k;
-  const size_t T = (size_t)gridDim.x * Q_BLOCK;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
-    const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
-    const size_t o = a.order ? (size_t)a.order[i] : i;
-    int k0 = KC - k;
-    asm volatile("" : "+v"(k0));
-    L.init(k0);
-    st.sp = 0;
-    knn_range_walk<Q_BLOCK>(a, qx, qy, qz, a.r2, L, st);
-    // entries: the slots with a distance >= 0 (kd.cc:158-165), which are the first nr
-    int nr = 0;
-#pragma unroll
-    for (int j = 0; j < KC; j++) {
-      int jl = j - k0;
-      asm volatile("" : "+v"(jl));
-      nr += (jl >= 0 && L.d[j] >= 0.0) ? 1 : 0;
-    }
-    if (NORMALS) {
-      auto each = [&](auto&& f) {
-#pragma unroll
-        for (int j = 0; j < KC; j++) {
-          int jl = j - k0;
-          asm volatile("" : "+v"(jl));
-          if (jl >= 0 && jl < nr) f(a.pts[L.s[j]]);
-        }
-      };
-      list_normal(each, nr, qx, qy, qz, a, a.normals + 3 * o);
-    }
-    if (a.nr_out) a.nr_out[o] = nr;
-    int32_t* row = NORMALS ? a.knn_out : a.idx;
-    row = row ? row + o * k : nullptr;
-    double* drow = (!NORMALS && a.d2) ? a.d2 + o * k : nullptr;
-#pragma unroll
-    for (int j = 0; j < KC; j++) {
-      int jl = j - k0;
-      asm volatile("" : "+v"(jl));
-      if (jl >= 0) {
-        const bool v = jl < nr;
-        if (row) row[jl] = v ? a.pts[v ? L.s[j] : 0u].orig : -1;     // (an unset slot's point is never loaded)
-        if (drow) drow[jl] = v ? L.d[j] : -1.0;
-      }
-    }
-  }
+  knn_reg_body<KC, NORMALS, true>(s_stack);
 }
 
 // the LDS-list form (33 <= k <= 64)
-template <bool NORMALS>
-__global__ void __launch_bounds__(Q_BLOCK_L) k_knnr_lds(const QueryArgs a_)
+template <bool NORMALS, bool RANGE>
+__device__ __forceinline__ void knn_lds_body(uint4 (*s_stack)[Q_BLOCK_L], double (*s_d)[Q_BLOCK_L], uint32_t (*s_s)[Q_BLOCK_L])
 {
   const QueryArgs& a = q_args();
-  __shared__ uint4 s_stack[Q_SD][Q_BLOCK_L];
-  __shared__ double s_d[KNN_MAX_K][Q_BLOCK_L];
-  __shared__ uint32_t s_s[KNN_MAX_K][Q_BLOCK_L];
-  LaneStackQ<Q_BLOCK_L, Q_SD> st;
-  stack_init<Q_BLOCK_L>(st, s_stack, a);
+  LaneQueries<Q_BLOCK_L> q(a, s_stack);
   ListLds<Q_BLOCK_L> L;
   L.ld = &s_d[0][threadIdx.x];
   L.ls = &s_s[0][threadIdx.x];
   const int k = a.k;
-  const size_t T = (size_t)gridDim.x * Q_BLOCK_L;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK_L + threadIdx.x; i < a.n; i += T) {
+  for (; q.i < a.n; q.i += q.T) {
+    const size_t i = q.i;
     const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
     const size_t o = a.order ? (size_t)a.order[i] : i;
     L.init(k);
-    st.sp = 0;
-    knn_range_walk<Q_BLOCK_L>(a, qx, qy, qz, a.r2, L, st);
+    q.st.sp = 0;
+    if (RANGE) knn_range_walk(a, qx, qy, qz, a.r2, L, q.st);
+    else knn_walk(a, qx, qy, qz, L, q.st);
     int nr = 0;
-    for (int j = 0; j < k; j++) nr += (L.dist(j) >= 0.0) ? 1 : 0;   // kd.cc:158-165
-    if (a.nr_out) a.nr_out[o] = nr;
+    for (int j = 0; j < k; j++) nr += (L.dist(j) >= 0.0) ? 1 : 0;   // kdIndexed.cc:152-156, kd.cc:158-165
+    if (RANGE && a.nr_out) a.nr_out[o] = nr;
     int32_t* row = NORMALS ? a.knn_out : a.idx;
     row = row ? row + o * k : nullptr;
     double* drow = (!NORMALS && a.d2) ? a.d2 + o * k : nullptr;
@@ -585,12 +246,30 @@ __global__ void __launch_bounds__(Q_BLOCK_L) k_knnr_lds(const QueryArgs a_)
       list_normal(each, nr, qx, qy, qz, a, a.normals + 3 * o);
     }
   }
+}
+
+template <bool NORMALS>
+__global__ void __launch_bounds__(Q_BLOCK_L) k_knn_lds(const QueryArgs a_)
+{
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK_L];
+  __shared__ double s_d[KNN_MAX_K][Q_BLOCK_L];
+  __shared__ uint32_t s_s[KNN_MAX_K][Q_BLOCK_L];
+  knn_lds_body<NORMALS, false>(s_stack, s_d, s_s);
+}
+
+template <bool NORMALS>
+__global__ void __launch_bounds__(Q_BLOCK_L) k_knnr_lds(const QueryArgs a_)
+{
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK_L];
+  __shared__ double s_d[KNN_MAX_K][Q_BLOCK_L];
+  __shared__ uint32_t s_s[KNN_MAX_K][Q_BLOCK_L];
+  knn_lds_body<NORMALS, true>(s_stack, s_d, s_s);
 }
 
 // ---- adaptive-k normals (calculateNormalsAdaptiveKNN) --------------------------------------------------------------
 // Every query repeats the whole search for kidx = kmin .. kmax with a fresh list of kidx + 1 slots and an empty stack, runs
 // the PCA on each list and stops at the first whose eigenvalues pass adaptive_k_accepts, or at kmax (rules: the header
-// comment).  kidx is a per-lane value.  The two kernels are the two list forms of the k-NN kernels, with their block sizes
+// comment of query_lane.h).  kidx is a per-lane value.  The two kernels are the two list forms of the k-NN kernels, with their block sizes
 // and grids (query_overflow_entries covers both).
 // Rows: normals [n][3], k_used [n] (nullable), knn_out [n][kmax + 1] (nullable): the chosen list, -1 behind its nr entries.
 //
@@ -605,23 +284,21 @@ __global__ void __launch_bounds__(Q_BLOCK) k_knn_adaptive_reg(const QueryArgs a_
 {
   const QueryArgs& a = q_args();
   __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
-  LaneStackQ<Q_BLOCK, Q_SD> st;
-  stack_init<Q_BLOCK>(st, s_stack, a);
+  LaneQueries<Q_BLOCK> q(a, s_stack);
   ListReg<KC, true> L;
-  const size_t T = (size_t)gridDim.x * Q_BLOCK;
   // one loop over (query, kidx) steps: a lane whose list passed the test goes on to its next query while its neighbours are
   // still trying longer lists of theirs (as two nested loops the kernel carried two more loop masks beside insert()'s lane
   // masks, and spilled SGPRs at KC = 32)
-  size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x;
   int kidx = a.kmin;
-  while (i < a.n) {
+  while (q.i < a.n) {
+    const size_t i = q.i;
     const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
-    // (k0 through an empty asm at every use, as in k_knn_reg: the slot tests stay in vector registers)
+    // (k0 through an empty asm at every use, as in knn_reg_body: the slot tests stay in vector registers)
     int k0 = KC - (kidx + 1);
     asm volatile("" : "+v"(k0));
     L.init(k0);
-    st.sp = 0;
-    knn_walk<Q_BLOCK>(a, qx, qy, qz, L, st);
+    q.st.sp = 0;
+    knn_walk(a, qx, qy, qz, L, q.st);
     int nr = 0;
 #pragma unroll
     for (int j = 0; j < KC; j++) {
@@ -658,7 +335,7 @@ __global__ void __launch_bounds__(Q_BLOCK) k_knn_adaptive_reg(const QueryArgs a_
       }
       for (int jl = kidx + 1; jl <= kmax; jl++) row[jl] = -1;
     }
-    i += T;
+    q.i += q.T;
     kidx = a.kmin;
   }
 }
@@ -670,20 +347,18 @@ __global__ void __launch_bounds__(Q_BLOCK_L) k_knn_adaptive_lds(const QueryArgs 
   __shared__ uint4 s_stack[Q_SD][Q_BLOCK_L];
   __shared__ double s_d[KNN_MAX_K][Q_BLOCK_L];
   __shared__ uint32_t s_s[KNN_MAX_K][Q_BLOCK_L];
-  LaneStackQ<Q_BLOCK_L, Q_SD> st;
-  stack_init<Q_BLOCK_L>(st, s_stack, a);
+  LaneQueries<Q_BLOCK_L> q(a, s_stack);
   ListLds<Q_BLOCK_L> L;
   L.ld = &s_d[0][threadIdx.x];
   L.ls = &s_s[0][threadIdx.x];
-  const size_t T = (size_t)gridDim.x * Q_BLOCK_L;
-  size_t i = (size_t)blockIdx.x * Q_BLOCK_L + threadIdx.x;
   int kidx = a.kmin;
-  while (i < a.n) {
+  while (q.i < a.n) {
+    const size_t i = q.i;
     const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
     const int k = kidx + 1;
     L.init(k);
-    st.sp = 0;
-    knn_walk<Q_BLOCK_L>(a, qx, qy, qz, L, st);
+    q.st.sp = 0;
+    knn_walk(a, qx, qy, qz, L, q.st);
     int nr = 0;
     for (int j = 0; j < k; j++) nr += (L.dist(j) >= 0.0) ? 1 : 0;   // kdIndexed.cc:152-156
     auto each = [&](auto&& f) { for (int j = 0; j < nr; j++) f(a.pts[L.slot(j)]); };
@@ -702,7 +377,7 @@ __global__ void __launch_bounds__(Q_BLOCK_L) k_knn_adaptive_lds(const QueryArgs 
         row[j] = v ? a.pts[v ? L.slot(j) : 0u].orig : -1;
       }
     }
-    i += T;
+    q.i += q.T;
     kidx = a.kmin;
   }
 }
@@ -712,14 +387,12 @@ __global__ void __launch_bounds__(Q_BLOCK) k_range_count(const QueryArgs a_)
 {
   const QueryArgs& a = q_args();
   __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
-  LaneStackQ<Q_BLOCK, Q_SD> st;
-  stack_init<Q_BLOCK>(st, s_stack, a);
-  const size_t T = (size_t)gridDim.x * Q_BLOCK;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
+    const size_t i = q.i;
     uint32_t c = 0;
     auto emit = [&](const KdPoint&, uint32_t, double) { ++c; };
-    st.sp = 0;
-    range_walk<Q_BLOCK>(a, a.x[i], a.y[i], a.z[i], a.r2, st, emit);
+    q.st.sp = 0;
+    range_walk(a, a.x[i], a.y[i], a.z[i], a.r2, q.st, emit);
     a.counts[a.order ? (size_t)a.order[i] : i] = c;
   }
 }
@@ -729,10 +402,8 @@ __global__ void __launch_bounds__(Q_BLOCK) k_range_fill(const QueryArgs a_)
 {
   const QueryArgs& a = q_args();
   __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
-  LaneStackQ<Q_BLOCK, Q_SD> st;
-  stack_init<Q_BLOCK>(st, s_stack, a);
-  const size_t T = (size_t)gridDim.x * Q_BLOCK;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
+    const size_t i = q.i;
     const size_t o = a.order ? (size_t)a.order[i] : i;
     unsigned long long w = a.offsets[o];
     const unsigned long long end = a.offsets[o + 1];
@@ -743,8 +414,8 @@ __global__ void __launch_bounds__(Q_BLOCK) k_range_fill(const QueryArgs a_)
       }
       ++w;
     };
-    st.sp = 0;
-    range_walk<Q_BLOCK>(a, a.x[i], a.y[i], a.z[i], a.r2, st, emit);
+    q.st.sp = 0;
+    range_walk(a, a.x[i], a.y[i], a.z[i], a.r2, q.st, emit);
   }
 }
 
@@ -756,18 +427,16 @@ __global__ void __launch_bounds__(Q_BLOCK) k_range_normals(const QueryArgs a_)
 {
   const QueryArgs& a = q_args();
   __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
-  LaneStackQ<Q_BLOCK, Q_SD> st;
-  stack_init<Q_BLOCK>(st, s_stack, a);
-  const size_t T = (size_t)gridDim.x * Q_BLOCK;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
+    const size_t i = q.i;
     const double qx = a.x[i], qy = a.y[i], qz = a.z[i];
     const size_t o = a.order ? (size_t)a.order[i] : i;
     int nr = 0;
     bool counted = false;
     auto each = [&](auto&& f) {
       auto emit = [&](const KdPoint& p, uint32_t, double) { f(p); if (!counted) ++nr; };
-      st.sp = 0;
-      range_walk<Q_BLOCK>(a, qx, qy, qz, a.r2, st, emit);
+      q.st.sp = 0;
+      range_walk(a, qx, qy, qz, a.r2, q.st, emit);
       counted = true;
     };
     list_normal(each, nr, qx, qy, qz, a, a.normals + 3 * o);
@@ -775,203 +444,18 @@ __global__ void __launch_bounds__(Q_BLOCK) k_range_normals(const QueryArgs a_)
 }
 
 // ---- cylinder, box and segment queries ------------------------------------------------------------------------
-// the segment of the two segment queries with the reference's set-up values, and the three-case comparison point
-struct Segment {
-  double px, py, pz, ex, ey, ez;   // p, p0
-  double dx, dy, dz, len2;         // segment_dir, segment_len2
-  double nx, ny, nz;               // segment_n = dir / len2
-  __device__ __forceinline__ void init(const double px_, const double py_, const double pz_, const double ex_,
-                                       const double ey_, const double ez_)
-  {
-    px = px_; py = py_; pz = pz_; ex = ex_; ey = ey_; ez = ez_;
-    dx = ex - px; dy = ey - py; dz = ez - pz;
-    len2 = (dx * dx + dy * dy) + dz * dz;
-    nx = dx / len2; ny = dy / len2; nz = dz / len2;
-  }
-  // Dist2(comp, x), comp the comparison point of x
-  __device__ __forceinline__ double comp_d2(const double x, const double y, const double z) const
-  {
-    const double ax = x - px, ay = y - py, az = z - pz;
-    const double t = (ax * dx + ay * dy) + az * dz;
-    double cx, cy, cz;
-    if (t < 0.0) { cx = px; cy = py; cz = pz; }
-    else if (t > len2) { cx = ex; cy = ey; cz = ez; }
-    else { cx = px + t * nx; cy = py + t * ny; cz = pz + t * nz; }
-    const double gx = x - cx, gy = y - cy, gz = z - cz;
-    return (gx * gx + gy * gy) + gz * gz;
-  }
-};
-
-// Len2(p2x) - sqr(Dot(p2x, dir)), p2x = p - x (kdTreeImpl.h:507-510, 519-522)
-__device__ __forceinline__ double line_d2(const double px, const double py, const double pz, const double x, const double y,
-                                          const double z, const double ux, const double uy, const double uz, double& len2)
-{
-  const double wx = px - x, wy = py - y, wz = pz - z;
-  len2 = (wx * wx + wy * wy) + wz * wz;
-  const double dot = (wx * ux + wy * uy) + wz * uz;
-  return len2 - dot * dot;
-}
-
-// EMIT(point) for every point of the list of query (p, v), in the reference's visiting order
-template <int MODE, int BLOCK, class EMIT>
-__device__ void shape_walk(const QueryArgs& a, const double px, const double py, const double pz, const double vx,
-                           const double vy, const double vz, LaneStackQ<BLOCK, Q_SD>& st, EMIT& emit)
-{
-  const double md2 = a.r2;
-  const double maxd = __dsqrt_rn(md2);
-  // the cylinder's axis, and Between2Points' dist
-  double ux = vx, uy = vy, uz = vz, dist = 0.0;
-  if (MODE == SHAPE_BETWEEN) {
-    ux = vx - px; uy = vy - py; uz = vz - pz;
-    dist = __dsqrt_rn((ux * ux + uy * uy) + uz * uz);
-    ux /= dist; uy /= dist; uz /= dist;
-  }
-  Segment sg;
-  double scx = 0.0, scy = 0.0, scz = 0.0, sr2 = 0.0;   // segment_center, segment_r2
-  if (MODE == SHAPE_SEGMENT) {
-    sg.init(px, py, pz, vx, vy, vz);
-    scx = px + sg.dx * 0.5; scy = py + sg.dy * 0.5; scz = pz + sg.dz * 0.5;
-    const double sr = 0.5 * __dsqrt_rn(sg.len2) + maxd;
-    sr2 = sr * sr;
-  }
-  bool root = (MODE == SHAPE_BETWEEN);
-  uint32_t cur = a.root_ref;
-  for (;;) {
-    if (cur & REF_LEAF) {
-      uint32_t start, count;
-      leaf_span(a, cur, start, count);
-      for (uint32_t i = 0; i < count; i++) {
-        const KdPoint p = a.pts[start + i];
-        bool take;
-        if (MODE == SHAPE_ALONG_DIR || MODE == SHAPE_BETWEEN) {
-          double unused;
-          take = line_d2(px, py, pz, p.x, p.y, p.z, ux, uy, uz, unused) < md2;
-        } else if (MODE == SHAPE_AABB) {
-          take = p.x >= px && p.x <= vx && p.y >= py && p.y <= vy && p.z >= pz && p.z <= vz;
-        } else {
-          take = sg.comp_d2(p.x, p.y, p.z) < md2;
-        }
-        if (take) emit(p);
-      }
-    } else {
-      const KdNode nd = a.nodes[cur & REF_VAL];
-      bool pruned;
-      if (MODE == SHAPE_ALONG_DIR || MODE == SHAPE_BETWEEN) {
-        const double r = a.node_r[cur & REF_VAL];
-        double len2;
-        const double d2c = line_d2(px, py, pz, nd.cx, nd.cy, nd.cz, ux, uy, uz, len2);
-        const double lim = r + maxd;
-        pruned = d2c > lim * lim;
-        if (MODE == SHAPE_BETWEEN && root && !pruned) {
-          // "check if not between points", as written (kdTreeImpl.h:465-472)
-          const double wx = vx - nd.cx, wy = vy - nd.cy, wz = vz - nd.cz;
-          const double dxp2 = (wx * wx + wy * wy) + wz * wz;
-          if (dist > dxp2 + r) pruned = true;
-          else if (dist > __dsqrt_rn(len2) + r) pruned = true;
-        }
-      } else if (MODE == SHAPE_AABB) {
-        pruned = nd.cx + nd.hx < px || nd.cy + nd.hy < py || nd.cz + nd.hz < pz ||
-                 nd.cx - nd.hx > vx || nd.cy - nd.hy > vy || nd.cz - nd.hz > vz;
-      } else {
-        const double ap = box_dist(nd, scx, scy, scz);
-        pruned = (ap >= 0.0 && ap * ap >= sr2);
-        if (!pruned) {
-          const double lim = a.node_r[cur & REF_VAL] + maxd;
-          pruned = sg.comp_d2(nd.cx, nd.cy, nd.cz) > lim * lim;
-        }
-      }
-      if (!pruned) {
-        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
-        const double pa = (axis == 0) ? px : ((axis == 1) ? py : pz);
-        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2c = nd.c2 & ~REF_AXIS;
-        root = false;
-        if (MODE == SHAPE_AABB) {
-          const double va = (axis == 0) ? vx : ((axis == 1) ? vy : vz);
-          if (nd.splitval > pa) {
-            if (nd.splitval < va) st.push(r2c, 0.0);
-            cur = r1;
-          } else {
-            cur = r2c;
-          }
-        } else {
-          const bool first = pa < nd.splitval;
-          st.push(first ? r2c : r1, 0.0);
-          cur = first ? r1 : r2c;
-        }
-        continue;
-      }
-    }
-    root = false;
-    if (st.sp == 0) break;
-    --st.sp;
-    double unused;
-    st.top(cur, unused);
-  }
-}
-
-// segmentSearch_1NearestPoint: best / bslot are closest_d2 / the bucket slot of closest (0xFFFFFFFF: none)
-template <int BLOCK>
-__device__ void segment_nearest_walk(const QueryArgs& a, const Segment& sg, LaneStackQ<BLOCK, Q_SD>& st, double& best,
-                                     uint32_t& bslot)
-{
-  const double md2 = a.r2;
-  const double maxd = __dsqrt_rn(md2);
-  uint32_t cur = a.root_ref;
-  for (;;) {
-    if (cur & REF_LEAF) {
-      uint32_t start, count;
-      leaf_span(a, cur, start, count);
-      for (uint32_t i = 0; i < count; i++) {
-        const KdPoint p = a.pts[start + i];
-        if (sg.comp_d2(p.x, p.y, p.z) >= md2) continue;
-        const double nd2 = dist2(p, sg.px, sg.py, sg.pz);
-        if (nd2 < best) { best = nd2; bslot = start + i; }
-      }
-    } else {
-      const KdNode nd = a.nodes[cur & REF_VAL];
-      const double ap = box_dist(nd, sg.px, sg.py, sg.pz);
-      bool pruned = (ap >= 0.0 && ap * ap >= best);
-      if (!pruned) {
-        const double lim = a.node_r[cur & REF_VAL] + maxd;
-        pruned = sg.comp_d2(nd.cx, nd.cy, nd.cz) > lim * lim;
-      }
-      if (!pruned) {
-        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
-        const double pa = (axis == 0) ? sg.px : ((axis == 1) ? sg.py : sg.pz);
-        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2c = nd.c2 & ~REF_AXIS;
-        const double myd = nd.splitval - pa;
-        const bool first = myd >= 0.0;
-        st.push(first ? r2c : r1, myd * myd);
-        cur = first ? r1 : r2c;
-        continue;
-      }
-    }
-    // the far child of the innermost open node, if its plane still lies inside closest_d2
-    bool more = false;
-    while (st.sp > 0) {
-      --st.sp;
-      double m2;
-      st.top(cur, m2);
-      if (m2 < best) { more = true; break; }
-    }
-    if (!more) break;
-  }
-}
-
 // first walk of a list query: the length of every list (caller order)
 template <int MODE>
 __global__ void __launch_bounds__(Q_BLOCK) k_shape_count(const QueryArgs a_)
 {
   const QueryArgs& a = q_args();
   __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
-  LaneStackQ<Q_BLOCK, Q_SD> st;
-  stack_init<Q_BLOCK>(st, s_stack, a);
-  const size_t T = (size_t)gridDim.x * Q_BLOCK;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
+    const size_t i = q.i;
     uint32_t c = 0;
     auto emit = [&](const KdPoint&) { ++c; };
-    st.sp = 0;
-    shape_walk<MODE, Q_BLOCK>(a, a.x[i], a.y[i], a.z[i], a.vx[i], a.vy[i], a.vz[i], st, emit);
+    q.st.sp = 0;
+    shape_walk<MODE>(a, a.x[i], a.y[i], a.z[i], a.vx[i], a.vy[i], a.vz[i], q.st, emit);
     a.counts[a.order ? (size_t)a.order[i] : i] = c;
   }
 }
@@ -982,10 +466,8 @@ __global__ void __launch_bounds__(Q_BLOCK) k_shape_fill(const QueryArgs a_)
 {
   const QueryArgs& a = q_args();
   __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
-  LaneStackQ<Q_BLOCK, Q_SD> st;
-  stack_init<Q_BLOCK>(st, s_stack, a);
-  const size_t T = (size_t)gridDim.x * Q_BLOCK;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
+    const size_t i = q.i;
     const size_t o = a.order ? (size_t)a.order[i] : i;
     unsigned long long w = a.offsets[o];
     const unsigned long long end = a.offsets[o + 1];
@@ -993,8 +475,8 @@ __global__ void __launch_bounds__(Q_BLOCK) k_shape_fill(const QueryArgs a_)
       if (w < end) a.idx[w] = p.orig;       // (the count walk made the same visits: never false)
       ++w;
     };
-    st.sp = 0;
-    shape_walk<MODE, Q_BLOCK>(a, a.x[i], a.y[i], a.z[i], a.vx[i], a.vy[i], a.vz[i], st, emit);
+    q.st.sp = 0;
+    shape_walk<MODE>(a, a.x[i], a.y[i], a.z[i], a.vx[i], a.vy[i], a.vz[i], q.st, emit);
   }
 }
 
@@ -1002,135 +484,32 @@ __global__ void __launch_bounds__(Q_BLOCK) k_segment_nearest(const QueryArgs a_)
 {
   const QueryArgs& a = q_args();
   __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
-  LaneStackQ<Q_BLOCK, Q_SD> st;
-  stack_init<Q_BLOCK>(st, s_stack, a);
-  const size_t T = (size_t)gridDim.x * Q_BLOCK;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
+    const size_t i = q.i;
     const size_t o = a.order ? (size_t)a.order[i] : i;
     Segment sg;
     sg.init(a.x[i], a.y[i], a.z[i], a.vx[i], a.vy[i], a.vz[i]);
     const double b0 = __dsqrt_rn(sg.len2) + __dsqrt_rn(a.r2);     // Dist2(p, p0) is Len2(segment_dir), term for term
     double best = b0 * b0;
     uint32_t bslot = 0xFFFFFFFFu;
-    st.sp = 0;
-    segment_nearest_walk<Q_BLOCK>(a, sg, st, best, bslot);
+    q.st.sp = 0;
+    segment_nearest_walk(a, sg, q.st, best, bslot);
     const bool found = bslot != 0xFFFFFFFFu;
     a.idx[o] = found ? a.pts[found ? bslot : 0u].orig : -1;
     if (a.d2) a.d2[o] = found ? best : -1.0;
   }
 }
 
-// ---- collision detection along a trajectory (collision_model.cc) ----------------------------------------------------------
-// A point model moves through the tree's cloud along F frames (4x4, column-major).  Marking: every tree point within the
-// radius of a moved model point (method 1, handle_pointcloud CTYPE1, collision_model.cc:338-367: fixedRangeSearch) or of the
-// segment a model point sweeps between two consecutive frames (method 2, CTYPE2, :368-410: segmentSearch_all) gets a 1 in
-// a byte mask.  Depth along the model's axis (calculate_collidingdist2, :714-800): per (frame, model point) the nearest tree
-// point c1 of the segment from the moved point to its projection on the model's y axis, and every tree point within the
-// radius of c1 takes the minimum of Dist2(moved point, c1).  Both results are sets / minima, so they do not depend on the
-// order of the queries: item i is (frame or segment i / P, model point i % P), generated in the lane -- nothing of size
-// F x P exists anywhere.  The model is uploaded once in spatial order; consecutive lanes take consecutive model points of
-// one frame, and a rigid motion keeps neighbours neighbours, so a wave's lanes walk nearby parts of the tree.  The walks are
-// range_walk, shape_walk<SHAPE_SEGMENT> and segment_nearest_walk as they stand, under emitters that mark or minimise.
-
-// transform3 (globals.icc:1454-1463) of (x, y, z) by the frame T: (x*T0 + y*T4 + z*T8) + T12, and so on
-__device__ __forceinline__ void transform3(const double* T, const double x, const double y, const double z, double& ox,
-                                           double& oy, double& oz)
-{
-  const double xn = x * T[0] + y * T[4] + z * T[8];
-  const double yn = x * T[1] + y * T[5] + z * T[9];
-  const double zn = x * T[2] + y * T[6] + z * T[10];
-  ox = xn + T[12]; oy = yn + T[13]; oz = zn + T[14];
-}
-
-// the marking emitter of both list walks: fill_colliding (collision_model.cc:305-310).  Many lanes may store the same 1 to
-// the same byte: plain stores, no atomics.  Stored without a look at the byte first ("collision": the test
-// costs a dependent load per listed point and saves nothing that was measured)
-struct MarkEmit {
-  uint8_t* mask;
-  __device__ __forceinline__ void operator()(const KdPoint& p) const { mask[p.orig] = 1; }
-  __device__ __forceinline__ void operator()(const KdPoint& p, uint32_t, double) const { mask[p.orig] = 1; }
-};
-
-// the minimising emitter of the depth walk: "if (dist2 < dist[k]) dist[k] = dist2" for every k of the sphere around c1.
-// Non-negative doubles order as their bit patterns do, so the minimum is a 64-bit unsigned atomicMin; the caller passes
-// only d2 < 1000.0 (the entries' initial value), so neither a NaN nor a negative zero's sign bit ever gets in
-struct DepthEmit {
-  unsigned long long* dmin;
-  unsigned long long bits;
-  __device__ __forceinline__ void operator()(const KdPoint& p, uint32_t, double) const { atomicMin(&dmin[p.orig], bits); }
-};
-
-// marking, method 1: item i is model point i % P under frame i / P
-template <int BLOCK>
-__device__ __forceinline__ void collide_sphere_item(const QueryArgs& a, const size_t i, LaneStackQ<BLOCK, Q_SD>& st)
-{
-  const size_t f = i / a.P, m = i - f * a.P;
-  double px, py, pz;
-  transform3(a.frames + 16 * f, a.x[m], a.y[m], a.z[m], px, py, pz);
-  MarkEmit emit{a.mask};
-  st.sp = 0;
-  range_walk<BLOCK>(a, px, py, pz, a.r2, st, emit);
-}
-
-// marking, method 2: item i is the segment model point i % P sweeps from frame i / P to the next one (the reference carries
-// point2 over as the next point1: the same value as transforming afresh).  Two identical frames give p == p0 and nothing
-template <int BLOCK>
-__device__ __forceinline__ void collide_segment_item(const QueryArgs& a, const size_t i, LaneStackQ<BLOCK, Q_SD>& st)
-{
-  const size_t f = i / a.P, m = i - f * a.P;
-  const double x = a.x[m], y = a.y[m], z = a.z[m];
-  double px, py, pz, ex, ey, ez;
-  transform3(a.frames + 16 * f, x, y, z, px, py, pz);
-  transform3(a.frames + 16 * (f + 1), x, y, z, ex, ey, ez);
-  MarkEmit emit{a.mask};
-  st.sp = 0;
-  shape_walk<SHAPE_SEGMENT, BLOCK>(a, px, py, pz, ex, ey, ez, st, emit);
-}
-
-// depth along the model's axis: item i is model point i % P under frame i / P; the tree holds the colliding points only.
-// dist2 = Dist2(point1, pa[c1]) is the walk's closest_d2: the last newdist2 it took, Dist2(p, point) of that very point
-template <int BLOCK>
-__device__ __forceinline__ void collide_depth_axis_item(const QueryArgs& a, const size_t i, LaneStackQ<BLOCK, Q_SD>& st)
-{
-  const size_t f = i / a.P, m = i - f * a.P;
-  const double* T = a.frames + 16 * f;
-  const double y = a.y[m];
-  double px, py, pz, ex, ey, ez;
-  transform3(T, a.x[m], y, a.z[m], px, py, pz);
-  transform3(T, 0.0, y, 0.0, ex, ey, ez);
-  Segment sg;
-  sg.init(px, py, pz, ex, ey, ez);
-  const double b0 = __dsqrt_rn(sg.len2) + __dsqrt_rn(a.r2);
-  double best = b0 * b0;
-  uint32_t bslot = 0xFFFFFFFFu;
-  st.sp = 0;
-  segment_nearest_walk<BLOCK>(a, sg, st, best, bslot);
-  if (bslot == 0xFFFFFFFFu) return;       // found nothing
-  if (!(best < 1000.0)) return;           // no entry is above its initial 1000: the reference's comparison is never true
-  const KdPoint c1 = a.pts[bslot];
-  DepthEmit emit{a.dmin, (unsigned long long)__double_as_longlong(best)};
-  st.sp = 0;
-  range_walk<BLOCK>(a, c1.x, c1.y, c1.z, a.r2, st, emit);
-}
-
-// the last step of the depth: the minimum as the float the reference stored, and its root in float
-__device__ __forceinline__ float collide_depth_value(const unsigned long long bits)
-{
-  const float d2 = (float)__longlong_as_double((long long)bits);
-  return (float)__dsqrt_rn((double)d2);      // == sqrtf(d2): 53 bits are more than twice 24 plus two
-}
-
+// ---- collision detection along a trajectory (the per-item bodies: query_lane.h) ------------------------------------
 template <int METHOD>
 __global__ void __launch_bounds__(Q_BLOCK) k_collide_mark(const QueryArgs a_)
 {
   const QueryArgs& a = q_args();
   __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
-  LaneStackQ<Q_BLOCK, Q_SD> st;
-  stack_init<Q_BLOCK>(st, s_stack, a);
-  const size_t T = (size_t)gridDim.x * Q_BLOCK;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) {
-    if (METHOD == 1) collide_sphere_item<Q_BLOCK>(a, i, st);
-    else collide_segment_item<Q_BLOCK>(a, i, st);
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
+    const size_t i = q.i;
+    if (METHOD == 1) collide_sphere_item(a, i, q.st);
+    else collide_segment_item(a, i, q.st);
   }
 }
 
@@ -1138,10 +517,7 @@ __global__ void __launch_bounds__(Q_BLOCK) k_collide_depth_axis(const QueryArgs 
 {
   const QueryArgs& a = q_args();
   __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
-  LaneStackQ<Q_BLOCK, Q_SD> st;
-  stack_init<Q_BLOCK>(st, s_stack, a);
-  const size_t T = (size_t)gridDim.x * Q_BLOCK;
-  for (size_t i = (size_t)blockIdx.x * Q_BLOCK + threadIdx.x; i < a.n; i += T) collide_depth_axis_item<Q_BLOCK>(a, i, st);
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) collide_depth_axis_item(a, q.i, q.st);
 }
 
 // num_colliding: the set bytes of the mask, one atomic per wave
@@ -1186,130 +562,76 @@ size_t query_overflow_entries(size_t n, uint32_t max_depth)
   return lanes * (size_t)need;
 }
 
+typedef void (*QueryKernel)(const QueryArgs);
+
+static hipError_t launch_q(QueryKernel kernel, const QueryArgs& a, hipStream_t s, int block = Q_BLOCK)
+{
+  hipLaunchKernelGGL(kernel, dim3(q_grid(a.n, block)), dim3(block), 0, s, a);
+  return hipGetLastError();
+}
+
+// the capacity ladder of the three k-NN families: register lists of 4, 10, 20 and 32 slots -- k = 10 (slam6D) and k = 20
+// (calc_normals) get lists of exactly their size -- and the LDS list above them; tab: the family's kernels in that order
+static hipError_t launch_by_capacity(const QueryKernel (&tab)[5], int k, const QueryArgs& a, hipStream_t s)
+{
+  const int rung = k <= 4 ? 0 : k <= 10 ? 1 : k <= 20 ? 2 : k <= 32 ? 3 : 4;
+  return launch_q(tab[rung], a, s, rung < 4 ? Q_BLOCK : Q_BLOCK_L);
+}
+
 hipError_t launch_knn(const QueryArgs& a, bool normals, hipStream_t s)
 {
   if (a.k < 1 || a.k > KNN_MAX_K) return hipErrorInvalidValue;
-  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
-#define KNN_REG(KC)                                                                         \
-  do {                                                                                      \
-    if (normals) hipLaunchKernelGGL((k_knn_reg<KC, true>), g, b, 0, s, a);                  \
-    else hipLaunchKernelGGL((k_knn_reg<KC, false>), g, b, 0, s, a);                         \
-  } while (0)
-  // k = 10 (slam6D) and k = 20 (calc_normals) get lists of exactly their size
-  if (a.k <= 4) KNN_REG(4);
-  else if (a.k <= 10) KNN_REG(10);
-  else if (a.k <= 20) KNN_REG(20);
-  else if (a.k <= 32) KNN_REG(32);
-  else {
-    const dim3 gl(q_grid(a.n, Q_BLOCK_L)), bl(Q_BLOCK_L);
-    if (normals) hipLaunchKernelGGL(k_knn_lds<true>, gl, bl, 0, s, a);
-    else hipLaunchKernelGGL(k_knn_lds<false>, gl, bl, 0, s, a);
-  }
-#undef KNN_REG
-  return hipGetLastError();
+  static const QueryKernel tab[2][5] = {
+      {k_knn_reg<4, false>, k_knn_reg<10, false>, k_knn_reg<20, false>, k_knn_reg<32, false>, k_knn_lds<false>},
+      {k_knn_reg<4, true>, k_knn_reg<10, true>, k_knn_reg<20, true>, k_knn_reg<32, true>, k_knn_lds<true>}};
+  return launch_by_capacity(tab[normals], a.k, a, s);
 }
 
 hipError_t launch_knn_range(const QueryArgs& a, bool normals, hipStream_t s)
 {
   if (a.k < 1 || a.k > KNN_MAX_K) return hipErrorInvalidValue;
-  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
-#define KNNR_REG(KC)                                                                        \
-  do {                                                                                      \
-    if (normals) hipLaunchKernelGGL((k_knnr_reg<KC, true>), g, b, 0, s, a);                 \
-    else hipLaunchKernelGGL((k_knnr_reg<KC, false>), g, b, 0, s, a);                        \
-  } while (0)
-  // launch_knn's capacities
-  if (a.k <= 4) KNNR_REG(4);
-  else if (a.k <= 10) KNNR_REG(10);
-  else if (a.k <= 20) KNNR_REG(20);
-  else if (a.k <= 32) KNNR_REG(32);
-  else {
-    const dim3 gl(q_grid(a.n, Q_BLOCK_L)), bl(Q_BLOCK_L);
-    if (normals) hipLaunchKernelGGL(k_knnr_lds<true>, gl, bl, 0, s, a);
-    else hipLaunchKernelGGL(k_knnr_lds<false>, gl, bl, 0, s, a);
-  }
-#undef KNNR_REG
-  return hipGetLastError();
+  static const QueryKernel tab[2][5] = {
+      {k_knnr_reg<4, false>, k_knnr_reg<10, false>, k_knnr_reg<20, false>, k_knnr_reg<32, false>, k_knnr_lds<false>},
+      {k_knnr_reg<4, true>, k_knnr_reg<10, true>, k_knnr_reg<20, true>, k_knnr_reg<32, true>, k_knnr_lds<true>}};
+  return launch_by_capacity(tab[normals], a.k, a, s);
 }
 
 hipError_t launch_knn_adaptive(const QueryArgs& a, hipStream_t s)
 {
   if (a.kmin < 0 || a.kmin > a.kmax || a.kmax + 1 > KNN_MAX_K) return hipErrorInvalidValue;
-  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
-  const int k = a.kmax + 1;      // the capacities of launch_knn, by the longest list
-  if (k <= 4) hipLaunchKernelGGL(k_knn_adaptive_reg<4>, g, b, 0, s, a);
-  else if (k <= 10) hipLaunchKernelGGL(k_knn_adaptive_reg<10>, g, b, 0, s, a);
-  else if (k <= 20) hipLaunchKernelGGL(k_knn_adaptive_reg<20>, g, b, 0, s, a);
-  else if (k <= 32) hipLaunchKernelGGL(k_knn_adaptive_reg<32>, g, b, 0, s, a);
-  else hipLaunchKernelGGL(k_knn_adaptive_lds, dim3(q_grid(a.n, Q_BLOCK_L)), dim3(Q_BLOCK_L), 0, s, a);
-  return hipGetLastError();
+  static const QueryKernel tab[5] = {k_knn_adaptive_reg<4>, k_knn_adaptive_reg<10>, k_knn_adaptive_reg<20>,
+                                     k_knn_adaptive_reg<32>, k_knn_adaptive_lds};
+  return launch_by_capacity(tab, a.kmax + 1, a, s);      // by the longest list
 }
 
-hipError_t launch_range_count(const QueryArgs& a, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_range_count, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
-  return hipGetLastError();
-}
+hipError_t launch_range_count(const QueryArgs& a, hipStream_t s) { return launch_q(k_range_count, a, s); }
+hipError_t launch_range_fill(const QueryArgs& a, hipStream_t s) { return launch_q(k_range_fill, a, s); }
+hipError_t launch_range_normals(const QueryArgs& a, hipStream_t s) { return launch_q(k_range_normals, a, s); }
+hipError_t launch_segment_nearest(const QueryArgs& a, hipStream_t s) { return launch_q(k_segment_nearest, a, s); }
 
-hipError_t launch_range_fill(const QueryArgs& a, hipStream_t s)
+// the count (fill = false) or fill walk of list query `mode` (ShapeMode)
+static hipError_t launch_shape(bool fill, int mode, const QueryArgs& a, hipStream_t s)
 {
-  hipLaunchKernelGGL(k_range_fill, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
-  return hipGetLastError();
+  static const QueryKernel tab[2][4] = {
+      {k_shape_count<SHAPE_ALONG_DIR>, k_shape_count<SHAPE_BETWEEN>, k_shape_count<SHAPE_AABB>, k_shape_count<SHAPE_SEGMENT>},
+      {k_shape_fill<SHAPE_ALONG_DIR>, k_shape_fill<SHAPE_BETWEEN>, k_shape_fill<SHAPE_AABB>, k_shape_fill<SHAPE_SEGMENT>}};
+  if (mode < SHAPE_ALONG_DIR || mode > SHAPE_SEGMENT) return hipErrorInvalidValue;
+  return launch_q(tab[fill][mode], a, s);
 }
-
-hipError_t launch_range_normals(const QueryArgs& a, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_range_normals, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_shape_count(const QueryArgs& a, int mode, hipStream_t s)
-{
-  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
-  switch (mode) {
-    case SHAPE_ALONG_DIR: hipLaunchKernelGGL(k_shape_count<SHAPE_ALONG_DIR>, g, b, 0, s, a); break;
-    case SHAPE_BETWEEN: hipLaunchKernelGGL(k_shape_count<SHAPE_BETWEEN>, g, b, 0, s, a); break;
-    case SHAPE_AABB: hipLaunchKernelGGL(k_shape_count<SHAPE_AABB>, g, b, 0, s, a); break;
-    case SHAPE_SEGMENT: hipLaunchKernelGGL(k_shape_count<SHAPE_SEGMENT>, g, b, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_shape_fill(const QueryArgs& a, int mode, hipStream_t s)
-{
-  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
-  switch (mode) {
-    case SHAPE_ALONG_DIR: hipLaunchKernelGGL(k_shape_fill<SHAPE_ALONG_DIR>, g, b, 0, s, a); break;
-    case SHAPE_BETWEEN: hipLaunchKernelGGL(k_shape_fill<SHAPE_BETWEEN>, g, b, 0, s, a); break;
-    case SHAPE_AABB: hipLaunchKernelGGL(k_shape_fill<SHAPE_AABB>, g, b, 0, s, a); break;
-    case SHAPE_SEGMENT: hipLaunchKernelGGL(k_shape_fill<SHAPE_SEGMENT>, g, b, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_segment_nearest(const QueryArgs& a, hipStream_t s)
-{
-  hipLaunchKernelGGL(k_segment_nearest, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
-  return hipGetLastError();
-}
+hipError_t launch_shape_count(const QueryArgs& a, int mode, hipStream_t s) { return launch_shape(false, mode, a, s); }
+hipError_t launch_shape_fill(const QueryArgs& a, int mode, hipStream_t s) { return launch_shape(true, mode, a, s); }
 
 hipError_t launch_collide_mark(const QueryArgs& a, int cmethod, hipStream_t s)
 {
   if (!a.n) return hipSuccess;
-  const dim3 g(q_grid(a.n, Q_BLOCK)), b(Q_BLOCK);
-  if (cmethod == 1) hipLaunchKernelGGL(k_collide_mark<1>, g, b, 0, s, a);
-  else if (cmethod == 2) hipLaunchKernelGGL(k_collide_mark<2>, g, b, 0, s, a);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  if (cmethod != 1 && cmethod != 2) return hipErrorInvalidValue;
+  return launch_q(cmethod == 1 ? k_collide_mark<1> : k_collide_mark<2>, a, s);
 }
 
 hipError_t launch_collide_depth_axis(const QueryArgs& a, hipStream_t s)
 {
   if (!a.n) return hipSuccess;
-  hipLaunchKernelGGL(k_collide_depth_axis, dim3(q_grid(a.n, Q_BLOCK)), dim3(Q_BLOCK), 0, s, a);
-  return hipGetLastError();
+  return launch_q(k_collide_depth_axis, a, s);
 }
 
 hipError_t launch_collide_count(const uint8_t* mask, size_t M, unsigned long long* count, hipStream_t s)
@@ -1348,3 +670,4 @@ hipError_t launch_range_scan(const uint32_t* counts, unsigned long long* offsets
 }
 
 }  // namespace tdtk
+

@@ -11,6 +11,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_lane
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
 
@@ -224,50 +226,12 @@ def test_collision_kernels_spill_nothing():
 
 
 # ---- the per-lane device code on the host ----------------------------------------------------------------------------
-# the walks, the emitters and the three per-lane bodies of the collision kernels as they stand in query.hip (cut out between
-# the comments that open them), with __device__ defined away, a std::vector for the lane stack, a plain minimum for the atomic
-# and kd_build.cpp's host tree under them.  The model is taken in the caller's order: the results do not depend on it
+# the walks, the emitters and the three per-lane bodies of the collision kernels as they stand in query_lane.h
+# (host_lane_shim.h: __device__ defined away, a std::vector for the lane stack, a plain minimum for the atomic), with
+# kd_build.cpp's host tree under them.  The model is taken in the caller's order: the results do not depend on it
 _HOST_LANE = r"""
-#include <cmath>
-#include <cstdint>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-#include "tdtk_hip.h"
-#include "tdtk_internal.h"
-#define __device__
-#define __forceinline__ inline
-static inline double __dsqrt_rn(double x) { return std::sqrt(x); }
-static inline long long __double_as_longlong(double x) { long long v; std::memcpy(&v, &x, 8); return v; }
-static inline double __longlong_as_double(long long v) { double x; std::memcpy(&x, &v, 8); return x; }
-static inline unsigned long long atomicMin(unsigned long long* p, unsigned long long v)
-{ const unsigned long long o = *p; if (v < o) *p = v; return o; }
-namespace tdtk {
-constexpr int Q_SD = 16;
-enum ShapeMode { SHAPE_ALONG_DIR = 0, SHAPE_BETWEEN = 1, SHAPE_AABB = 2, SHAPE_SEGMENT = 3 };
-struct QueryArgs {
-  const KdNode* nodes; const KdPoint* pts; const LeafEntry* leaf_tab; uint32_t root_ref, cb, cmask;
-  const double *x, *y, *z; size_t n; double r2; const double* node_r;
-  const double* frames; size_t P; uint8_t* mask; unsigned long long* dmin;
-};
-template <int BLOCK, int SD> struct LaneStackQ {
-  std::vector<uint32_t> v; std::vector<double> w; int sp = 0;
-  void push(uint32_t r, double m) { if ((int)v.size() <= sp) { v.resize(sp + 1); w.resize(sp + 1); } v[sp] = r; w[sp] = m; ++sp; }
-  void top(uint32_t& r, double& m) const { r = v[sp]; m = w[sp]; }
-};
-@@CUT@@
-}
-using namespace tdtk;
-extern "C" void* hl_create(const double* xyz, size_t n, int bucket) {
-  HostTree* T = new HostTree; std::string err;
-  if (!build_tree(xyz, n, bucket, *T, err)) return nullptr;
-  return T;
-}
-extern "C" void hl_destroy(void* p) { delete (HostTree*)p; }
 static QueryArgs args_of(HostTree& T, const std::vector<double>* soa, size_t P, const double* frames, double radius) {
-  QueryArgs a{}; a.nodes = T.nodes.data(); a.pts = T.pts.data(); a.leaf_tab = T.table_mode ? T.leaf_tab.data() : nullptr;
-  a.root_ref = T.root_ref; a.cb = T.cb; a.cmask = (1u << T.cb) - 1; a.node_r = T.node_r.data();
+  QueryArgs a = host_args(T);
   a.x = soa[0].data(); a.y = soa[1].data(); a.z = soa[2].data(); a.P = P; a.frames = frames; a.r2 = radius * radius;
   return a;
 }
@@ -280,10 +244,10 @@ extern "C" void hl_mark(void* p, const double* model, size_t P, const double* fr
   std::vector<double> soa[3]; split(model, P, soa);
   QueryArgs a = args_of(T, soa, P, frames, radius);
   a.mask = mask; a.n = (cmethod == 1 ? F : F - 1) * P;
-  LaneStackQ<1, Q_SD> st;
+  HostStack st;
   for (size_t i = 0; i < a.n; i++) {
-    if (cmethod == 1) collide_sphere_item<1>(a, i, st);
-    else collide_segment_item<1>(a, i, st);
+    if (cmethod == 1) collide_sphere_item(a, i, st);
+    else collide_segment_item(a, i, st);
   }
 }
 extern "C" void hl_depth_axis(void* p, size_t nc, const double* model, size_t P, const double* frames, size_t F, double radius,
@@ -293,8 +257,8 @@ extern "C" void hl_depth_axis(void* p, size_t nc, const double* model, size_t P,
   QueryArgs a = args_of(T, soa, P, frames, radius);
   std::vector<unsigned long long> dmin(nc, (unsigned long long)__double_as_longlong(1000.0));
   a.dmin = dmin.data(); a.n = F * P;
-  LaneStackQ<1, Q_SD> st;
-  for (size_t i = 0; i < a.n; i++) collide_depth_axis_item<1>(a, i, st);
+  HostStack st;
+  for (size_t i = 0; i < a.n; i++) collide_depth_axis_item(a, i, st);
   for (size_t i = 0; i < nc; i++) dist[i] = collide_depth_value(dmin[i]);
 }
 """
@@ -303,30 +267,7 @@ extern "C" void hl_depth_axis(void* p, size_t nc, const double* model, size_t P,
 def test_device_lane_code_compiled_for_the_host_equals_the_fixture(mg, fx, tmp_path):
     """masks of both methods and the axis depth on every small case.  (The closest depth adds no per-lane code: it is the
     FindClosest batch search and (float)sqrt, which test_depths_of_the_fixture restates by brute force.)"""
-    csrc = os.path.join(ROOT, "3dtk_amd", "csrc")
-    src = open(os.path.join(csrc, "query.hip")).read()
-
-    def cut(start, end):
-        a = src.index(start)
-        return src[a:src.index(end, a)]
-
-    parts = [cut("// one node's box test", "template <int BLOCK>\n__device__ __forceinline__ void stack_init"),
-             cut("// EMIT(point, slot, d2) for every point of the radius list", "// k nearest within r2 (_KNNRangeSearch)"),
-             cut("// the segment of the two segment queries", "// first walk of a list query"),
-             cut("// transform3 (globals.icc:1454-1463)", "template <int METHOD>\n__global__")]
-    assert "range_walk" in parts[1] and "segment_nearest_walk" in parts[2] and "shape_walk" in parts[2]
-    for f in ("collide_sphere_item", "collide_segment_item", "collide_depth_axis_item", "collide_depth_value", "DepthEmit"):
-        assert f in parts[3], f
-    (tmp_path / "hl.cc").write_text(_HOST_LANE.replace("@@CUT@@", "\n".join(parts)))
-    so = str(tmp_path / "libhl.so")
-    r = subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + csrc, str(tmp_path / "hl.cc"), os.path.join(csrc, "kd_build.cpp"), "-o", so],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    L = C.CDLL(so)
-    L.hl_create.restype = C.c_void_p
-    L.hl_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
-    L.hl_destroy.argtypes = [C.c_void_p]
+    L = host_lane.build(_HOST_LANE, tmp_path, "hl")
     L.hl_mark.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p]
     L.hl_depth_axis.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p]
     n = 0
@@ -334,7 +275,7 @@ def test_device_lane_code_compiled_for_the_host_equals_the_fixture(mg, fx, tmp_p
         pts, model, frames, radius = mg.small_case(name)
         pts, model, frames = (np.ascontiguousarray(a) for a in (pts, model, frames))
         for b in mg.BUCKETS:
-            h = L.hl_create(pts.ctypes.data, len(pts), b)
+            h = L.host_tree_create(pts.ctypes.data, len(pts), b)
             assert h
             for cm in mg.METHODS:
                 key = "%s_b%d_m%d" % (name, b, cm)
@@ -343,13 +284,13 @@ def test_device_lane_code_compiled_for_the_host_equals_the_fixture(mg, fx, tmp_p
                 assert np.array_equal(mask.astype(bool), fx.mask(key, len(pts))), key
                 if name not in mg.NO_DEPTH:
                     hit = np.ascontiguousarray(pts[mask.astype(bool)])
-                    hh = L.hl_create(hit.ctypes.data, len(hit), b)
+                    hh = L.host_tree_create(hit.ctypes.data, len(hit), b)
                     assert hh
                     d2 = np.empty(len(hit), np.float32)
                     L.hl_depth_axis(hh, len(hit), model.ctypes.data, len(model), frames.ctypes.data, len(frames), radius,
                                     d2.ctypes.data)
-                    L.hl_destroy(hh)
+                    L.host_tree_destroy(hh)
                     assert np.array_equal(d2, fx.z[key + "_d2"]), key
                 n += 1
-            L.hl_destroy(h)
+            L.host_tree_destroy(h)
     assert n == 6 * 3 * 2

@@ -6,10 +6,11 @@ import ctypes as C
 import importlib.util
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
+
+import host_lane
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
@@ -178,44 +179,17 @@ def test_knn_range_kernels_spill_nothing():
 
 
 # ---- the device walk on the host -----------------------------------------------------------------------------------
-# knn_range_walk, the LDS list and the helpers they call, as they stand in query.hip (cut out between the comments that
-# open them), with __device__ defined away, a std::vector for the lane stack and kd_build.cpp's host tree under them
+# knn_range_walk, the LDS list and the helpers they call, as they stand in query_lane.h (host_lane_shim.h: __device__ defined
+# away, a std::vector for the lane stack), with kd_build.cpp's host tree under them
 _HOST_WALK = r"""
-#include <cmath>
-#include <cstdint>
-#include <cstdlib>
-#include <string>
-#include <vector>
-#include "tdtk_hip.h"
-#include "tdtk_internal.h"
-#define __device__
-#define __forceinline__ inline
-namespace tdtk {
-constexpr int Q_SD = 16;
-struct QueryArgs { const KdNode* nodes; const KdPoint* pts; const LeafEntry* leaf_tab; uint32_t root_ref, cb, cmask; };
-template <int BLOCK, int SD> struct LaneStackQ {
-  std::vector<uint32_t> v; int sp = 0;
-  void push(uint32_t r, double) { if ((int)v.size() <= sp) v.resize(sp + 1); v[sp++] = r; }
-  void top(uint32_t& r, double& m) { r = v[sp]; m = 0; }
-};
-@@CUT@@
-}
-using namespace tdtk;
-extern "C" void* hw_create(const double* xyz, size_t n, int bucket) {
-  HostTree* T = new HostTree; std::string err;
-  if (!build_tree(xyz, n, bucket, *T, err)) return nullptr;
-  return T;
-}
-extern "C" void hw_destroy(void* p) { delete (HostTree*)p; }
 extern "C" void hw_search(void* p, const double* q, int nq, int k, double r2, int* idx, double* d2, int* cnt) {
   HostTree& T = *(HostTree*)p;
-  QueryArgs a; a.nodes = T.nodes.data(); a.pts = T.pts.data(); a.leaf_tab = T.table_mode ? T.leaf_tab.data() : nullptr;
-  a.root_ref = T.root_ref; a.cb = T.cb; a.cmask = (1u << T.cb) - 1;
+  QueryArgs a = host_args(T);
   std::vector<double> ld(64); std::vector<uint32_t> ls(64);
   for (int i = 0; i < nq; i++) {
     ListLds<1> L; L.ld = ld.data(); L.ls = ls.data(); L.init(k);
-    LaneStackQ<1, Q_SD> st;
-    knn_range_walk<1>(a, q[3 * i], q[3 * i + 1], q[3 * i + 2], r2, L, st);
+    HostStack st;
+    knn_range_walk(a, q[3 * i], q[3 * i + 1], q[3 * i + 2], r2, L, st);
     int nr = 0;
     for (int j = 0; j < k; j++) nr += (L.dist(j) >= 0.0) ? 1 : 0;
     cnt[i] = nr;
@@ -226,33 +200,13 @@ extern "C" void hw_search(void* p, const double* q, int nq, int k, double r2, in
 
 
 def test_device_walk_compiled_for_the_host_equals_the_fixture(mr, fx, tmp_path):
-    csrc = os.path.join(ROOT, "3dtk_amd", "csrc")
-    src = open(os.path.join(csrc, "query.hip")).read()
-
-    def cut(start, end):
-        a = src.index(start)
-        return src[a:src.index(end, a)]
-
-    parts = [cut("// one node's box test", "template <int BLOCK>\n__device__ __forceinline__ void stack_init"),
-             cut("// in LDS, [slot][lane]", "// ---- the walks"),
-             cut("// k nearest within r2 (_KNNRangeSearch)", "// calculateNormal (normals.cc:518-558) over a list")]
-    assert "knn_range_walk" in parts[2] and "struct ListLds" in parts[1] and "box_dist" in parts[0]
-    (tmp_path / "hw.cc").write_text(_HOST_WALK.replace("@@CUT@@", "\n".join(parts)))
-    so = str(tmp_path / "libhw.so")
-    r = subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + csrc, str(tmp_path / "hw.cc"), os.path.join(csrc, "kd_build.cpp"), "-o", so],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    L = C.CDLL(so)
-    L.hw_create.restype = C.c_void_p
-    L.hw_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
-    L.hw_destroy.argtypes = [C.c_void_p]
+    L = host_lane.build(_HOST_WALK, tmp_path, "hw")
     L.hw_search.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
     n = 0
     for name, (pts, Q, no, _) in mr.G8.k8_clouds().items():
         pts, Q = np.ascontiguousarray(pts), np.ascontiguousarray(Q)
         for b in mr.BUCKETS:
-            h = L.hw_create(pts.ctypes.data, len(pts), b)
+            h = L.host_tree_create(pts.ctypes.data, len(pts), b)
             assert h
             for ri, r2 in enumerate(fx.radii(name)):
                 for k in mr.KS:
@@ -263,5 +217,5 @@ def test_device_walk_compiled_for_the_host_equals_the_fixture(mr, fx, tmp_path):
                     assert np.array_equal(have, rep >= 0) and np.array_equal(pts[idx[have]], pts[rep[have]]), (name, b, ri, k)
                     assert np.array_equal(d2, np.where(have, _d2(mr, pts, Q, idx), -1.0)), (name, b, ri, k)
                     n += 1
-            L.hw_destroy(h)
+            L.host_tree_destroy(h)
     assert n == 7 * 3 * 3 * len(mr.KS)
