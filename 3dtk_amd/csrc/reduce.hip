@@ -3,7 +3,9 @@
 // The reference builds a pointer octree over the scan (BOctTree constructor,
 // include/slam6d/Boctree.h:222-270: cubic root box = bbox centre, half size = largest half extent
 // + 1.0), splits a cell into its occupied octants while its half size is > voxelSize
-// (branch, :1163-1195; child index = (x > cx) | (y > cy) << 1 | (z > cz) << 2, :1353-1355; child
+// (branch, :1163-1195; child index = !(x < cx) | !(y < cy) << 1 | !(z < cz) << 2: the array constructor
+// Scan::calcReducedPoints uses cuts with `p < centre` | `p >= centre`, fullsort / sort, :1737-1816, so a point on a
+// centre plane goes up -- not childIndex's strict `>`, :1353-1355, which the searches use; child
 // centre = parent centre -/+ size/2 per axis, :612-657) and emits the centre of every leaf cell
 // in depth-first child order (GetOctTreeCenter, :928-948).  Scan::calcReducedPoints
 // (src/slam6d/scan.cc:577-603) stores those centres as "xyz reduced".

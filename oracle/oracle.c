@@ -17,8 +17,8 @@
  * own translation units (kdIndexed.cc and the minimizer TUs) built by
  * oracle/build_ref.sh into oracle/_ref/, against the known-answer tests of
  * testing/kdtree/, and against the committed fixtures under tests/golden/.
- * PARITY UNPINNED for orc_octree_center (Boctree.h cannot be compiled here; see
- * the comment at that function).
+ * PINNED too for orc_octree_center / orc_octree_random: against the reference's own BOctTree<double>, compiled by
+ * tests/golden/make_golden_octree.py (see the comment at orc_octree_center).
  */
 #include <math.h>
 #include <stdint.h>
@@ -565,9 +565,15 @@ uint64_t orc_k5_hash(const int32_t *idx, size_t n)
 }
 
 /* ---- octree reduction, centre mode ("-r <voxelSize>") -------------------------------------
- * PARITY UNPINNED: include/slam6d/Boctree.h needs boost/interprocess/offset_ptr.hpp, which this
- * image does not have, so the reference octree cannot be compiled into oracle/_ref and the
- * reference holds no golden vector for it.  This is a restatement by reading:
+ * PINNED by tests/golden/k14_octree.npz and its generator tests/golden/make_golden_octree.py, which compiles the
+ * reference's Boctree.cc and allocator.cc where they lie and runs BOctTree<double> as Scan::calcReducedPoints does
+ * (tests/test_octree_reference_host.py: this file against the fixture and against the live class, bit for bit).
+ * include/slam6d/Boctree.h needs boost/interprocess/offset_ptr.hpp, which this image does not have; the generator's
+ * temporary build gives it a stand-in of ours (a raw pointer in the wrapper's clothes: the six members it types only
+ * address the tree, no arithmetic goes through them) and our own bodies for PointType's default constructor and
+ * getPointDim() (xyz only, 3) and for SearchTree's three out-of-line virtuals (never called).  oracle/_ref still holds
+ * no stand-in.  GetOctTreeAvg (nrpts == -1) and rm_scatter stay refused by the product and therefore unpinned.
+ * This is a restatement by reading:
  *   BOctTree(P* const* pts, int n, T voxelSize)   Boctree.h:222-270  (root cube: bbox centre,
  *       half size = largest half extent + 1.0; the root is always split)
  *   countPointsAndQueueFast / branch              Boctree.h:1163-1195, 1268-1300 (occupied octants in
@@ -656,7 +662,8 @@ size_t orc_octree_center(const double *xyz, size_t n, double voxel, double *out)
 }
 
 /* ---- octree reduction, random modes ("-r <voxelSize> -O <nrpts>", nrpts >= 1) ------------------------------------
- * PARITY UNPINNED (Boctree.h cannot be compiled here, see above).  Restatement by reading, structured like the
+ * PINNED like the centre mode (see above): the leaf order by the fixture's `leaf` rows, which need no rand(), the draws
+ * by its `d1` / `d3` rows.  Restatement by reading, structured like the
  * reference: an array of point pointers (here: indices) partitioned IN PLACE,
  *   fullsort                Boctree.h:1737-1780: z, then y inside each z half, then x inside each quarter
  *   sort                    Boctree.h:1784-1816: the two-pointer partition as written (`< splitval` | `>= splitval`)

@@ -357,7 +357,8 @@ def k5_hash(idx):
 
 
 def octree_center(xyz, voxel):
-    """Octree-centre reduction (parity unpinned, see oracle.c); returns [cells, 3] in DFS order."""
+    """Octree-centre reduction (GetOctTreeCenter; pinned to the reference's compiled BOctTree<double> by
+    tests/golden/k14_octree.npz, see oracle.c); returns [cells, 3] in DFS order."""
     xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
     out = np.empty_like(xyz)
     m = lib().orc_octree_center(_d(xyz), len(xyz), float(voxel), _d(out))
@@ -365,7 +366,8 @@ def octree_center(xyz, voxel):
 
 
 def octree_random(xyz, voxel, nrpts, seed=None, want_perm=False):
-    """Octree reduction with `-O nrpts` (nrpts >= 1; parity unpinned, see oracle.c): the kept points in DFS order.
+    """Octree reduction with `-O nrpts` (nrpts >= 1, GetOctTreeRandom; pinned to the reference's compiled BOctTree<double> by
+    tests/golden/k14_octree.npz, see oracle.c): the kept points in DFS order.
     seed: srand(seed) of the C library first (the reference draws std::rand())."""
     xyz = np.ascontiguousarray(xyz, np.float64).reshape(-1, 3)
     out = np.empty_like(xyz)

@@ -643,7 +643,7 @@ def test_scan_io_uos_pose_frames(tdtk, tmp_path):
 
 
 def test_oracle_octree_random_modes_against_cell_membership(orc):
-    """The restatement of the random octree modes (oracle.c, parity unpinned) checked against what does not depend on how
+    """The restatement of the random octree modes (oracle.c; pinned to the reference by test_octree_reference_host.py) checked against what does not depend on how
     the partitions are written: the order the partitions leave behind groups the points by leaf in the depth-first order
     of the centre mode, every leaf contributes exactly one point (nrpts = 1) resp. min(nrpts, length) points (the
     reference draws rand(length - 1) there, so a leaf's LAST point is only ever kept when the whole leaf is), and each
@@ -690,7 +690,7 @@ def test_oracle_octree_random_modes_against_cell_membership(orc):
 
 
 def test_oracle_octree_center_against_grid_formulation(orc):
-    """The recursive octree restatement (oracle.c, parity unpinned: Boctree.h is not buildable here)
+    """The recursive octree restatement (oracle.c; pinned to the reference by test_octree_reference_host.py)
     checked against an independent closed-form formulation: occupied cells of the regular 2^D grid over
     the root cube, ordered by their (x lowest) Morton code = depth-first child order."""
     rng = np.random.default_rng(11)
