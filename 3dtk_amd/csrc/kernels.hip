@@ -9,7 +9,9 @@
 // configurations of the kernels below (lab_launch.inc).
 //   search, three families by batch size (launch_search picks; each has a COUNT instantiation that tallies the visits):
 //     k_search_refill  persistent lanes, from 256K queries: a wave owns a slab of sorted queries, a lane that finishes takes the
-//                      next one.  Configured by one type (RefillCfg; the product's: SinglePass).
+//                      next one.  Configured by one type (RefillCfg; the product's: SinglePass).  Its repeated passes (DEFER) walk in
+//                      one mode -- no quick check on a divergent visit -- and search the few queries that accepted a point thinly
+//                      again behind the slab, as the reference walks them (kd_search_plain).
 //     k_search         one query per lane, 96K..256K queries: near-first DFS, per-lane stack in LDS (+ HBM overflow); also FindClosestAlongDir (DIRMODE)
 //     k_search_g8      four lanes per query, below 96K queries
 //     k_search_refill_multi (LinkPass), k_search_multi, k_search_g8_multi: several batches (a graph-SLAM round's links) in one launch
@@ -688,6 +690,68 @@ __device__ __forceinline__ void kd_search(const TreeDev& T, const double qx, con
     atomicAdd(&cnt[0], (unsigned long long)c_int);
     atomicAdd(&cnt[1], (unsigned long long)c_leaf);
     atomicAdd(&cnt[2], (unsigned long long)c_pts);
+  }
+}
+
+// The same walk as plain as it gets, for one lane on its own: the exact fp64 box test on the full 64-byte node record (no fp32
+// shortcut to argue about), one bucket point per trip, strict `<` in stored order.  The persistent-lane kernel's DEFER passes run
+// it behind a slab for the few queries they search a second time; it is written to need few registers, not to be fast.
+// n_int / n_leaf / n_pts: node visits, buckets and bucket points, added to.  bk is the point's position in T.pts, like everywhere.
+template <class STK>
+__device__ __forceinline__ void kd_search_plain(const char* nodes, const char* pb, const LeafEntry* leaf_tab, const uint32_t cb,
+                                                const uint32_t cmask, const uint32_t root_ref, const double qx, const double qy,
+                                                const double qz, double& best, int& bk, STK& st, unsigned& n_int, unsigned& n_leaf,
+                                                unsigned& n_pts)
+{
+  uint32_t cur = root_ref;
+  st.sp = 0;
+  for (;;) {
+    while (!(cur & REF_LEAF)) {
+      ++n_int;
+      const uint32_t no = (uint32_t)((cur & REF_VAL) << 6);
+      const double4 n0 = gload<double4>(nodes, no);            // cx cy cz hx
+      const double4 n1 = gload<double4>(nodes, no + 32);       // hy hz splitval { c1, c2 }
+      uint32_t next = REF_DONE;
+      if (!box_prunes_exact(n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, qx, qy, qz, best)) {
+        const uint32_t c1b = (uint32_t)__double2loint(n1.w), c2b = (uint32_t)__double2hiint(n1.w);
+        next = descend_ax(n1.z, c1b, c2b, ((c1b >> 30) & 1u) | (((c2b >> 30) & 1u) << 1), qx, qy, qz, best, st);
+      } else {
+        while (st.sp > 0) {
+          --st.sp;
+          uint32_t r; double m2;
+          st.top(r, m2);
+          if (m2 < best) { next = r; break; }
+        }
+      }
+      cur = next;
+    }
+    if (cur == REF_DONE) break;
+    const uint32_t v = cur & REF_VAL;
+    int start, count;
+    if (leaf_tab) {
+      const LeafEntry le = leaf_tab[v];
+      start = le.start; count = le.count;
+    } else {
+      start = (int)(v >> cb);
+      count = (int)(v & cmask);
+    }
+    ++n_leaf; n_pts += (unsigned)count;
+    for (int i = 0; i < count; i++) {
+      const uint32_t o = (uint32_t)(start + i) << 5;
+      const double2 pxy = gload<double2>(pb, o);
+      const double pz = gload<double>(pb, o + 16);
+      const double dx = pxy.x - qx, dy = pxy.y - qy, dz = pz - qz;
+      const double d = dx * dx + dy * dy + dz * dz;
+      if (d < best) { best = d; bk = start + i; }
+    }
+    cur = REF_DONE;
+    while (st.sp > 0) {
+      --st.sp;
+      uint32_t r; double m2;
+      st.top(r, m2);
+      if (m2 < best) { cur = r; break; }
+    }
+    if (cur == REF_DONE) break;
   }
 }
 
@@ -1530,11 +1594,14 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   // (the single-pass kernel only: the several-links launch -- LAZY, 118-120 VGPRs with either filter, four waves per SIMD, its
   // vector ALUs busier -- is SLOWER with it: 84 links 9.9 -> 10.8 ms, six links of 10M queries 11.6 -> 12.6; gpurun_out/r5g)
   constexpr bool USE_Q16 = BUCKET_Q16 && !LAZY;
+  // (DEFER, below: launched only over a tree that has the split halves and the 16-bit shadow -- launch_refill128 -- so that
+  // instantiation does not carry the "is there a shadow" answer around its loop)
+  constexpr bool DEFER_OK = DEFER && USE_Q16 && !FAT && !PIPE && TOP == 0 && PROBE == 0;
   uint32_t q16xy = 0u, q16zz = 0u;
   bool q16in = false;
   const char* const t_q16 = USE_Q16 ? reinterpret_cast<const char*>(T.q16) : nullptr;
   auto q16_query = [&]() {
-    if (USE_Q16 && t_q16) {
+    if (USE_Q16 && (DEFER_OK || t_q16)) {
       const SearchArgs* ap = &a;
       asm volatile("" : "+s"(ap));      // (read where a lane takes a query, like the matrices: not hoisted, not kept live)
       bool out = false;
@@ -1547,26 +1614,36 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   };
   const char* __restrict__ hotb = reinterpret_cast<const char*>(T.hot);
   // ---- the quick check deferred (round 5) ----
-  // A query that starts from a previous hit (SearchArgs::warm, tie > 0) makes its DIVERGENT visits without the quick check of
-  // kdTreeImpl.h:360-368: 16 bytes { splitval, children } instead of the 48-byte record, one load instead of three.  What it
-  // walks is the reference's walk plus subtrees the reference would have cut off there; the order is the reference's, a point
-  // of such a subtree lies at d2 >= closest_d2 - tie by the very test that was skipped (tie bounds 2 E R + E^2, E the rounding of
+  // EVERY query of a repeated pass (SearchArgs::warm, tie > 0: the DEFER instantiation) makes its DIVERGENT visits without the
+  // quick check of kdTreeImpl.h:360-368: 16 bytes { splitval, children } instead of the 48-byte record, one load instead of
+  // three, one mode for all 64 lane slots (the L1 charges a wave instruction by its bytes per lane whatever its mask: as a
+  // per-lane mode -- round 5 -- one checking lane made its whole wave issue three loads per trip).  What a lane walks is the
+  // reference's walk plus subtrees the reference would have cut off there; the order is the reference's, a point of such a
+  // subtree lies at d2 >= closest_d2 - tie by the very test that was skipped (tie bounds 2 E R + E^2, E the rounding of
   // fabs(q - center) - half-width against the exact face distance, R the search radius: api.cpp, search_tie), and the strict
   // `<` never takes an equal one.  So as long as no accepted point improved closest_d2 by `tie` or less -- `thin` -- every
-  // acceptance is one the reference makes, in its order: same index, same d2, same ties.  A query that did accept thinly is
-  // searched again when it retires, cold and with every check: the reference's own walk.  (A deferring lane skips the check in
-  // wave-uniform visits too; lanes that make it -- no previous hit -- make it everywhere.)  The warm radius is the previous hit's
-  // d2 + 2 tie, so that finding that very point again is not thin.  Measured with six waves per SIMD, 1M-vs-1M at the driver's
-  // arguments: k_search 0.1665 -> 0.157 ms; 21.4 -> 21.7 node visits, 2.77 -> 3.12 buckets per query (the checks compiled out
-  // altogether, which is not exact: 0.145-0.151).  This is an instantiation of its own (DEFER): a pass with no warm queries
-  // runs the kernel without any of it.
-  constexpr bool DEFER_OK = DEFER && USE_Q16 && !FAT && !PIPE && TOP == 0 && PROBE == 0;
+  // acceptance is one the reference makes, in its order: same index, same d2, same ties.
+  // None of this needs a previous hit: an acceptance needs d2 < closest_d2 <= maxd2, hence |q| <= absmax + R, which is the
+  // condition under which search_tie's bound on E holds; a query that accepts nothing returns -1 like the reference, wherever
+  // it lies.  So a query without a previous hit walks the same way from the full radius, and in wave-uniform visits nobody
+  // makes the check either.  (DEFER_UCHK: the queries without a previous hit keeping it THERE -- the record is in scalar
+  // registers, the check is masked arithmetic, a wave of queries far outside the model is turned away at the root -- was built
+  // and measured as well: every wave that holds one such lane pays for it at every node it visits together, k_search 0.1570
+  // against 0.1508 ms without; NEGATIVES.md Part 00.)
+  // A query that did accept thinly retires marked (kpos -2) and is searched again BEHIND the slab, cold and with every check:
+  // the reference's own walk (kd_search_plain; the pass after the main loop).  Inside the loop -- round 5 -- the second search
+  // kept the checking path and its selects in every visit.  The warm radius is the previous hit's d2 + 2 tie, so that finding
+  // that very point again is not thin.  This is an instantiation of its own (DEFER), launched only for a warm pass over a tree
+  // that has the split halves and the 16-bit shadow (launch_refill128); every other pass runs the kernel without any of it.
   const char* const splitb = DEFER_OK ? reinterpret_cast<const char*>(T.split) : nullptr;
-  const uint32_t split_off = (DEFER_OK && splitb != nullptr) ? (uint32_t)(splitb - hotb) : 0u;
-  const double a_tie = (DEFER_OK && splitb != nullptr && t_q16 != nullptr) ? a.tie : 0.0;
+  const uint32_t split_off = DEFER_OK ? (uint32_t)(splitb - hotb) : 0u;
+  const double a_tie = DEFER_OK ? a.tie : 0.0;
   // (the two per-lane flags ride in the top bits of nbk, the query's cost counter: as lane masks of their own they were two more
   // SGPR pairs in a kernel that has none to spare -- spilled into VGPR lanes, +5 % on every launch)
-  constexpr uint32_t NBK_DEFER = 0x80000000u, NBK_THIN = 0x40000000u, NBK_COST = 0x3FFFFFFFu;
+  // (NBK_UCHK, with DEFER_UCHK only: a lane without a previous hit, which makes the quick check in wave-uniform visits; the cost
+  // field keeps 29 bits and is clamped to 255 where it is stored)
+  constexpr uint32_t NBK_DEFER = 0x80000000u, NBK_THIN = 0x40000000u, NBK_UCHK = 0x20000000u, NBK_COST = 0x1FFFFFFFu;
+  constexpr bool DEFER_UCHK = false;
   unsigned c_int = 0, c_leaf = 0, c_pts = 0, c_redo = 0;
   unsigned c_t1 = 0, c_t2 = 0;   // lab, instrumented instantiations: trips of the wave through the node walk / the bucket scan
   unsigned nbk = 0;   // buckets this lane's query has visited (the next pass's ordering key)
@@ -1581,16 +1658,14 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
 
   for (;;) {
     // ---- retire finished queries, hand out new ones ----
-    if (DEFER_OK && cur == REF_DONE && have && (nbk & (NBK_DEFER | NBK_THIN)) == (NBK_DEFER | NBK_THIN)) {
-      // accepted a point within `tie` of its closest_d2 on a walk without quick checks: again, as the reference does it
-      nbk &= NBK_COST;
-      if (COUNT) ++c_redo;
-      cur = T.root_ref; bk = -1; st.sp = 0;
-      { const SearchArgs* ap = &a; asm volatile("" : "+s"(ap)); best = ap->maxd2; }
-      bx.set_radius(best);
-    }
     const bool idle = (cur == REF_DONE);
     if (idle && have) {
+      if (DEFER_OK && (nbk & (NBK_DEFER | NBK_THIN)) == (NBK_DEFER | NBK_THIN)) {
+        // accepted a point within `tie` of its closest_d2 on a walk without quick checks: marked (kpos -2, the dearest cost) and
+        // searched again behind the slab, as the reference does it (the pass behind this loop); nobody outside this launch sees
+        // the mark
+        bk = -2; nbk = 255u;
+      }
       gstore<int>(reinterpret_cast<char*>(a_kpos), (uint32_t)qi << 2, bk);
       if (ORDER && a_cost) a_cost[qi] = (unsigned char)min(nbk & NBK_COST, 255u);   // nbk: node visits + 4 per bucket
       if (a_d2) gstore<double>(reinterpret_cast<char*>(a_d2), (uint32_t)qi << 3, best);
@@ -1706,7 +1781,9 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
         if (a.has_inv) dev_xf3(a.inv, tx, ty, tz, qx, qy, qz);  // searchTree.cc:122
         qi = mine; have = true; nbk = 0;
         cur = T.root_ref; best = warm_radius_kp(a, kp_prev, qx, qy, qz); bk = -1; st.sp = 0;
-        if (DEFER_OK && a_tie > 0.0 && kp_prev >= 0 && best < a.maxd2) nbk = NBK_DEFER;
+        // (every lane of a DEFER pass walks in the one mode; DEFER_UCHK: one without a previous hit -- or whose warm radius is
+        // not below maxd2 -- makes the quick check where the wave visits a node together)
+        if (DEFER_OK) nbk = (DEFER_UCHK && !(kp_prev >= 0 && best < a.maxd2)) ? (NBK_DEFER | NBK_UCHK) : NBK_DEFER;
         bx.set_query(qx, qy, qz, T.absmax);
         q16_query();
         bx.set_radius(best);
@@ -1756,8 +1833,9 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
         uint32_t s_c1 = su[10], s_c2 = su[11], s_axis = su[6];
         TDTK_PIN_S64(s_split); TDTK_PIN_S32(s_c1); TDTK_PIN_S32(s_c2); TDTK_PIN_S32(s_axis);
         bool prune = false;
-        // (the quick check only for the lanes that make it: a wave whose lanes all defer it jumps over the arithmetic)
-        if (!(DEFER_OK && (nbk & NBK_DEFER))) {
+        // (the quick check only for the lanes that make it -- in a DEFER pass nobody, or with DEFER_UCHK those without a previous
+        // hit: a wave that holds none of them jumps over the arithmetic)
+        if (DEFER_OK ? (DEFER_UCHK && (nbk & NBK_UCHK) != 0u) : true) {
         const float a32 = fmaxf(fmaxf(fabsf(bx.qx - sf[0]) - sf[3], fabsf(bx.qy - sf[1]) - sf[4]), fabsf(bx.qz - sf[2]) - sf[5]);
         prune = a32 >= bx.thi;
         if (__builtin_expect(!prune && !(a32 < bx.tlo), 0)) {      // undecidable in fp32 (or not finite): the exact test
@@ -1778,28 +1856,12 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
         float4 b0, b1;
         double2 sc;
         if constexpr (DEFER_OK) {
-          // One batch of loads whatever the lanes' modes (a branch per mode would be two round trips in a row for a wave that
-          // holds both): the split half for everybody, the box for the lanes that make the quick check.
-          const bool dfr = (nbk & NBK_DEFER) != 0u;
-          // (the split halves sit behind the hot records in ONE allocation: one scalar base, the lane picks the offset -- a lane
-          // that makes the check reads its 48 bytes from one record, as before)
-          sc = gload<double2>(hotb, dfr ? split_off + __umul24(cur, 16u) : ho + 32u);
-          bool prune = false;
-          if (!dfr) {
-            b0 = gload<float4>(hotb, ho); b1 = gload<float4>(hotb, ho + 16);
-            asm volatile("" : "+v"(b0.x), "+v"(b1.x));        // (both requested behind sc's load, before anything waits)
-            const float a32 = fmaxf(fmaxf(fabsf(bx.qx - b0.x) - b0.w, fabsf(bx.qy - b0.y) - b1.x), fabsf(bx.qz - b0.z) - b1.y);
-            prune = a32 >= bx.thi;
-            if (__builtin_expect(!prune && !(a32 < bx.tlo), 0)) {      // undecidable in fp32 (or not finite): the exact test
-              const uint32_t no = (uint32_t)((cur & REF_VAL) << 6);
-              const double4 n0 = gload<double4>(reinterpret_cast<const char*>(nodes), no);
-              const double2 n1 = gload<double2>(reinterpret_cast<const char*>(nodes), no + 32);
-              prune = box_prunes_exact(n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, qx, qy, qz, best);
-            }
-          }
+          // One mode: every lane reads the 16-byte split half { splitval, c1, c2 } -- the halves sit behind the hot records in
+          // ONE allocation, one scalar base -- and descends.  No box, no check, no select: one load per trip for all 64 slots.
+          (void)ho; (void)b0; (void)b1;
+          sc = gload<double2>(hotb, split_off + __umul24(cur, 16u));
           const uint32_t c1b = (uint32_t)__double2loint(sc.y), c2b = (uint32_t)__double2hiint(sc.y);
-          if (prune) need_pop = true;
-          else next = descend_ax(sc.x, c1b, c2b, ((c1b >> 30) & 1u) | (((c2b >> 30) & 1u) << 1), qx, qy, qz, best, st);
+          next = descend_ax(sc.x, c1b, c2b, ((c1b >> 30) & 1u) | (((c2b >> 30) & 1u) << 1), qx, qy, qz, best, st);
         } else {
         if (TOP > 0 && ho < top_n * (uint32_t)sizeof(KdHot)) {
           const char* lp = reinterpret_cast<const char*>(lds_top) + ho;
@@ -1871,7 +1933,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
       const uint32_t olast = o0 + ((uint32_t)(count - 1) << 5);
       // (one filter per build: with both in the kernel the register allocation is the fp32 one plus the grid query -- 130 VGPRs,
       // three waves per SIMD; a tree without the filter this build uses -- degenerate box, no memory -- takes the fp64 loop)
-      if (USE_Q16 && (PROBE == 0 || PROBE == 3) && t_q16 != nullptr && count <= 20) {
+      if (USE_Q16 && (PROBE == 0 || PROBE == 3) && (DEFER_OK || t_q16 != nullptr) && count <= 20) {
         bool thin = false;
         bucket_scan_q16(t_q16, pb, start, count, o0, bx, q16xy, q16zz, q16in, qx, qy, qz, best, bk, a_tie, thin);
         if (DEFER_OK && thin) nbk |= NBK_THIN;
@@ -1919,6 +1981,42 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
         st.top(r, m2);
         if (m2 < best) { cur = r; break; }
       }
+    }
+  }
+  if constexpr (DEFER_OK) {
+    // ---- thin acceptances, searched again behind the slab ----
+    // The wave passes over its own slab once more, consecutive lanes, consecutive queries; a query marked -2 above is read back
+    // (the moved point from x / y / z, mapped with `inv` as at its hand-out) and walked as the reference walks it: cold, radius
+    // maxd2, every check (kd_search_plain).  The walk's registers are dead here and the lane's stack column is free.  The marks
+    // were written by other lanes of this wave: a fence of workgroup scope makes them visible (as for the sums pass below, which
+    // -- like everybody behind this launch -- only ever sees >= 0 or -1).
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    const SearchArgs* ap = &a;
+    asm volatile("" : "+s"(ap));      // (the arguments are read here, not kept in scalar registers across the search)
+    const bool balanced = kLab && ap->bounds != nullptr;     // this wave's slab is [reg0, slab_end), in one piece
+    const uint32_t slab = balanced ? (uint32_t)(slab_end - reg0) : (uint32_t)ap->qpw, sub32 = balanced ? 0x7FFFFFFFu : (uint32_t)sub;
+    for (uint32_t j0 = 0; j0 < slab; j0 += WAVE) {
+      uint32_t j = j0 + lane, ph = 0;
+      const bool in = j < slab;
+      while (j >= sub32 && in) { j -= sub32; ph++; }
+      const size_t q = reg0 + (size_t)ph * pstride + j;
+      if (!(in && q < slab_end)) continue;
+      if (gload<int>(reinterpret_cast<const char*>(a_kpos), (uint32_t)q << 2) != -2) continue;
+      if (COUNT) ++c_redo;
+      const uint32_t q8 = (uint32_t)q << 3;
+      const double tx = gload<double>(reinterpret_cast<const char*>(ap->x), q8), ty = gload<double>(reinterpret_cast<const char*>(ap->y), q8),
+                   tz = gload<double>(reinterpret_cast<const char*>(ap->z), q8);
+      double rx = tx, ry = ty, rz = tz;
+      if (ap->has_inv) dev_xf3(ap->inv, tx, ty, tz, rx, ry, rz);  // searchTree.cc:122
+      double rbest = ap->maxd2;
+      int rbk = -1;
+      unsigned r_int = 0, r_leaf = 0, r_pts = 0;
+      kd_search_plain(reinterpret_cast<const char*>(ap->T.nodes), reinterpret_cast<const char*>(ap->T.pts), t_leaf_tab, t_cb, t_cmask,
+                      ap->T.root_ref, rx, ry, rz, rbest, rbk, st, r_int, r_leaf, r_pts);
+      if (COUNT) { c_int += r_int; c_leaf += r_leaf; c_pts += r_pts; }
+      gstore<int>(reinterpret_cast<char*>(a_kpos), (uint32_t)q << 2, rbk);
+      if (ORDER && a_cost) a_cost[q] = (unsigned char)min(r_int + 4u * r_leaf, 255u);   // the ordering key, as at a retire
+      if (a_d2) gstore<double>(reinterpret_cast<char*>(a_d2), q8, rbest);
     }
   }
   if (kLab && a.trace && lane == 0) {
@@ -2807,7 +2905,8 @@ static void launch_refill128(SearchArgs& a, hipStream_t s)
   if constexpr (FUSE == 0 || FUSE == 3) {      // (every other FUSE is the lab's, and launched above)
     // SinglePass<THRESH, COUNT, FUSE, DEFER>.  DEFER: the instantiation whose warm queries defer the quick check (SearchArgs::tie): a repeated pass over a tree that has
     // the split halves and the 16-bit shadow; everything else -- every cold pass -- runs the kernel without that machinery
-    const bool defer = a.warm && a.tie > 0.0 && a.T.split != nullptr && a.T.q16 != nullptr && BUCKET_Q16;
+    // (and slabs that are the waves' own: the lab's pool hands pieces to whoever runs dry, the redo pass covers a wave's own slab)
+    const bool defer = a.warm && a.tie > 0.0 && a.T.split != nullptr && a.T.q16 != nullptr && BUCKET_Q16 && !a.pool_slab;
     const bool thresh32 = refill_thresh(a.n) == 32;
     if (launched) {}      // (by the lab's hook)
     else if (thresh32 && defer) launch_refill<SinglePass<32, COUNT, FUSE, true>>(nb, occ_lds, s, a);
