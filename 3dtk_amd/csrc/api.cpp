@@ -1,856 +1,10 @@
-// C ABI of lib3dtk_hip.so (include/tdtk_hip.h): handles, workspaces, host orchestration of
-// the kernels in kernels.hip.  There is NO CPU fallback in this library: without a HIP device
-// every compute entry point fails with TDTK_EDEVICE.
-#include <sched.h>
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <numeric>
-#include <string>
-#include <vector>
-
-#include "kernels.h"
-#include "query.h"
+// C ABI of lib3dtk_hip.so (include/tdtk_hip.h), host side: closest-point search and pair sums, resident scans, icp6D::match and
+// the graph-SLAM back-ends.  (Context and state: api_ctx.cpp; trees and query.hip's families: api_tree.cpp,
+// api_query.cpp.)  There is NO CPU fallback in this library: without a HIP device every compute entry point fails with
+// TDTK_EDEVICE.
+#include "api_internal.h"
 
 using namespace tdtk;
-
-// ------------------------------------------------------------------------------------------
-// errors
-// ------------------------------------------------------------------------------------------
-static thread_local std::string g_err;
-void tdtk::set_error(const std::string& s) { g_err = s; }
-
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) {                                                                  \
-      set_error(std::string(#expr) + ": " + hipGetErrorString(_e));                          \
-      return TDTK_EDEVICE;                                                                   \
-    }                                                                                        \
-  } while (0)
-
-static std::atomic<int> g_ctx_live{0};             // host threads that hold a context right now (all devices)
-static std::atomic<uint64_t> g_respeculated{0};   // tree builds whose speculative cuts failed the final check
-
-static double now_ms()
-{
-  using namespace std::chrono;
-  return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-
-// ------------------------------------------------------------------------------------------
-// per-thread, per-device context: stream, events, growable workspaces
-// ------------------------------------------------------------------------------------------
-// the arrays of trees and resident scans and the per-context workspaces below come from the pool (pool.cpp)
-static inline hipError_t handle_malloc(void** p, size_t bytes) { return (hipError_t)pool_malloc_raw(p, bytes); }
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { if (p) pool_free(p); }     // (pooled like the handles' arrays: the contexts of a prefetch pool's threads come and go)
-  int ensure(size_t bytes)
-  {
-    if (bytes <= cap) return TDTK_OK;
-    if (p) pool_free(p);
-    p = nullptr; cap = 0;
-    size_t want = bytes + bytes / 8 + 256;
-    hipError_t e = (hipError_t)pool_malloc_raw(&p, want);
-    if (e != hipSuccess) { set_error(std::string("hipMalloc: ") + hipGetErrorString(e)); return TDTK_ENOMEM; }
-    cap = want;
-    return TDTK_OK;
-  }
-  template <class T> T* as() { return static_cast<T*>(p); }
-};
-
-enum { WS_KPOS, WS_D2, WS_PART, WS_OUT, WS_OVF_M2, WS_OVF_REF, WS_IDX, WS_QX, WS_QY, WS_QZ, WS_DX,
-       WS_DY, WS_DZ, WS_ORDER, WS_CELL, WS_HIST, WS_TMPA, WS_TMPB, WS_CNT, WS_BOX, WS_ARENA, WS_COST, WS_MOVES, WS_BOUNDS, WS_COUNT };
-
-// an auxiliary stream with the buffers one whole-scan pass needs: batches of links over small scans run several
-// passes side by side (one pass of an 80K-point scan occupies a fraction of the machine and is latency-bound)
-// draw counters of the work-queue search kernel: two sets of 8 that alternate from launch to launch on one stream
-// (each launch zeroes the set of the next one, kernels.hip)
-struct QueueCtr {
-  DevBuf buf;
-  int parity = 0;
-  int attach(SearchArgs& a)
-  {
-    if (!buf.p) {
-      int rc = buf.ensure(64 * sizeof(uint32_t));
-      if (rc) return rc;
-      if (hipMemset(buf.p, 0, 64 * sizeof(uint32_t)) != hipSuccess) { set_error("hipMemset failed"); return TDTK_EDEVICE; }
-    }
-    a.q_ctr = buf.as<uint32_t>() + 32 * parity;
-    a.q_ctr_next = buf.as<uint32_t>() + 32 * (parity ^ 1);
-    parity ^= 1;
-    return TDTK_OK;
-  }
-};
-
-struct Lane {
-  hipStream_t s = nullptr;
-  bool owns = true;     // lane 0 runs on the context's own stream
-  QueueCtr qc;
-  DevBuf kpos, part, ovf_m2, ovf_ref;
-  DevBuf moved;      // batched link passes: this link's own copy of a scan another link of the launch is moving (lazy moves)
-  // batched link passes: whose hits kpos holds (handle numbers of the tree and the scan, queries) -- the next pass of the SAME
-  // link at this position starts every search from its previous hit (SearchArgs::warm)
-  uint64_t k_tree = 0, k_scan = 0; size_t k_n = 0;
-  ~Lane() { if (s && owns) (void)hipStreamDestroy(s); }
-};
-
-// batched link passes: what each query of the link at this position of the launch order cost in the previous pass (one
-// byte per query: the next pass's hand-out order), and which link that was
-struct LinkCost {
-  DevBuf cost;
-  const void* tree = nullptr; const void* scan = nullptr; size_t n = 0;
-};
-
-struct Ctx {
-  int device = -1;
-  hipStream_t stream = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;   // around the search kernel of the last pass
-  hipEvent_t e2 = nullptr, e3 = nullptr;   // around the pair-sum kernels behind it (k_accum + k_final, or k_final alone)
-  hipEvent_t e4 = nullptr, e5 = nullptr;   // around k_ann_normals of the last calcNormals
-  hipEvent_t e_user = nullptr;             // fence between a caller's stream and this context's stream
-  hipEvent_t e_defer = nullptr;            // behind the last batch of scan moves that was left running (defer_fence)
-  hipStream_t stream_b = nullptr, stream_c = nullptr, stream_d = nullptr;   // the tree build's background chains (exact centroid sums beside the levels below)
-  hipEvent_t e_b1 = nullptr, e_b2 = nullptr, e_b3 = nullptr, e_b4 = nullptr;
-  DevBuf ws[WS_COUNT];
-  double* h_pin = nullptr;  // pinned staging for the per-iteration sums: words [0, ACC_TOTAL); behind them two slots of the tree build
-  // (both are filled by copies enqueued on `stream` and read only behind a synchronisation of that stream that was made after
-  //  the copy was enqueued: one of the build's looks at the device for the box, tree_finish's own hipStreamSynchronize for the
-  //  groups -- device_build_tree may return with its last kernels still running, see build.hip "no_last_look")
-  static constexpr int PIN_BOX = 128;      // 6 doubles: the root bounding box (tree_from_device_points)
-  static constexpr int PIN_GROUPS = 140;   // 1 uint32: groups of the padded layout (tree_pad_buckets -> tree_finish)
-  void* h_build = nullptr;  // 64 KB, pinned: the tree build's looks at the device (BuildSide::h_pin)
-  void* h_stage = nullptr;  // pinned staging for descriptor tables of batched launches (grows on demand)
-  size_t h_stage_cap = 0;
-  DevBuf d_mask, d_skip;                // -R passes: the keep-mask (bits, caller order) and what the search reads (bytes, sorted order)
-  std::vector<unsigned char> h_mask;
-  DevBuf d_loop;                        // lab, the host-free ICP loop: its IcpLoopDev block (kernels.h)
-  double* h_loop = nullptr;             // ... and its record, pinned: ICP_LOOP_RING rows of ICP_ROW doubles
-  DevBuf d_hash;                        // tdtk_icp_index_hashes: one 64-bit word per iteration of the last tdtk_icp_match
-  std::vector<uint64_t> last_hashes;
-  void* h_moves = nullptr;  // pinned staging of scans_settle's table (its own: a settle may precede a batched launch in one call)
-  size_t h_moves_cap = 0;
-  hipEvent_t e_moves = nullptr;   // behind the last copy out of h_moves
-  bool moves_inflight = false;
-  double last_nn_ms = 0.0, last_sums_ms = 0.0, last_normals_ms = 0.0, last_build_ms = 0.0;
-  bool ev_pending = false, ev2_pending = false, ev4_pending = false;
-  uint64_t counted_ann_queries = 0;
-  // tdtk_visit_counting: every search of this thread runs its instrumented instantiation and adds to d_counters
-  bool counting = false;
-  // tdtk_visit_counting(device, 2): count the REFERENCE's walk -- every search while counting starts cold (no warm start, no
-  // deferred quick check), i.e. kdTreeImpl.h:345-383 with radius maxdist2; results are the same, so a loop stays on its path
-  bool count_cold = false;
-  DevBuf d_counters;
-  uint64_t counted_queries = 0;
-  std::vector<std::unique_ptr<Lane>> lanes;
-  std::vector<std::unique_ptr<Lane>> slots;   // per-link buffers of a several-links-in-one-launch batch (no streams)
-  std::vector<std::unique_ptr<LinkCost>> link_costs;
-  DevBuf multi_args;                          // its argument tables on the device
-  std::vector<void*> free_later;              // see pool_free_later
-  QueueCtr qc;       // for launches on `stream` (a caller's stream gets its launches ordered behind it, see run_search)
-  // slabs of equal cost for the next pass of an ICP loop (launch_slab_bounds): valid for the loop's next scan_pass only
-  const uint32_t* next_bounds = nullptr;
-  size_t next_bounds_n = 0;
-  // a context dies with its host thread (worker threads of a prefetch pool come and go): give everything back
-  ~Ctx();
-};
-
-// Batched scan moves (the pose update of a graph-SLAM round: every resident scan of the rank, ~0.6 ms for 63 x 1M
-// points) are left running when the call returns; whatever the host does next -- Python marshalling, building the
-// next round's graph -- overlaps with them.  The fence is process-wide: the next library call of ANY host thread on
-// that device waits for it in get_ctx before it touches a scan, so "the scans have moved when the call has returned"
-// still holds for everything that can observe them.
-struct Deferred { int device; hipEvent_t ev; Ctx* owner; };
-static std::mutex g_defer_mu;
-static std::atomic<int> g_defer_n{0};
-static std::vector<Deferred> g_defer;
-
-static void wait_deferred(int device, const Ctx* only_owner = nullptr)
-{
-  if (g_defer_n.load(std::memory_order_acquire) == 0) return;
-  std::lock_guard<std::mutex> lk(g_defer_mu);
-  for (size_t i = 0; i < g_defer.size();) {
-    if (g_defer[i].device == device && (!only_owner || g_defer[i].owner == only_owner)) {
-      (void)hipEventSynchronize(g_defer[i].ev);
-      g_defer.erase(g_defer.begin() + (long)i);
-    } else {
-      ++i;
-    }
-  }
-  g_defer_n.store((int)g_defer.size(), std::memory_order_release);
-}
-
-Ctx::~Ctx()
-  {
-    g_ctx_live.fetch_sub(1);
-    if (device >= 0) (void)hipSetDevice(device);
-    wait_deferred(device, this);
-    if (e_defer) (void)hipEventDestroy(e_defer);
-    for (void* q : free_later) pool_free(q);
-    free_later.clear();
-    if (h_stage) (void)hipHostFree(h_stage);
-    if (h_moves) (void)hipHostFree(h_moves);
-    if (e_moves) (void)hipEventDestroy(e_moves);
-    lanes.clear();
-    slots.clear();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e2) (void)hipEventDestroy(e2);
-    if (e3) (void)hipEventDestroy(e3);
-    if (e4) (void)hipEventDestroy(e4);
-    if (e5) (void)hipEventDestroy(e5);
-    if (e_user) (void)hipEventDestroy(e_user);
-    if (e_b1) (void)hipEventDestroy(e_b1);
-    if (e_b2) (void)hipEventDestroy(e_b2);
-    if (e_b3) (void)hipEventDestroy(e_b3);
-    if (e_b4) (void)hipEventDestroy(e_b4);
-    if (stream_b) (void)hipStreamDestroy(stream_b);
-    if (stream_c) (void)hipStreamDestroy(stream_c);
-    if (stream_d) (void)hipStreamDestroy(stream_d);
-    if (h_pin) (void)hipHostFree(h_pin);
-    if (h_loop) (void)hipHostFree(h_loop);     // (lab)
-    if (h_build) (void)hipHostFree(h_build);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-
-static thread_local std::map<int, std::unique_ptr<Ctx>> g_ctx;
-
-static int get_ctx(int device, Ctx** out, bool touches_scans = true)
-{
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    set_error("no HIP device available (lib3dtk_hip has no CPU fallback)");
-    return TDTK_EDEVICE;
-  }
-  if (device < 0 || device >= ndev) { set_error("bad device ordinal"); return TDTK_EINVAL; }
-  HIPCHK(hipSetDevice(device));
-  auto it = g_ctx.find(device);
-  if (it == g_ctx.end()) {
-    std::unique_ptr<Ctx> c(new Ctx);
-    c->device = device;
-    HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreate(&c->e0));
-    HIPCHK(hipEventCreate(&c->e1));
-    HIPCHK(hipEventCreate(&c->e2));
-    HIPCHK(hipEventCreate(&c->e3));
-    HIPCHK(hipEventCreate(&c->e4));
-    HIPCHK(hipEventCreate(&c->e5));
-    HIPCHK(hipEventCreateWithFlags(&c->e_user, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->e_defer, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->e_moves, hipEventDisableTiming));
-    // (coherent, said explicitly: the host reads these words while the kernel that writes them is still running -- await_sums)
-    HIPCHK(hipHostMalloc((void**)&c->h_pin, sizeof(double) * 256, hipHostMallocCoherent));
-    HIPCHK(hipHostMalloc(&c->h_build, 65536, hipHostMallocDefault));
-    it = g_ctx.emplace(device, std::move(c)).first;
-    g_ctx_live.fetch_add(1);
-  }
-  *out = it->second.get();
-  if (touches_scans) wait_deferred(device);    // (the timing / counter read-outs do not: they must not end the overlap)
-  return TDTK_OK;
-}
-
-namespace tdtk {
-int ctx_stream(int device, void** stream_out)
-{
-  Ctx* c;
-  int rc = get_ctx(device, &c);
-  if (rc) return rc;
-  *stream_out = c->stream;
-  return TDTK_OK;
-}
-}  // namespace tdtk
-
-// leave what has been enqueued on c->stream running (see Deferred); TDTK_SYNC_MOVES=1 waits as before
-static int defer_fence(Ctx* c)
-{
-  static const bool sync_moves = [] { const char* e = getenv("TDTK_SYNC_MOVES"); return e && e[0] == '1'; }();
-  if (sync_moves) { HIPCHK(hipStreamSynchronize(c->stream)); return TDTK_OK; }
-  // the event is re-recorded under the lock: another host thread may be inside hipEventSynchronize on this very event
-  // (wait_deferred holds the lock while it waits), and re-recording an event somebody is waiting on is undefined
-  std::lock_guard<std::mutex> lk(g_defer_mu);
-  HIPCHK(hipEventRecord(c->e_defer, c->stream));
-  bool have = false;
-  for (const Deferred& d : g_defer) have = have || d.owner == c;
-  if (!have) g_defer.push_back({c->device, c->e_defer, c});
-  g_defer_n.store((int)g_defer.size(), std::memory_order_release);
-  return TDTK_OK;
-}
-
-// blocks an enqueued kernel still reads: given back behind the next synchronisation of the context's stream
-static void pool_free_later(Ctx* c, void* p) { if (p) c->free_later.push_back(p); }
-static void flush_free_later(Ctx* c)
-{
-  for (void* p : c->free_later) pool_free(p);
-  c->free_later.clear();
-}
-
-// pinned host staging that stays valid until the next library call on this thread (get_ctx has then waited for the
-// copy that reads it)
-static int stage_reserve(Ctx* c, size_t bytes)
-{
-  if (c->h_stage_cap < bytes) {
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    c->h_stage = nullptr; c->h_stage_cap = 0;
-    const size_t want = std::max<size_t>(bytes, 64 * 1024);
-    if (hipHostMalloc(&c->h_stage, want, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return TDTK_ENOMEM; }
-    c->h_stage_cap = want;
-  }
-  return TDTK_OK;
-}
-static int stage_pinned(Ctx* c, const void* src, size_t bytes, void** out)
-{
-  if (c->h_stage_cap < bytes) {
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    c->h_stage = nullptr; c->h_stage_cap = 0;
-    const size_t want = std::max<size_t>(bytes, 64 * 1024);
-    if (hipHostMalloc(&c->h_stage, want, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return TDTK_ENOMEM; }
-    c->h_stage_cap = want;
-  }
-  std::memcpy(c->h_stage, src, bytes);
-  *out = c->h_stage;
-  return TDTK_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// handles
-// ------------------------------------------------------------------------------------------
-// every tree / scan handle of the process has a number of its own: what "the same tree, the same scan as last time" is tested
-// with where a stale answer would be an out-of-range read (a freed handle's address can come back)
-static std::atomic<uint64_t> g_handle_uid{1};
-
-struct tdtk_tree {
-  const uint64_t uid = g_handle_uid.fetch_add(1, std::memory_order_relaxed);
-  int device = 0;
-  size_t M = 0;
-  int bucket = 0;
-  TreeDev dev{};
-  void *d_nodes = nullptr, *d_pts = nullptr, *d_leaf = nullptr, *d_r = nullptr, *d_hot = nullptr, *d_grp = nullptr, *d_fat = nullptr;
-  void* d_q16 = nullptr;     // 16-bit shadow of the padded buckets (TreeDev::q16), 6 bytes per slot + 128 of slack
-  void* d_split = nullptr;   // { splitval, children } of every internal node, 16 bytes (TreeDev::split): inside d_hot's allocation
-  double q_lo[3] = {0, 0, 0}, q_scale = 0.0;
-  size_t Mp = 0;   // slots of d_pts: M, or 4 * groups once the buckets are padded to whole groups (tree_pad_buckets)
-  double bbmin[3], bbmax[3], centre[3];
-  tdtk_tree_info info{};
-  tdtk_tree() = default;
-  tdtk_tree(const tdtk_tree&) = delete;
-  tdtk_tree& operator=(const tdtk_tree&) = delete;
-  ~tdtk_tree()   // also the error paths of tdtk_tree_create: nothing stays allocated on the device
-  {
-    (void)hipSetDevice(device);
-    void* p[] = {d_nodes, d_pts, d_leaf, d_r, d_hot, d_grp, d_fat, d_q16};
-    for (void* q : p)
-      if (q) pool_free(q);
-  }
-};
-
-struct tdtk_scan {
-  const uint64_t uid = g_handle_uid.fetch_add(1, std::memory_order_relaxed);
-  int device = 0;
-  size_t N = 0;
-  double *x = nullptr, *y = nullptr, *z = nullptr, *nx = nullptr, *ny = nullptr, *nz = nullptr;
-  int32_t* d_order = nullptr;    // sorted position -> caller index
-  // "xyz reduced original" (basicScan.cc:739-757 copyReducedToOriginal): once tdtk_scan_mark_original has been
-  // called, the first operation that moves the points first saves them here (a device-to-device copy), so the
-  // scan's search tree can still be built later without the points ever visiting the host
-  bool track_original = false;
-  double *ox = nullptr, *oy = nullptr, *oz = nullptr;
-  // Lazy moves.  The pose update of a graph-SLAM round does not touch the points: it queues its in-place transforms here
-  // (oldest first), and whoever reads the scan next applies them -- the link passes of the next round in registers where a
-  // lane takes a query (the link that owns the update stores the result into the spare arrays ax / ay / az, swapped in
-  // behind the launch), every other entry point through scan_settle (one pass, all queued matrices in order).  A rank
-  // never moves a scan none of its links reads.  The arithmetic is the one Scan::transform does point by point
-  // (scan.cc:851-875), matrix after matrix: same bits as moving the scan every time.
-  // Several host threads may hold the same scan (a prefetch pool, an OpenMP host): the queue, the spare arrays and the
-  // swap are only touched under g_moves_mu; npend mirrors pending.size() so that the readers' fast path ("nothing
-  // queued") takes no lock.  A settle issued while more than one context is live waits for its kernel before it
-  // publishes npend == 0, so a reader on ANOTHER stream that finds nothing queued also finds the points moved.
-  mutable std::vector<Mat4> pending;
-  mutable std::atomic<uint32_t> npend{0};
-  mutable double *ax = nullptr, *ay = nullptr, *az = nullptr;
-  tdtk_scan() = default;
-  tdtk_scan(const tdtk_scan&) = delete;
-  tdtk_scan& operator=(const tdtk_scan&) = delete;
-  ~tdtk_scan()
-  {
-    (void)hipSetDevice(device);
-    double* p[] = {x, y, z, nx, ny, nz, ox, oy, oz, ax, ay, az};
-    for (double* q : p)
-      if (q) pool_free(q);
-    if (d_order) pool_free(d_order);
-  }
-};
-
-// ------------------------------------------------------------------------------------------
-extern "C" {
-
-const char* tdtk_last_error(void) { return g_err.c_str(); }
-const char* tdtk_version(void) { return "3dtk_amd 0.1 (gfx950)"; }
-
-size_t tdtk_pool_trim(void) { return pool_trim(); }
-uint64_t tdtk_build_respeculated(void) { return g_respeculated.load(); }
-
-int tdtk_device_count(void)
-{
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-  return n;
-}
-
-// copy-on-first-write of a tracked scan's original points; called by everything that moves a resident scan
-static int scan_keep_original(Ctx* c, tdtk_scan* s)
-{
-  if (!s || !s->track_original || s->ox || s->N == 0) return TDTK_OK;
-  const size_t b = s->N * sizeof(double);
-  {   // all three or none (a partial set would pass the `s->ox` test above next time)
-    void* p[3] = {nullptr, nullptr, nullptr};
-    for (int k = 0; k < 3; k++)
-      if (handle_malloc(&p[k], b) != hipSuccess) {
-        for (int j = 0; j < k; j++) pool_free(p[j]);
-        set_error("out of device memory (saved original of a scan)");
-        return TDTK_ENOMEM;
-      }
-    s->ox = static_cast<double*>(p[0]); s->oy = static_cast<double*>(p[1]); s->oz = static_cast<double*>(p[2]);
-  }
-  HIPCHK(hipMemcpyAsync(s->ox, s->x, b, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(s->oy, s->y, b, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(s->oz, s->z, b, hipMemcpyDeviceToDevice, c->stream));
-  return TDTK_OK;
-}
-
-// ---- lazy scan moves (see tdtk_scan::pending) ---------------------------------------------------
-static std::recursive_mutex g_moves_mu;      // guards every scan's pending / npend / ax..az and the x <-> ax swap
-static bool lazy_moves()
-{
-  const char* e = getenv("TDTK_LAZY_MOVES");     // 0: every queued move is carried out at once (the round-3 behaviour)
-  return !(e && e[0] == '0');
-}
-// longest chain a scan may carry: a rank that never reads a scan (seven of eight ranks, for most scans) carries it out
-// once per this many queued transforms -- one trip of the points through HBM per 16 rounds instead of one per round
-constexpr size_t LAZY_CHAIN_MAX = 32;
-
-// carry out what is queued on these scans: one launch, every scan's chain in order.  Enqueued on c->stream; the caller
-// decides whether to wait (the entry points that go on to read the scan on the same stream need not).
-static int scans_settle(Ctx* c, const tdtk_scan* const* scans, int count)
-{
-  {   // fast path without the lock: nothing queued on any of them
-    bool any = false;
-    for (int i = 0; i < count && !any; i++) any = scans[i] && scans[i]->npend.load(std::memory_order_acquire) != 0;
-    if (!any) return TDTK_OK;
-  }
-  std::lock_guard<std::recursive_mutex> lk(g_moves_mu);
-  size_t nmat = 0, max_n = 0;
-  int nd = 0;
-  for (int i = 0; i < count; i++) {
-    const tdtk_scan* sc = scans[i];
-    if (!sc || sc->pending.empty()) continue;
-    bool dup = false;
-    for (int j = 0; j < i && !dup; j++) dup = scans[j] == sc;
-    if (dup) continue;
-    if (!sc->N) { sc->pending.clear(); sc->npend.store(0, std::memory_order_release); continue; }
-    if (sc->device != c->device) { set_error("resident scans of one call must live on one device"); return TDTK_EINVAL; }
-    nmat += sc->pending.size(); nd++;
-    max_n = std::max(max_n, sc->N);
-  }
-  if (!nd) {
-    for (int i = 0; i < count; i++)
-      if (scans[i] && scans[i]->pending.empty()) scans[i]->npend.store(0, std::memory_order_release);
-    return TDTK_OK;
-  }
-  const size_t o_mat = ((sizeof(XfChainDesc) * (size_t)nd + 127) / 128) * 128, bytes = o_mat + nmat * sizeof(Mat4);
-  int rc = c->ws[WS_MOVES].ensure(bytes);
-  if (rc) return rc;
-  if (c->moves_inflight) { HIPCHK(hipEventSynchronize(c->e_moves)); c->moves_inflight = false; }
-  if (c->h_moves_cap < bytes) {
-    if (c->h_moves) (void)hipHostFree(c->h_moves);
-    c->h_moves = nullptr; c->h_moves_cap = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 2, 64 * 1024);
-    if (hipHostMalloc(&c->h_moves, want, hipHostMallocDefault) != hipSuccess) { set_error("hipHostMalloc failed"); return TDTK_ENOMEM; }
-    c->h_moves_cap = want;
-  }
-  char* tab = static_cast<char*>(c->h_moves);
-  std::memset(tab, 0, o_mat);
-  XfChainDesc* hd = reinterpret_cast<XfChainDesc*>(tab);
-  Mat4* hm = reinterpret_cast<Mat4*>(tab + o_mat);
-  const Mat4* dm = reinterpret_cast<const Mat4*>(static_cast<char*>(c->ws[WS_MOVES].p) + o_mat);
-  size_t k = 0;
-  std::vector<const tdtk_scan*> moved;      // (each scan once, however often the caller's list names it)
-  for (int i = 0; i < count; i++) {
-    const tdtk_scan* sc = scans[i];
-    if (!sc || sc->pending.empty() || std::find(moved.begin(), moved.end(), sc) != moved.end()) continue;
-    XfChainDesc& e = hd[moved.size()];
-    e.x = sc->x; e.y = sc->y; e.z = sc->z; e.nx = sc->nx; e.ny = sc->ny; e.nz = sc->nz; e.n = sc->N;
-    e.mats = dm + k; e.nm = (int)sc->pending.size();
-    for (const Mat4& m : sc->pending) hm[k++] = m;
-    moved.push_back(sc);
-  }
-  // The queues are emptied -- chain and count together -- only once the chain kernel is on the stream: a copy, an event or a
-  // launch that fails on the way returns with every move still queued (round-5 advice: they used to be lost).
-  HIPCHK(hipMemcpyAsync(c->ws[WS_MOVES].p, tab, bytes, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipEventRecord(c->e_moves, c->stream));
-  c->moves_inflight = true;
-  HIPCHK(launch_transform_chain_batch(reinterpret_cast<const XfChainDesc*>(c->ws[WS_MOVES].p), (int)moved.size(), max_n, c->stream));
-  for (const tdtk_scan* sc : moved) sc->pending.clear();
-  // other contexts (host threads with streams of their own) may read these scans next: they must not find "nothing
-  // queued" before the chain kernel has run.  A lone context orders everything on its one stream and need not wait.
-  if (g_ctx_live.load() > 1) HIPCHK(hipStreamSynchronize(c->stream));
-  for (int i = 0; i < count; i++)
-    if (scans[i] && scans[i]->pending.empty()) scans[i]->npend.store(0, std::memory_order_release);
-  return TDTK_OK;
-}
-static int scan_settle(Ctx* c, const tdtk_scan* s)
-{
-  if (!s || s->npend.load(std::memory_order_acquire) == 0) return TDTK_OK;
-  return scans_settle(c, &s, 1);
-}
-// the spare coordinate arrays of a scan (tdtk_scan::ax / ay / az): all three or none -- a launch stores through all of
-// them and swaps them in, so a partial set (one allocation of the three failed) must never be left on the handle
-static int scan_ensure_spare(const tdtk_scan* sc)
-{
-  if (sc->ax && sc->ay && sc->az) return TDTK_OK;
-  const size_t b = sc->N * sizeof(double);
-  void* p[3] = {nullptr, nullptr, nullptr};
-  for (int k = 0; k < 3; k++) {
-    if (handle_malloc(&p[k], b) != hipSuccess) {
-      for (int j = 0; j < k; j++) pool_free(p[j]);
-      set_error("out of device memory (spare arrays of a moving scan)");
-      return TDTK_ENOMEM;
-    }
-  }
-  double* old[3] = {sc->ax, sc->ay, sc->az};
-  for (double* q : old)
-    if (q) pool_free(q);
-  sc->ax = static_cast<double*>(p[0]); sc->ay = static_cast<double*>(p[1]); sc->az = static_cast<double*>(p[2]);
-  return TDTK_OK;
-}
-// queue one in-place transform on a resident scan (the caller has saved "xyz reduced original" if it is tracked)
-static void scan_queue_move(tdtk_scan* s, const double* A16)
-{
-  Mat4 m;
-  std::memcpy(m.m, A16, sizeof m.m);
-  std::lock_guard<std::recursive_mutex> lk(g_moves_mu);
-  s->pending.push_back(m);
-  s->npend.store((uint32_t)s->pending.size(), std::memory_order_release);
-}
-
-// ---- tree ------------------------------------------------------------------------------
-// device construction (build.hip) over the [M][3] points already sitting in c->ws[WS_TMPA]
-static int tree_from_device_points(Ctx* c, tdtk_tree* t, size_t M, int bucket_size, double t0)
-{
-  int rc;
-  if ((rc = c->ws[WS_BOX].ensure(bbox_temp_bytes() + 8 * sizeof(double)))) return rc;
-  double* d_box = c->ws[WS_BOX].as<double>();
-  // root bounding box (binning of unsorted query batches, accumulation shift): min / max on the device
-  // (read back behind the build: the build's own looks at the device are the next synchronisation points)
-  HIPCHK(launch_bbox(c->ws[WS_TMPA].as<double>(), M, d_box + 8, d_box, c->stream));
-  HIPCHK(hipMemcpyAsync(c->h_pin + Ctx::PIN_BOX, d_box, 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  const double t1 = now_ms();
-  t->info.upload_ms = t1 - t0;
-  const bool alone = g_ctx_live.load() <= 2;
-  if ((rc = c->ws[WS_ARENA].ensure(device_build_arena_bytes(M, alone)))) return rc;
-  // The background chain of the build needs a stream of its own, and the runtime has four hardware queues for all the
-  // streams of the process: when several host threads are at work -- a doICP that prepares
-  // three scans ahead -- a sixth and seventh stream end up queued behind other threads' kernels, the root's chain (one
-  // wave, 1.2 ms) in front of somebody's search, and ten 1M-point scans take 43.5 ms instead of 36.4.  So: beside at
-  // most one other thread.
-  if (alone && !c->stream_b) {
-    // made when first needed: every stream of the process takes a share of the four hardware queues, used or not, and
-    // the worker threads of a prefetch pool never build alone
-    HIPCHK(hipStreamCreateWithFlags(&c->stream_b, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&c->stream_c, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&c->stream_d, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->e_b1, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->e_b2, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->e_b3, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->e_b4, hipEventDisableTiming));
-  }
-  const bool four = [] { const char* e = lab_env("TDTK_BUILD_STREAMS"); return !(e && e[0] == '3'); }();   // (lab: TDTK_BUILD_STREAMS=3: round 5's two side streams)
-  const BuildSide side = {alone ? c->stream_b : nullptr, alone ? c->stream_c : nullptr, c->e_b1, c->e_b2, c->e_b3, c->h_build,
-                          (alone && four) ? c->stream_d : nullptr, c->e_b4};
-  DevBuildResult r = device_build_tree(c->ws[WS_TMPA].as<double>(), M, bucket_size, c->ws[WS_ARENA].p, c->stream, &side);
-  if (r.respeculated) g_respeculated.fetch_add(1);
-  if (r.err != hipSuccess) {
-    set_error(r.degenerate ? std::string("degenerate split (non-finite coordinates?)")
-                           : std::string("device tree build: ") + hipGetErrorString(r.err));
-    return r.degenerate ? TDTK_EINVAL : TDTK_EDEVICE;
-  }
-  for (int a = 0; a < 3; a++) { t->bbmin[a] = c->h_pin[Ctx::PIN_BOX + a]; t->bbmax[a] = c->h_pin[Ctx::PIN_BOX + 3 + a]; }   // (the copy was enqueued in front of the build, and every path through device_build_tree synchronises c->stream at least once behind it: a look at the level loop's counters, or its last one)
-  t->d_nodes = r.nodes; t->d_r = r.node_r; t->d_pts = r.pts;
-  t->d_leaf = r.leaf_tab;   // non-null only in table mode
-  t->dev.root_ref = r.root_ref;
-  t->dev.cb = (uint32_t)r.cb;
-  t->info.n_internal = r.n_internal; t->info.n_leaves = r.n_leaves;
-  t->info.max_depth = r.max_depth; t->info.max_leaf_points = r.max_leaf;
-  t->info.build_ms = now_ms() - t1;
-  c->last_build_ms = t->info.build_ms;
-  return TDTK_OK;
-}
-
-// Pad every bucket to whole groups of four slots and build the fp32 shadow groups the big-batch search filters buckets
-// with (kernels.hip, "bucket groups").  The build's scratch arena is free again at this point and holds the two counter
-// arrays and the scan's temporary.  Skipped (the tree stays as built, the search scans buckets in fp64 only) when the
-// tree is a single bucket, when the padded positions would not fit the reference format, or with TDTK_BUCKET_GROUPS=0.
-static int tree_pad_buckets(Ctx* c, tdtk_tree* t, size_t M)
-{
-  t->Mp = M;
-  static const bool off = [] { const char* e = getenv("TDTK_BUCKET_GROUPS"); return e && e[0] == '0'; }();
-  if (off || t->info.n_internal == 0) return TDTK_OK;
-  const size_t n1 = M + 1;
-  const size_t tmpb = scan_u32_temp_bytes(n1);
-  const size_t need = 2 * n1 * sizeof(uint32_t) + tmpb + 256;
-  int rc;
-  if ((rc = c->ws[WS_ARENA].ensure(need))) return rc;
-  uint32_t* ng_at = c->ws[WS_ARENA].as<uint32_t>();
-  uint32_t* g_at = ng_at + n1;
-  void* tmp = (void*)(((uintptr_t)(g_at + n1) + 127) & ~(uintptr_t)127);
-  const uint32_t cb = t->dev.cb, cmask = (cb >= 32) ? 0xFFFFFFFFu : ((1u << cb) - 1u);
-  KdNode* nodes = static_cast<KdNode*>(t->d_nodes);
-  LeafEntry* leaf = static_cast<LeafEntry*>(t->d_leaf);
-  HIPCHK(launch_pad_mark(nodes, t->info.n_internal, leaf, cb, cmask, ng_at, M, c->stream));
-  HIPCHK(launch_scan_u32(ng_at, g_at, n1, tmp, tmpb, c->stream));
-  // The number of groups is known on the device; every bucket is padded by at most three slots, so (M + 3 leaves) / 4 groups
-  // are enough room.  When that bound passes the format checks below, the fill is enqueued right away and the exact count is
-  // read with it -- one look at the device less (a small scan's tree is a few dozen microseconds of launches per look).
-  // the 16-bit grid over the root box (TreeDev::q16): one cell size for the three axes, so that distances stay isotropic
-  bool want_q16 = false;
-  {
-    static const bool q_off = [] { const char* e = getenv("TDTK_BUCKET_Q16"); return e && e[0] == '0'; }();
-    double ext = 0.0;
-    for (int a = 0; a < 3; a++) ext = std::max(ext, t->bbmax[a] - t->bbmin[a]);
-    const double sc = 65535.0 / ext;
-    if (!q_off && ext > 0.0 && std::isfinite(ext) && std::isfinite(sc) && sc > 0.0) {
-      want_q16 = true;
-      for (int a = 0; a < 3; a++) t->q_lo[a] = t->bbmin[a];
-      t->q_scale = sc;
-    }
-  }
-  uint32_t G = 0;
-  const uint64_t G_bound = ((uint64_t)M + 3ull * t->info.n_leaves + 3ull) / 4ull;
-  const bool bound_ok = (4ull * G_bound) * sizeof(KdPoint) < (1ull << 32) && (leaf || ((4ull * G_bound) << cb) <= (uint64_t)REF_VAL);
-  if (bound_ok) {
-    void *ptsB = nullptr, *grpB = nullptr;
-    if (handle_malloc(&ptsB, 4ull * G_bound * sizeof(KdPoint)) == hipSuccess && handle_malloc(&grpB, (size_t)G_bound * 48) == hipSuccess) {
-      void* q16B = nullptr;      // (no room for it: the fp32 groups alone)
-      if (want_q16 && handle_malloc(&q16B, (size_t)G_bound * 24 + 128) != hipSuccess) { (void)hipGetLastError(); q16B = nullptr; }
-      hipError_t e = launch_pad_fill(nodes, t->info.n_internal, leaf, cb, cmask, g_at, static_cast<const KdPoint*>(t->d_pts),
-                                     static_cast<KdPoint*>(ptsB), static_cast<float4*>(grpB), c->stream, static_cast<uint32_t*>(q16B), t->q_lo, t->q_scale);
-      if (e == hipSuccess) e = hipMemcpyAsync(c->h_pin + Ctx::PIN_GROUPS, g_at + M, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream);
-      if (e != hipSuccess) { pool_free(ptsB); pool_free(grpB); if (q16B) pool_free(q16B); set_error(std::string("bucket groups: ") + hipGetErrorString(e)); return TDTK_EDEVICE; }
-      pool_free_later(c, t->d_pts);
-      t->d_pts = ptsB; t->d_grp = grpB; t->d_q16 = q16B;
-      t->Mp = 0;                 // = 4 G, read in tree_finish behind its synchronisation
-      return TDTK_OK;
-    }
-    (void)hipGetLastError();
-    if (ptsB) pool_free(ptsB);
-  }
-  HIPCHK(hipMemcpyAsync(&G, g_at + M, sizeof G, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  const uint64_t slots = 4ull * G;
-  // the padded starts must fit where the starts fitted: 30-bit packed references (start << cb | count), 32-bit byte
-  // offsets into the point and group arrays, int32 starts of the leaf table
-  if (G == 0 || slots * sizeof(KdPoint) >= (1ull << 32) || (!leaf && (slots << cb) > (uint64_t)REF_VAL)) return TDTK_OK;
-  // No room for the padded copy (a transient peak of twice the point array + 12 bytes per slot): the tree as it stands is
-  // complete and searchable -- nothing has been rewritten yet --, so padding is skipped and the fp64-only bucket scan used.
-  void *ptsP = nullptr, *grp = nullptr;
-  if (handle_malloc(&ptsP, slots * sizeof(KdPoint)) != hipSuccess) { (void)hipGetLastError(); return TDTK_OK; }
-  if (handle_malloc(&grp, (size_t)G * 48) != hipSuccess) { (void)hipGetLastError(); pool_free(ptsP); return TDTK_OK; }
-  void* q16 = nullptr;
-  if (want_q16 && handle_malloc(&q16, (size_t)G * 24 + 128) != hipSuccess) { (void)hipGetLastError(); q16 = nullptr; }
-  hipError_t e = launch_pad_fill(nodes, t->info.n_internal, leaf, cb, cmask, g_at, static_cast<const KdPoint*>(t->d_pts),
-                                 static_cast<KdPoint*>(ptsP), static_cast<float4*>(grp), c->stream, static_cast<uint32_t*>(q16), t->q_lo, t->q_scale);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess) { pool_free(ptsP); pool_free(grp); if (q16) pool_free(q16); set_error(std::string("bucket groups: ") + hipGetErrorString(e)); return TDTK_EDEVICE; }
-  pool_free(t->d_pts);
-  t->d_pts = ptsP; t->d_grp = grp; t->d_q16 = q16; t->Mp = (size_t)slots;
-  return TDTK_OK;
-}
-
-static int tree_finish(Ctx* c, tdtk_tree* t, size_t M)
-{
-  int prc = tree_pad_buckets(c, t, M);
-  if (prc) return prc;
-  for (int a = 0; a < 3; a++) t->centre[a] = 0.5 * (t->bbmin[a] + t->bbmax[a]);
-  // the compact hot records (fp32 box + split value + children) the big-batch search kernel walks
-  double am = 0.0;
-  for (int a = 0; a < 3; a++) am = std::max(am, std::max(std::fabs(t->bbmin[a]), std::fabs(t->bbmax[a])));
-  t->dev.absmax = (float)std::min(am * 1.0000002, 3.0e38);
-  if (t->info.n_internal) {
-    // (+ the split halves on their own behind them, 16 bytes per node, for the visits that defer the quick check: ONE allocation,
-    // so that a lane picks between the two by an offset from the same base)
-    HIPCHK(handle_malloc(&t->d_hot, t->info.n_internal * (sizeof(KdHot) + sizeof(double2))));
-    t->d_split = static_cast<char*>(t->d_hot) + t->info.n_internal * sizeof(KdHot);
-    HIPCHK(launch_make_hot(static_cast<const KdNode*>(t->d_nodes), t->info.n_internal, static_cast<KdHot*>(t->d_hot), c->stream,
-                           static_cast<double2*>(t->d_split)));
-#ifdef TDTK_LAB
-    // ... and, on request only, the two-level records (a node with its children's hot parts): two tree levels per round
-    // trip are a measured negative both for the persistent-lane kernel (TDTK_FAT_NODES=1) and for the lane-group kernels of
-    // small batches (TDTK_FAT_SMALL=1); kernels.hip has the numbers
-    static const bool want_fat = [] {
-      const char *a = lab_env("TDTK_FAT_NODES"), *b = lab_env("TDTK_FAT_SMALL");
-      return (a && a[0] == '1') || (b && b[0] == '1');
-    }();
-    if (want_fat) {
-      HIPCHK(handle_malloc(&t->d_fat, t->info.n_internal * sizeof(KdFat)));
-      HIPCHK(launch_make_fat(static_cast<const KdNode*>(t->d_nodes), t->info.n_internal, static_cast<KdFat*>(t->d_fat), c->stream));
-    }
-#endif
-    HIPCHK(hipStreamSynchronize(c->stream));
-  }
-  if (t->d_grp && t->Mp == 0) {        // the padded layout was filled without a look of its own: its size now
-    if (!t->info.n_internal) HIPCHK(hipStreamSynchronize(c->stream));
-    uint32_t G = 0;
-    std::memcpy(&G, c->h_pin + Ctx::PIN_GROUPS, sizeof G);
-    t->Mp = 4ull * G;
-  }
-  flush_free_later(c);
-  t->dev.hot = static_cast<const KdHot*>(t->d_hot);
-  t->dev.n_hot = (uint32_t)t->info.n_internal;
-  t->dev.n_slots = (uint32_t)std::min<size_t>(t->Mp, 0xFFFFFFFFu);
-  t->dev.fat = static_cast<const KdFat*>(t->d_fat);
-  t->dev.nodes = static_cast<const KdNode*>(t->d_nodes);
-  t->dev.pts = static_cast<const KdPoint*>(t->d_pts);
-  t->dev.grp = static_cast<const float4*>(t->d_grp);
-  t->dev.q16 = static_cast<const uint32_t*>(t->d_q16);
-  t->dev.split = static_cast<const double2*>(t->d_split);
-  for (int a = 0; a < 3; a++) t->dev.q_lo[a] = t->q_lo[a];
-  t->dev.q_scale = t->q_scale;
-  t->dev.leaf_tab = static_cast<const LeafEntry*>(t->d_leaf);
-  t->dev.node_r = static_cast<const double*>(t->d_r);
-  t->dev.cmask = (t->dev.cb >= 32) ? 0xFFFFFFFFu : ((1u << t->dev.cb) - 1u);
-  t->info.n_points = M;
-  t->info.device_bytes = t->info.n_internal * (sizeof(KdNode) + sizeof(KdHot) + sizeof(double2) + (t->d_fat ? sizeof(KdFat) : 0) + sizeof(double)) + t->Mp * sizeof(KdPoint) +
-                         (t->d_grp ? t->Mp / 4 * 48 : 0) + (t->d_q16 ? t->Mp / 4 * 24 + 128 : 0) +
-                         (t->d_leaf ? t->info.n_leaves * sizeof(LeafEntry) : 0);
-  return TDTK_OK;
-}
-
-static int tree_check_args(size_t M, int bucket_size)
-{
-  if (bucket_size < 1) { set_error("bucket size must be >= 1"); return TDTK_EINVAL; }
-  if (M > (size_t)REF_VAL || M * sizeof(KdPoint) >= (1ull << 32)) {
-    set_error("model scan too large (30-bit references / 32-bit byte offsets: < 2^27 points)");
-    return TDTK_EINVAL;
-  }
-  return TDTK_OK;
-}
-
-int tdtk_tree_create(const double* xyz, size_t M, int bucket_size, int device, tdtk_tree** out)
-{
-  if (!out) { set_error("out is NULL"); return TDTK_EINVAL; }
-  *out = nullptr;
-  if (!xyz || M == 0) { set_error("cannot create kdtree with zero points"); return TDTK_EINVAL; }
-  Ctx* c;
-  int rc = get_ctx(device, &c);
-  if (rc) return rc;
-
-  const double t0 = now_ms();
-  std::unique_ptr<tdtk_tree> t(new tdtk_tree);
-  t->device = device; t->M = M; t->bucket = bucket_size;
-  if ((rc = tree_check_args(M, bucket_size))) return rc;
-  // device construction (build.hip): upload the points once, build level by level.  (The host builder, kd_build.cpp,
-  // is reachable through tdtk_tree_verify only -- it is the cross-check of this path, not an alternative to it.)
-  if ((rc = c->ws[WS_TMPA].ensure(3 * M * sizeof(double)))) return rc;
-  HIPCHK(hipMemcpyAsync(c->ws[WS_TMPA].p, xyz, 3 * M * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if ((rc = tree_from_device_points(c, t.get(), M, bucket_size, t0))) return rc;
-  if ((rc = tree_finish(c, t.get(), M))) return rc;
-  *out = t.release();
-  return TDTK_OK;
-}
-
-// KDtree over the points of a resident scan as they are now, in the caller's order -- what BasicScan builds
-// over "xyz reduced original" (basicScan.cc:702-728) when it is called before the scan has been moved: no trip
-// of the points through the host.
-int tdtk_tree_create_from_scan(const tdtk_scan* scan, int bucket_size, tdtk_tree** out)
-{
-  if (!out) { set_error("out is NULL"); return TDTK_EINVAL; }
-  *out = nullptr;
-  if (!scan || scan->N == 0) { set_error("cannot create kdtree with zero points"); return TDTK_EINVAL; }
-  Ctx* c;
-  int rc = get_ctx(scan->device, &c);
-  if (rc) return rc;
-  const double t0 = now_ms();
-  const size_t M = scan->N;
-  std::unique_ptr<tdtk_tree> t(new tdtk_tree);
-  t->device = scan->device; t->M = M; t->bucket = bucket_size;
-  if ((rc = tree_check_args(M, bucket_size))) return rc;
-  if ((rc = c->ws[WS_TMPA].ensure(3 * M * sizeof(double)))) return rc;
-  const bool saved = scan->ox != nullptr;   // moved since tdtk_scan_mark_original: the saved points are the original
-  if (!saved && (rc = scan_settle(c, scan))) return rc;
-  HIPCHK(launch_unsort_aos(saved ? scan->ox : scan->x, saved ? scan->oy : scan->y, saved ? scan->oz : scan->z,
-                           scan->d_order, M, c->ws[WS_TMPA].as<double>(), c->stream));
-  if ((rc = tree_from_device_points(c, t.get(), M, bucket_size, t0))) return rc;
-  if ((rc = tree_finish(c, t.get(), M))) return rc;
-  *out = t.release();
-  return TDTK_OK;
-}
-
-// KDtreeMetaManaged (src/slam6d/kdMeta.cc:34-134): one tree over the CURRENT points of several resident scans,
-// concatenated in the order given, each scan in its caller's order (prepareTempIndices, kdMeta.cc:60-79)
-int tdtk_tree_create_from_scans(tdtk_scan* const* scans, int nscans, int bucket_size, tdtk_tree** out)
-{
-  if (!out) { set_error("out is NULL"); return TDTK_EINVAL; }
-  *out = nullptr;
-  if (!scans || nscans <= 0 || !scans[0]) { set_error("cannot create kdtree with zero points"); return TDTK_EINVAL; }
-  size_t M = 0;
-  for (int i = 0; i < nscans; i++) {
-    if (!scans[i]) { set_error("NULL scan"); return TDTK_EINVAL; }
-    if (scans[i]->device != scans[0]->device) { set_error("scans live on different devices"); return TDTK_EINVAL; }
-    M += scans[i]->N;
-  }
-  if (M == 0) { set_error("cannot create kdtree with zero points"); return TDTK_EINVAL; }
-  Ctx* c;
-  int rc = get_ctx(scans[0]->device, &c);
-  if (rc) return rc;
-  const double t0 = now_ms();
-  std::unique_ptr<tdtk_tree> t(new tdtk_tree);
-  t->device = scans[0]->device; t->M = M; t->bucket = bucket_size;
-  if ((rc = tree_check_args(M, bucket_size))) return rc;
-  if ((rc = c->ws[WS_TMPA].ensure(3 * M * sizeof(double)))) return rc;
-  if ((rc = scans_settle(c, scans, nscans))) return rc;
-  size_t off = 0;
-  for (int i = 0; i < nscans; i++) {
-    const tdtk_scan* sc = scans[i];
-    HIPCHK(launch_unsort_aos(sc->x, sc->y, sc->z, sc->d_order, sc->N, c->ws[WS_TMPA].as<double>() + 3 * off, c->stream));
-    off += sc->N;
-  }
-  if ((rc = tree_from_device_points(c, t.get(), M, bucket_size, t0))) return rc;
-  if ((rc = tree_finish(c, t.get(), M))) return rc;
-  *out = t.release();
-  return TDTK_OK;
-}
-
-void tdtk_tree_destroy(tdtk_tree* t)
-{
-  if (!t) return;
-  // a batch of scan moves / link passes left running behind the fence may still read this tree: explicit wait, not
-  // hipFree's implicit device synchronisation
-  wait_deferred(t->device);
-  delete t;   // ~tdtk_tree releases the device arrays
-}
-
-int tdtk_tree_get_info(const tdtk_tree* t, tdtk_tree_info* info)
-{
-  if (!t || !info) { set_error("NULL argument"); return TDTK_EINVAL; }
-  *info = t->info;
-  return TDTK_OK;
-}
-
-}  // extern "C"
 
 // ------------------------------------------------------------------------------------------
 // internal: one search pass over SoA queries
@@ -881,7 +35,6 @@ static int prepare_overflow(Ctx* c, const tdtk_tree* t, size_t nq, SearchArgs& a
 // tdtk_last_kernel_ms, tdtk_last_timings) are a profiling aid and OFF unless asked for (tdtk_kernel_timing(1) or
 // TDTK_KERNEL_TIMING=1): four marker packets on the stream, two event waits and two read-outs per ICP iteration cost
 // 10 us of it -- 4 % of a 1M-point iteration, 19 % of an 81K-point one (0.2602 -> 0.2504 ms, 54.9 -> 44.4 us).
-static std::atomic<int> g_kernel_timing{-1};
 static bool kernel_timing()
 {
   int v = g_kernel_timing.load(std::memory_order_relaxed);
@@ -1383,536 +536,6 @@ int tdtk_find_closest(const tdtk_tree* t, const double* q, size_t K, double maxd
   if (d2) HIPCHK(hipMemcpyAsync(d2, c->ws[WS_TMPB].p, K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return TDTK_OK;
-}
-
-}  // extern "C"
-
-// ---- k-NN and fixed-radius search (query.hip) ------------------------------------------------
-// the K queries at d_q [K][3], spatially binned into WS_QX / WS_QY / WS_QZ (order: sorted position -> caller index), the
-// tree's walk arguments and the stack overflow area
-// (d_v: a second vector per query [K][3], carried through the bin into WS_DX / WS_DY / WS_DZ -- the cylinder, box and
-// segment queries)
-// (box: 6 doubles, the lower and upper corner the bin's grid spans instead of the tree's root box; n_walks: the number of
-// walks the overflow area is sized for, where that is not K -- the collision kernels bin their model and walk once per
-// (frame, model point))
-static int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K, QueryArgs& a, const double* d_v = nullptr,
-                         const double* box = nullptr, size_t n_walks = 0)
-{
-  int rc;
-  int ids[] = {WS_QX, WS_QY, WS_QZ};
-  for (int id : ids)
-    if ((rc = c->ws[id].ensure(K * sizeof(double)))) return rc;
-  if (d_v) {
-    int vids[] = {WS_DX, WS_DY, WS_DZ};
-    for (int id : vids)
-      if ((rc = c->ws[id].ensure(K * sizeof(double)))) return rc;
-  }
-  if ((rc = c->ws[WS_ORDER].ensure(K * sizeof(int32_t)))) return rc;
-  if ((rc = c->ws[WS_CELL].ensure(K * sizeof(uint32_t)))) return rc;
-  if ((rc = c->ws[WS_HIST].ensure(32768 * sizeof(uint32_t)))) return rc;
-  BinArgs b{};
-  b.q = d_q; b.dir = d_v; b.n = K;
-  for (int ax = 0; ax < 3; ax++) {
-    b.lo[ax] = box ? box[ax] : t->bbmin[ax];
-    const double ext = (box ? box[3 + ax] : t->bbmax[ax]) - b.lo[ax];
-    b.scale[ax] = (ext > 0) ? 32.0 / ext : 0.0;
-  }
-  b.hist = c->ws[WS_HIST].as<uint32_t>();
-  b.cell = c->ws[WS_CELL].as<uint32_t>();
-  b.sx = c->ws[WS_QX].as<double>(); b.sy = c->ws[WS_QY].as<double>(); b.sz = c->ws[WS_QZ].as<double>();
-  if (d_v) { b.sdx = c->ws[WS_DX].as<double>(); b.sdy = c->ws[WS_DY].as<double>(); b.sdz = c->ws[WS_DZ].as<double>(); }
-  b.order = c->ws[WS_ORDER].as<int32_t>();
-  HIPCHK(launch_bin(b, c->stream));
-  a = QueryArgs{};
-  a.node_r = t->dev.node_r; a.vx = b.sdx; a.vy = b.sdy; a.vz = b.sdz;
-  a.nodes = t->dev.nodes; a.pts = t->dev.pts; a.leaf_tab = t->dev.leaf_tab;
-  a.root_ref = t->dev.root_ref; a.cb = t->dev.cb; a.cmask = t->dev.cmask;
-  a.x = b.sx; a.y = b.sy; a.z = b.sz; a.order = b.order; a.n = K;
-  const size_t ovf = query_overflow_entries(n_walks ? n_walks : K, t->info.max_depth);
-  if (ovf) {
-    if ((rc = c->ws[WS_OVF_M2].ensure(ovf * sizeof(double)))) return rc;
-    if ((rc = c->ws[WS_OVF_REF].ensure(ovf * sizeof(uint32_t)))) return rc;
-    a.ovf_m2 = c->ws[WS_OVF_M2].as<double>();
-    a.ovf_ref = c->ws[WS_OVF_REF].as<uint32_t>();
-  }
-  return TDTK_OK;
-}
-
-static int knn_check_k(int k)
-{
-  if (k < 1) { set_error("k must be >= 1"); return TDTK_EINVAL; }
-  if (k > KNN_MAX_K) { set_error("k = " + std::to_string(k) + " exceeds the supported list capacity of " + std::to_string(KNN_MAX_K)); return TDTK_EUNSUP; }
-  return TDTK_OK;
-}
-
-// a tree over host points [n][3] for the normal estimators; the points stay in WS_TMPA (the build only reads them)
-static int normals_tree(Ctx* c, const double* xyz, size_t n, int bucket, int device, std::unique_ptr<tdtk_tree>& t)
-{
-  int rc;
-  t.reset(new tdtk_tree);
-  t->device = device; t->M = n; t->bucket = bucket;
-  if ((rc = tree_check_args(n, bucket))) return rc;
-  if ((rc = c->ws[WS_TMPA].ensure(3 * n * sizeof(double)))) return rc;
-  HIPCHK(hipMemcpyAsync(c->ws[WS_TMPA].p, xyz, 3 * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if ((rc = tree_from_device_points(c, t.get(), n, bucket, now_ms()))) return rc;
-  return tree_finish(c, t.get(), n);
-}
-
-// the K queries at q [K][3] uploaded to WS_TMPA -- with v, their second vectors [K][3] side by side behind them -- and
-// query_prepare over them
-static int query_begin(Ctx* c, const tdtk_tree* t, const double* q, const double* v, size_t K, QueryArgs& a)
-{
-  int rc;
-  if ((rc = c->ws[WS_TMPA].ensure((v ? 6 : 3) * K * sizeof(double)))) return rc;
-  double* dq = c->ws[WS_TMPA].as<double>();
-  double* dv = v ? dq + 3 * K : nullptr;
-  HIPCHK(hipMemcpyAsync(dq, q, 3 * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (v) HIPCHK(hipMemcpyAsync(dv, v, 3 * K * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  return query_prepare(c, t, dq, K, a, dv);
-}
-
-// The list queries -- the fixed radius (mode < 0; d2 nullable) and the four shape walks of query.hip (mode: ShapeMode, v
-// their second vector) -- in two walks: the count walk into WS_KPOS, the scan into WS_D2 (WS_ARENA its scratch), the offsets
-// to the host, and, where the caller's capacity holds the total, the fill walk into WS_IDX (and WS_TMPB for d2).
-// `noun`: what the capacity error counts
-static int list_query(const char* name, const char* noun, int mode, const tdtk_tree* t, const double* q, const double* v,
-                      size_t K, double r2, uint64_t* offsets, int32_t* idx, double* d2, size_t cap, uint64_t* total)
-{
-  Ctx* c;
-  int rc;
-  if ((rc = get_ctx(t->device, &c))) return rc;
-  offsets[0] = 0; *total = 0;
-  if (K == 0) return TDTK_OK;
-  hipStream_t s = c->stream;
-  const size_t tmpb = range_scan_temp_bytes(K);
-  QueryArgs a;
-  if ((rc = query_begin(c, t, q, v, K, a))) return rc;
-  if ((rc = c->ws[WS_KPOS].ensure((K + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = c->ws[WS_D2].ensure((K + 1) * sizeof(unsigned long long)))) return rc;
-  if ((rc = c->ws[WS_ARENA].ensure(tmpb + 256))) return rc;
-  a.r2 = r2;
-  a.counts = c->ws[WS_KPOS].as<uint32_t>();
-  unsigned long long* d_off = c->ws[WS_D2].as<unsigned long long>();
-  HIPCHK(hipMemsetAsync(a.counts + K, 0, sizeof(uint32_t), s));
-  HIPCHK(mode < 0 ? launch_range_count(a, s) : launch_shape_count(a, mode, s));
-  HIPCHK(launch_range_scan(a.counts, d_off, K, c->ws[WS_ARENA].p, tmpb, s));
-  HIPCHK(hipMemcpyAsync(offsets, d_off, (K + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const uint64_t tot = offsets[K];
-  *total = tot;
-  if (cap < tot) {
-    set_error(std::string(name) + ": " + std::to_string(tot) + " " + noun + ", capacity " + std::to_string(cap) + " (offsets and total are filled)");
-    return TDTK_EINVAL;
-  }
-  if (tot == 0) return TDTK_OK;
-  if (!idx) { set_error("idx is NULL"); return TDTK_EINVAL; }
-  if ((rc = c->ws[WS_IDX].ensure(tot * sizeof(int32_t)))) return rc;
-  if (d2 && (rc = c->ws[WS_TMPB].ensure(tot * sizeof(double)))) return rc;
-  a.offsets = d_off;
-  a.idx = c->ws[WS_IDX].as<int32_t>();
-  a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
-  HIPCHK(mode < 0 ? launch_range_fill(a, s) : launch_shape_fill(a, mode, s));
-  HIPCHK(hipMemcpyAsync(idx, a.idx, tot * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, tot * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return TDTK_OK;
-}
-
-extern "C" {
-
-int tdtk_knn_search(const tdtk_tree* t, const double* q, size_t K, int k, int32_t* idx, double* d2)
-{
-  if (!t || (!q && K) || (!idx && K)) { set_error("NULL argument"); return TDTK_EINVAL; }
-  int rc;
-  if ((rc = knn_check_k(k))) return rc;
-  Ctx* c;
-  if ((rc = get_ctx(t->device, &c))) return rc;
-  if (K == 0) return TDTK_OK;
-  const size_t L = K * (size_t)k;
-  QueryArgs a;
-  if ((rc = query_begin(c, t, q, nullptr, K, a))) return rc;
-  if ((rc = c->ws[WS_IDX].ensure(L * sizeof(int32_t)))) return rc;
-  if (d2 && (rc = c->ws[WS_TMPB].ensure(L * sizeof(double)))) return rc;
-  a.k = k;
-  a.idx = c->ws[WS_IDX].as<int32_t>();
-  a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
-  HIPCHK(launch_knn(a, false, c->stream));
-  HIPCHK(hipMemcpyAsync(idx, a.idx, L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return TDTK_OK;
-}
-
-int tdtk_knn_range_search(const tdtk_tree* t, const double* q, size_t K, int k, double sqRad2, int32_t* idx, double* d2,
-                          int32_t* counts)
-{
-  if (!t || (!q && K) || (!idx && K)) { set_error("NULL argument"); return TDTK_EINVAL; }
-  int rc;
-  if ((rc = knn_check_k(k))) return rc;
-  if (!std::isfinite(sqRad2)) { set_error("sqRad2 must be finite"); return TDTK_EINVAL; }
-  Ctx* c;
-  if ((rc = get_ctx(t->device, &c))) return rc;
-  if (K == 0) return TDTK_OK;
-  const size_t L = K * (size_t)k;
-  if (sqRad2 <= 0) {     // no Dist2 is below it: every list is empty, nothing to walk
-    std::fill(idx, idx + L, -1);
-    if (d2) std::fill(d2, d2 + L, -1.0);
-    if (counts) std::fill(counts, counts + K, 0);
-    return TDTK_OK;
-  }
-  QueryArgs a;
-  if ((rc = query_begin(c, t, q, nullptr, K, a))) return rc;
-  if ((rc = c->ws[WS_IDX].ensure((L + K) * sizeof(int32_t)))) return rc;       // WS_IDX: the lists | counts
-  if (d2 && (rc = c->ws[WS_TMPB].ensure(L * sizeof(double)))) return rc;
-  a.k = k;
-  a.r2 = sqRad2;
-  a.idx = c->ws[WS_IDX].as<int32_t>();
-  a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
-  a.nr_out = counts ? a.idx + L : nullptr;
-  HIPCHK(launch_knn_range(a, false, c->stream));
-  HIPCHK(hipMemcpyAsync(idx, a.idx, L * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, L * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (counts) HIPCHK(hipMemcpyAsync(counts, a.nr_out, K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return TDTK_OK;
-}
-
-int tdtk_fixed_range_search(const tdtk_tree* t, const double* q, size_t K, double sqRad2, uint64_t* offsets, int32_t* idx,
-                            double* d2, size_t cap, uint64_t* total)
-{
-  if (!t || (!q && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
-  return list_query("fixedRangeSearch", "neighbours", -1, t, q, nullptr, K, sqRad2, offsets, idx, d2, cap, total);
-}
-
-int tdtk_fixed_range_search_along_dir(const tdtk_tree* t, const double* p, const double* dir, size_t K, double maxdist2,
-                                      uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total)
-{
-  if (!t || ((!p || !dir) && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
-  return list_query("fixedRangeSearchAlongDir", "points", SHAPE_ALONG_DIR, t, p, dir, K, maxdist2, offsets, idx, nullptr, cap, total);
-}
-
-int tdtk_fixed_range_search_between(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
-                                    uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total)
-{
-  if (!t || ((!p || !p0) && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
-  return list_query("fixedRangeSearchBetween2Points", "points", SHAPE_BETWEEN, t, p, p0, K, maxdist2, offsets, idx, nullptr, cap, total);
-}
-
-int tdtk_aabb_search(const tdtk_tree* t, const double* lo, const double* hi, size_t K, uint64_t* offsets, int32_t* idx,
-                     size_t cap, uint64_t* total)
-{
-  if (!t || ((!lo || !hi) && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
-  // kdIndexed.cc:237-238, the comparison in the reference's sense (a NaN corner passes it); nothing is written or launched
-  for (size_t i = 0; i < 3 * K; i++)
-    if (lo[i] > hi[i]) { set_error("invalid bbox"); return TDTK_EINVAL; }
-  return list_query("AABBSearch", "points", SHAPE_AABB, t, lo, hi, K, 0.0, offsets, idx, nullptr, cap, total);
-}
-
-int tdtk_segment_search_all(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
-                            uint64_t* offsets, int32_t* idx, size_t cap, uint64_t* total)
-{
-  if (!t || ((!p || !p0) && K) || !offsets || !total) { set_error("NULL argument"); return TDTK_EINVAL; }
-  return list_query("segmentSearch_all", "points", SHAPE_SEGMENT, t, p, p0, K, maxdist2, offsets, idx, nullptr, cap, total);
-}
-
-int tdtk_segment_search_nearest(const tdtk_tree* t, const double* p, const double* p0, size_t K, double maxdist2,
-                                int32_t* idx, double* d2)
-{
-  if (!t || ((!p || !p0 || !idx) && K)) { set_error("NULL argument"); return TDTK_EINVAL; }
-  Ctx* c;
-  int rc;
-  if ((rc = get_ctx(t->device, &c))) return rc;
-  if (K == 0) return TDTK_OK;
-  hipStream_t s = c->stream;
-  QueryArgs a;
-  if ((rc = query_begin(c, t, p, p0, K, a))) return rc;
-  if ((rc = c->ws[WS_IDX].ensure(K * sizeof(int32_t)))) return rc;
-  if (d2 && (rc = c->ws[WS_TMPB].ensure(K * sizeof(double)))) return rc;
-  a.r2 = maxdist2;
-  a.idx = c->ws[WS_IDX].as<int32_t>();
-  a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
-  HIPCHK(launch_segment_nearest(a, s));
-  HIPCHK(hipMemcpyAsync(idx, a.idx, K * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, K * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return TDTK_OK;
-}
-
-}  // extern "C"
-
-// ---- collision detection along a trajectory (query.hip, "collision detection") ------------------------------------------
-// the checks the marking and the axis depth share; F * P items at most
-static int collide_check_args(const double* model, size_t P, const double* frames, size_t F, double radius)
-{
-  if (!model || (!frames && F)) { set_error("NULL argument"); return TDTK_EINVAL; }
-  if (P == 0) { set_error("the point model is empty"); return TDTK_EINVAL; }
-  if (!std::isfinite(radius) || !(radius > 0)) { set_error("radius must be finite and > 0"); return TDTK_EINVAL; }
-  size_t items;
-  if (__builtin_mul_overflow(F, P, &items)) { set_error("frames x model points exceeds size_t"); return TDTK_EINVAL; }
-  return TDTK_OK;
-}
-
-// the model [P][3] and the frames [F][16] side by side in WS_TMPB, the model binned on its own bounding box (a non-finite
-// coordinate takes no part in the box and lands in a border cell) into WS_QX / WS_QY / WS_QZ; `items` walks
-static int collide_prepare(Ctx* c, const tdtk_tree* t, const double* model, size_t P, const double* frames, size_t F,
-                           size_t items, double radius, QueryArgs& a)
-{
-  int rc;
-  if ((rc = c->ws[WS_TMPB].ensure((3 * P + 16 * F) * sizeof(double)))) return rc;
-  double* d_model = c->ws[WS_TMPB].as<double>();
-  double* d_frames = d_model + 3 * P;
-  HIPCHK(hipMemcpyAsync(d_model, model, 3 * P * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  if (F) HIPCHK(hipMemcpyAsync(d_frames, frames, 16 * F * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  double box[6] = {0, 0, 0, 0, 0, 0};
-  for (int ax = 0; ax < 3; ax++) {
-    bool any = false;
-    for (size_t i = 0; i < P; i++) {
-      const double v = model[3 * i + ax];
-      if (!std::isfinite(v)) continue;
-      if (!any || v < box[ax]) box[ax] = v;
-      if (!any || v > box[3 + ax]) box[3 + ax] = v;
-      any = true;
-    }
-  }
-  if ((rc = query_prepare(c, t, d_model, P, a, nullptr, box, items))) return rc;
-  a.order = nullptr;
-  a.n = items;
-  a.P = P;
-  a.frames = d_frames;
-  a.r2 = radius * radius;
-  return TDTK_OK;
-}
-
-// the points of env_xyz [M][3] whose mask byte is (take != 0) or is not (take == 0) set, in ascending index
-static std::vector<double> collide_compact(const double* env_xyz, size_t M, const uint8_t* colliding, int take)
-{
-  std::vector<double> out;
-  for (size_t i = 0; i < M; i++)
-    if ((colliding[i] != 0) == (take != 0)) out.insert(out.end(), env_xyz + 3 * i, env_xyz + 3 * i + 3);
-  return out;
-}
-
-extern "C" {
-
-int tdtk_collision_mark(const tdtk_tree* env, const double* model, size_t P, const double* frames, size_t F, double radius,
-                        int cmethod, uint8_t* colliding, uint64_t* num_colliding)
-{
-  if (!env || !colliding || !num_colliding) { set_error("NULL argument"); return TDTK_EINVAL; }
-  int rc;
-  if ((rc = collide_check_args(model, P, frames, F, radius))) return rc;
-  if (cmethod != 1 && cmethod != 2) { set_error("cmethod must be 1 (spheres) or 2 (segments)"); return TDTK_EINVAL; }
-  if (cmethod == 2 && F == 0) { set_error("the segment method needs a trajectory of at least one frame"); return TDTK_EINVAL; }
-  Ctx* c;
-  if ((rc = get_ctx(env->device, &c))) return rc;
-  hipStream_t s = c->stream;
-  const size_t M = env->M;
-  const size_t items = (cmethod == 1 ? F : F - 1) * P;
-  // WS_IDX: the count (8 bytes) | the mask
-  if ((rc = c->ws[WS_IDX].ensure(8 + M))) return rc;
-  unsigned long long* d_count = c->ws[WS_IDX].as<unsigned long long>();
-  uint8_t* d_mask = c->ws[WS_IDX].as<uint8_t>() + 8;
-  HIPCHK(hipMemsetAsync(c->ws[WS_IDX].p, 0, 8 + M, s));
-  if (items) {
-    QueryArgs a;
-    if ((rc = collide_prepare(c, env, model, P, frames, F, items, radius, a))) return rc;
-    a.mask = d_mask;
-    HIPCHK(launch_collide_mark(a, cmethod, s));
-    HIPCHK(launch_collide_count(d_mask, M, d_count, s));
-  }
-  unsigned long long count = 0;
-  HIPCHK(hipMemcpyAsync(colliding, d_mask, M, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&count, d_count, sizeof(count), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  *num_colliding = count;
-  return TDTK_OK;
-}
-
-int tdtk_collision_depth_closest(const double* env_xyz, size_t M, const uint8_t* colliding, int bucket, int device,
-                                 float* dist, uint64_t* n_unreached)
-{
-  if (!env_xyz || !colliding || !dist) { set_error("NULL argument"); return TDTK_EINVAL; }
-  size_t nc = 0;
-  for (size_t i = 0; i < M; i++) nc += colliding[i] != 0;
-  if (nc == 0) { set_error("no colliding point"); return TDTK_EINVAL; }
-  if (nc == M) { set_error("no non-colliding point (the tree would be empty)"); return TDTK_EINVAL; }
-  int rc;
-  if ((rc = tree_check_args(M - nc, bucket))) return rc;
-  Ctx* c;
-  if ((rc = get_ctx(device, &c))) return rc;
-  const std::vector<double> rest = collide_compact(env_xyz, M, colliding, 0);
-  const std::vector<double> hit = collide_compact(env_xyz, M, colliding, 1);
-  std::unique_ptr<tdtk_tree> t;
-  if ((rc = normals_tree(c, rest.data(), M - nc, bucket, device, t))) return rc;
-  std::vector<int32_t> idx(nc);
-  std::vector<double> d2(nc);
-  if ((rc = tdtk_find_closest(t.get(), hit.data(), nc, 1000000.0, idx.data(), d2.data()))) return rc;
-  uint64_t unreached = 0;
-  for (size_t i = 0; i < nc; i++) {
-    if (idx[i] < 0) { dist[i] = 1000.0f; ++unreached; }
-    else dist[i] = (float)std::sqrt(d2[i]);
-  }
-  if (n_unreached) *n_unreached = unreached;
-  return TDTK_OK;
-}
-
-int tdtk_collision_depth_axis(const double* env_xyz, size_t M, const uint8_t* colliding, const double* model, size_t P,
-                              const double* frames, size_t F, double radius, int bucket, int device, float* dist)
-{
-  if (!env_xyz || !colliding || !dist) { set_error("NULL argument"); return TDTK_EINVAL; }
-  int rc;
-  if ((rc = collide_check_args(model, P, frames, F, radius))) return rc;
-  size_t nc = 0;
-  for (size_t i = 0; i < M; i++) nc += colliding[i] != 0;
-  if (nc == 0) { set_error("no colliding point (the tree would be empty)"); return TDTK_EINVAL; }
-  if ((rc = tree_check_args(nc, bucket))) return rc;
-  Ctx* c;
-  if ((rc = get_ctx(device, &c))) return rc;
-  hipStream_t s = c->stream;
-  const std::vector<double> hit = collide_compact(env_xyz, M, colliding, 1);
-  std::unique_ptr<tdtk_tree> t;
-  if ((rc = normals_tree(c, hit.data(), nc, bucket, device, t))) return rc;
-  // WS_D2: the minima (the bits of fp64 squared distances); WS_IDX: the depths
-  if ((rc = c->ws[WS_D2].ensure(nc * sizeof(unsigned long long)))) return rc;
-  if ((rc = c->ws[WS_IDX].ensure(nc * sizeof(float)))) return rc;
-  unsigned long long* d_min = c->ws[WS_D2].as<unsigned long long>();
-  HIPCHK(launch_collide_depth_init(d_min, nc, s));
-  if (F) {
-    QueryArgs a;
-    if ((rc = collide_prepare(c, t.get(), model, P, frames, F, F * P, radius, a))) return rc;
-    a.dmin = d_min;
-    HIPCHK(launch_collide_depth_axis(a, s));
-  }
-  HIPCHK(launch_collide_depth_finish(d_min, nc, c->ws[WS_IDX].as<float>(), s));
-  HIPCHK(hipMemcpyAsync(dist, c->ws[WS_IDX].p, nc * sizeof(float), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return TDTK_OK;
-}
-
-}  // extern "C"
-
-// The four tree-based normal estimators between their argument checks and their launch, and after it.  Begin: the context,
-// the tree over xyz (the points stay in WS_TMPA and are the queries), WS_TMPB for the normals, WS_IDX for `ints` int32 of
-// lists and per-point values (0: none), query_prepare, the scanner position.  Finish: the normals, the lists (a.knn_out, L
-// int32) and one int32 per point from d_per_point to the host, each where the caller gave an array; then the synchronise
-struct NormalsRun {
-  Ctx* c;
-  std::unique_ptr<tdtk_tree> t;
-  QueryArgs a;
-  int32_t* ints;
-};
-
-static int normals_begin(NormalsRun& r, const double* xyz, size_t n, int bucket, int device, const double rPos[3], size_t ints)
-{
-  int rc;
-  if ((rc = get_ctx(device, &r.c))) return rc;
-  Ctx* c = r.c;
-  if ((rc = normals_tree(c, xyz, n, bucket, device, r.t))) return rc;
-  if ((rc = c->ws[WS_TMPB].ensure(3 * n * sizeof(double)))) return rc;
-  if (ints && (rc = c->ws[WS_IDX].ensure(ints * sizeof(int32_t)))) return rc;
-  if ((rc = query_prepare(c, r.t.get(), c->ws[WS_TMPA].as<double>(), n, r.a))) return rc;
-  r.a.rx = rPos[0]; r.a.ry = rPos[1]; r.a.rz = rPos[2];
-  r.a.normals = c->ws[WS_TMPB].as<double>();
-  r.ints = ints ? c->ws[WS_IDX].as<int32_t>() : nullptr;
-  return TDTK_OK;
-}
-
-static int normals_finish(NormalsRun& r, size_t n, double* normals_out, int32_t* lists_out, size_t L, int32_t* per_point_out,
-                          const int32_t* d_per_point)
-{
-  hipStream_t s = r.c->stream;
-  HIPCHK(hipMemcpyAsync(normals_out, r.a.normals, 3 * n * sizeof(double), hipMemcpyDeviceToHost, s));
-  if (lists_out) HIPCHK(hipMemcpyAsync(lists_out, r.a.knn_out, L * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  if (per_point_out) HIPCHK(hipMemcpyAsync(per_point_out, d_per_point, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return TDTK_OK;
-}
-
-extern "C" {
-
-int tdtk_normals_knn(const double* xyz, size_t n, int k, const double rPos[3], int bucket, int device, double* normals_out,
-                     int32_t* knn_out)
-{
-  if (!rPos) { set_error("rPos is NULL"); return TDTK_EINVAL; }
-  if (!xyz || n == 0) { set_error("Could not calculate normals, XYZ data is empty"); return TDTK_EINVAL; }
-  if (!normals_out) { set_error("NULL argument"); return TDTK_EINVAL; }
-  int rc;
-  if ((rc = knn_check_k(k))) return rc;
-  const size_t L = knn_out ? n * (size_t)k : 0;
-  NormalsRun r;
-  if ((rc = normals_begin(r, xyz, n, bucket, device, rPos, L))) return rc;
-  r.a.k = k;
-  r.a.knn_out = knn_out ? r.ints : nullptr;
-  HIPCHK(launch_knn(r.a, true, r.c->stream));
-  return normals_finish(r, n, normals_out, knn_out, L, nullptr, nullptr);
-}
-
-int tdtk_normals_range(const double* xyz, size_t n, double sqRad2, const double rPos[3], int bucket, int device,
-                       double* normals_out)
-{
-  if (!rPos) { set_error("rPos is NULL"); return TDTK_EINVAL; }
-  if (!xyz || n == 0) { set_error("Could not calculate normals, XYZ data is empty"); return TDTK_EINVAL; }
-  if (!normals_out) { set_error("NULL argument"); return TDTK_EINVAL; }
-  if (!(sqRad2 > 0)) { set_error("sqRad2 must be > 0 (an empty neighbourhood has no mean)"); return TDTK_EINVAL; }
-  int rc;
-  NormalsRun r;
-  if ((rc = normals_begin(r, xyz, n, bucket, device, rPos, 0))) return rc;
-  r.a.r2 = sqRad2;
-  HIPCHK(launch_range_normals(r.a, r.c->stream));
-  return normals_finish(r, n, normals_out, nullptr, 0, nullptr, nullptr);
-}
-
-int tdtk_normals_knn_range(const double* xyz, size_t n, int k, double sqRad2, const double rPos[3], int bucket, int device,
-                           double* normals_out, int32_t* knn_out, int32_t* counts_out)
-{
-  if (!rPos) { set_error("rPos is NULL"); return TDTK_EINVAL; }
-  if (!xyz || n == 0) { set_error("Could not calculate normals, XYZ data is empty"); return TDTK_EINVAL; }
-  if (!normals_out) { set_error("NULL argument"); return TDTK_EINVAL; }
-  if (k < 1) { set_error("k must be >= 1"); return TDTK_EINVAL; }
-  int rc;
-  if ((rc = tree_check_args(n, bucket))) return rc;
-  if ((rc = knn_check_k(k))) return rc;
-  if (!std::isfinite(sqRad2)) { set_error("sqRad2 must be finite"); return TDTK_EINVAL; }
-  if (!(sqRad2 > 0)) { set_error("sqRad2 must be > 0 (an empty neighbourhood has no mean)"); return TDTK_EINVAL; }
-  const size_t L = knn_out ? n * (size_t)k : 0;       // WS_IDX: the lists | counts
-  NormalsRun r;
-  if ((rc = normals_begin(r, xyz, n, bucket, device, rPos, L + n))) return rc;
-  r.a.k = k;
-  r.a.r2 = sqRad2;
-  r.a.knn_out = knn_out ? r.ints : nullptr;
-  r.a.nr_out = counts_out ? r.ints + L : nullptr;
-  HIPCHK(launch_knn_range(r.a, true, r.c->stream));
-  return normals_finish(r, n, normals_out, knn_out, L, counts_out, r.a.nr_out);
-}
-
-// the argument checks the two adaptive-k estimators share (normals.cc:123-125, 569-571)
-static int adaptive_check_args(const double* xyz, size_t n, int kmin, int kmax, const double* rPos, const double* normals_out)
-{
-  if (!rPos) { set_error("rPos is NULL"); return TDTK_EINVAL; }
-  if (!xyz || n == 0) { set_error("Could not calculate normals, XYZ data is empty"); return TDTK_EINVAL; }
-  if (!normals_out) { set_error("NULL argument"); return TDTK_EINVAL; }
-  if (kmin > kmax) { set_error("kmin must not be larger than kmax"); return TDTK_EINVAL; }
-  if (kmin < 0) { set_error("kmin must be >= 0"); return TDTK_EINVAL; }
-  return TDTK_OK;
-}
-
-int tdtk_normals_adaptive_knn(const double* xyz, size_t n, int kmin, int kmax, const double rPos[3], int bucket, int device,
-                              double* normals_out, int32_t* k_used, int32_t* knn_out)
-{
-  int rc;
-  if ((rc = adaptive_check_args(xyz, n, kmin, kmax, rPos, normals_out))) return rc;
-  if ((rc = tree_check_args(n, bucket))) return rc;
-  if (kmax > KNN_MAX_K - 1) {
-    set_error("kmax + 1 = " + std::to_string((long long)kmax + 1) + " exceeds the supported list capacity of " + std::to_string(KNN_MAX_K));
-    return TDTK_EUNSUP;
-  }
-  const size_t L = knn_out ? n * (size_t)(kmax + 1) : 0;       // WS_IDX: the lists | k_used
-  NormalsRun r;
-  if ((rc = normals_begin(r, xyz, n, bucket, device, rPos, L + n))) return rc;
-  r.a.kmin = kmin; r.a.kmax = kmax;
-  r.a.knn_out = knn_out ? r.ints : nullptr;
-  r.a.k_used = k_used ? r.ints + L : nullptr;
-  HIPCHK(launch_knn_adaptive(r.a, r.c->stream));
-  return normals_finish(r, n, normals_out, knn_out, L, k_used, r.a.k_used);
 }
 
 int tdtk_find_closest_along_dir(const tdtk_tree* t, const double* q, const double* dir, size_t K,
@@ -2705,157 +1328,6 @@ int tdtk_get_pt_pairs(const tdtk_tree* t, const double A[16], const double* xyz_
   return TDTK_OK;
 }
 
-// ---- diagnostics: is the resident tree bit-identical to the host builder's? ----------------------
-int tdtk_tree_verify(const tdtk_tree* t, uint64_t mismatches[4])
-{
-  if (!t || !mismatches) { set_error("NULL argument"); return TDTK_EINVAL; }
-  Ctx* c;
-  int rc = get_ctx(t->device, &c);
-  if (rc) return rc;
-  // The resident arrays, with the padding of the buckets to whole groups (tree_pad_buckets) undone: the leaves in the
-  // order of their (padded) starts give back the packed array and the references the builder emitted.
-  std::vector<KdPoint> padded(t->Mp);
-  HIPCHK(hipMemcpy(padded.data(), t->d_pts, padded.size() * sizeof(KdPoint), hipMemcpyDeviceToHost));
-  std::vector<KdNode> dn(t->info.n_internal);
-  std::vector<LeafEntry> dl;
-  if (!dn.empty()) HIPCHK(hipMemcpy(dn.data(), t->d_nodes, dn.size() * sizeof(KdNode), hipMemcpyDeviceToHost));
-  if (t->d_leaf) { dl.resize(t->info.n_leaves); HIPCHK(hipMemcpy(dl.data(), t->d_leaf, dl.size() * sizeof(LeafEntry), hipMemcpyDeviceToHost)); }
-  std::vector<KdPoint> pts;
-  uint64_t group_errors = 0;
-  // the search-side copies of a node's split half (the hot record's, and the 16-byte one the deferred quick check reads) say
-  // what the node says
-  if (t->d_hot && !dn.empty()) {
-    std::vector<KdHot> hot(dn.size());
-    HIPCHK(hipMemcpy(hot.data(), t->d_hot, hot.size() * sizeof(KdHot), hipMemcpyDeviceToHost));
-    struct Half { double splitval; uint32_t c1, c2; };
-    std::vector<Half> half;
-    if (t->d_split) { half.resize(dn.size()); HIPCHK(hipMemcpy(half.data(), t->d_split, half.size() * sizeof(Half), hipMemcpyDeviceToHost)); }
-    for (size_t i = 0; i < dn.size(); i++) {
-      if (std::memcmp(&hot[i].splitval, &dn[i].splitval, 8) != 0 || hot[i].c1 != dn[i].c1 || hot[i].c2 != dn[i].c2) group_errors++;
-      if (!half.empty() && (std::memcmp(&half[i].splitval, &dn[i].splitval, 8) != 0 || half[i].c1 != dn[i].c1 || half[i].c2 != dn[i].c2)) group_errors++;
-    }
-  }
-  if (t->d_grp) {
-    const uint32_t cbv = t->dev.cb, cm = (cbv >= 32) ? 0xFFFFFFFFu : ((1u << cbv) - 1u);
-    struct Run { uint32_t start, count; uint32_t* ref; LeafEntry* le; };
-    std::vector<Run> runs;
-    for (KdNode& nd : dn)
-      for (uint32_t* r : {&nd.c1, &nd.c2})
-        if (*r & REF_LEAF) {
-          const uint32_t v = *r & REF_VAL;
-          if (t->d_leaf) runs.push_back({(uint32_t)dl[v].start, (uint32_t)dl[v].count, nullptr, &dl[v]});
-          else runs.push_back({v >> cbv, v & cm, r, nullptr});
-        }
-    std::sort(runs.begin(), runs.end(), [](const Run& a, const Run& b) { return a.start < b.start; });
-    std::vector<float> shadow((size_t)t->Mp * 3);
-    HIPCHK(hipMemcpy(shadow.data(), t->d_grp, shadow.size() * sizeof(float), hipMemcpyDeviceToHost));
-    // the 16-bit shadow (TreeDev::q16): every slot's grid indices recomputed here with the grid the tree carries
-    std::vector<uint16_t> q16;
-    if (t->d_q16) {
-      q16.resize((size_t)t->Mp * 3);
-      HIPCHK(hipMemcpy(q16.data(), t->d_q16, q16.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    }
-    auto grid_index = [&](double v, int a) -> uint16_t {       // kernels.hip: q16_index
-      const double u = (v - t->q_lo[a]) * t->q_scale + 0.5;
-      int i = (!(u >= 0.0)) ? -32768 : ((!(u < 65536.0)) ? 32767 : (int)u - 32768);
-      return (uint16_t)(i & 0xFFFF);
-    };
-    pts.reserve(t->M);
-    uint32_t expect = 0;
-    for (const Run& r : runs) {
-      if (r.start != expect || (r.start & 3u) || r.count == 0 || (size_t)r.start + r.count > t->Mp) { group_errors++; break; }
-      const uint32_t packed = (uint32_t)pts.size(), ng = (r.count + 3u) >> 2;
-      for (uint32_t j = 0; j < 4 * ng; j++) {
-        const KdPoint& P = padded[r.start + j];
-        const KdPoint& L = padded[r.start + std::min(j, r.count - 1)];
-        if (j < r.count) pts.push_back(P);
-        else if (std::memcmp(&P, &L, sizeof P) != 0) group_errors++;     // a pad slot repeats the bucket's last point
-        const size_t g = (r.start + j) >> 2, k = j & 3u;
-        if (shadow[g * 12 + k] != (float)L.x || shadow[g * 12 + 4 + k] != (float)L.y || shadow[g * 12 + 8 + k] != (float)L.z) group_errors++;
-        if (!q16.empty()) {
-          // two slots per 12 bytes: { (x0, y0), (x1, y1), (z0, z1) } as six uint16
-          const size_t pr = (size_t)(r.start + j) >> 1, hi = (r.start + j) & 1u;
-          const uint16_t* w = &q16[pr * 6];
-          if (w[2 * hi] != grid_index(L.x, 0) || w[2 * hi + 1] != grid_index(L.y, 1) || w[4 + hi] != grid_index(L.z, 2)) group_errors++;
-        }
-      }
-      expect = r.start + 4 * ng;
-      if (r.le) r.le->start = (int32_t)packed;
-      else *r.ref = (*r.ref & ~REF_VAL) | (packed << cbv) | r.count;
-    }
-    if (expect != t->Mp || pts.size() != t->M) group_errors++;
-    if (group_errors) { mismatches[0] = mismatches[1] = mismatches[2] = 0; mismatches[3] = group_errors; return TDTK_OK; }
-  } else {
-    pts = padded;
-    if (group_errors) { mismatches[0] = mismatches[1] = mismatches[2] = 0; mismatches[3] = group_errors; return TDTK_OK; }
-  }
-  // recover the caller's array from the resident points (each carries its caller index)
-  std::vector<double> xyz(3 * t->M);
-  for (size_t k = 0; k < t->M; k++) {
-    const size_t o = (size_t)pts[k].orig;
-    if (o >= t->M) { mismatches[0] = mismatches[1] = mismatches[2] = 0; mismatches[3] = 1; return TDTK_OK; }
-    xyz[3 * o] = pts[k].x; xyz[3 * o + 1] = pts[k].y; xyz[3 * o + 2] = pts[k].z;
-  }
-  HostTree H;
-  std::string err;
-  if (!build_tree(xyz.data(), t->M, t->bucket, H, err)) { set_error(err); return TDTK_EINVAL; }
-  std::vector<KdNode> nodes(H.nodes.size());
-  std::vector<double> rr(H.nodes.size());
-  mismatches[0] = mismatches[1] = mismatches[2] = mismatches[3] = 0;
-  if (H.n_internal != t->info.n_internal || H.n_leaves != t->info.n_leaves || H.max_depth != t->info.max_depth ||
-      H.max_leaf_points != t->info.max_leaf_points || H.root_ref != t->dev.root_ref || (uint32_t)H.cb != t->dev.cb ||
-      H.table_mode != (t->d_leaf != nullptr))
-    mismatches[3] = 1;
-  if (mismatches[3] == 0) {
-    if (!nodes.empty()) {
-      nodes = dn;    // with the references pointing into the packed array again
-      HIPCHK(hipMemcpy(rr.data(), t->d_r, rr.size() * sizeof(double), hipMemcpyDeviceToHost));
-    }
-    for (size_t i = 0; i < nodes.size(); i++) {
-      const KdNode &a = nodes[i], &b = H.nodes[i];
-      // == on doubles: +0 and -0 compare equal (the sign of a zero box centre never decides anything)
-      if (!(a.cx == b.cx && a.cy == b.cy && a.cz == b.cz && a.hx == b.hx && a.hy == b.hy && a.hz == b.hz &&
-            a.splitval == b.splitval && a.c1 == b.c1 && a.c2 == b.c2)) {
-        mismatches[0]++;
-        if (kLab && lab_env("TDTK_VERIFY_DUMP"))
-          fprintf(stderr, "VERIFY node %zu: dev c(%.17g %.17g %.17g) h(%.17g %.17g %.17g) split %.17g c1 %08x c2 %08x\n"
-                          "            host c(%.17g %.17g %.17g) h(%.17g %.17g %.17g) split %.17g c1 %08x c2 %08x\n",
-                  i, a.cx, a.cy, a.cz, a.hx, a.hy, a.hz, a.splitval, a.c1, a.c2, b.cx, b.cy, b.cz, b.hx, b.hy, b.hz, b.splitval, b.c1, b.c2);
-      }
-      if (rr[i] != H.node_r[i]) mismatches[1]++;
-    }
-    for (size_t i = 0; i < pts.size(); i++)
-      if (!(pts[i].x == H.pts[i].x && pts[i].y == H.pts[i].y && pts[i].z == H.pts[i].z && pts[i].orig == H.pts[i].orig))
-        mismatches[2]++;
-    if (H.table_mode) {
-      std::vector<LeafEntry> lt = dl;
-      // leaf ids may be numbered differently; compare through the references instead
-      auto leaf_of = [&](const std::vector<LeafEntry>& tab, uint32_t ref) { return tab[ref & REF_VAL]; };
-      for (size_t i = 0; i < nodes.size(); i++)
-        for (int k = 0; k < 2; k++) {
-          const uint32_t ra = k ? nodes[i].c2 : nodes[i].c1, rb = k ? H.nodes[i].c2 : H.nodes[i].c1;
-          if ((ra & REF_LEAF) != (rb & REF_LEAF)) continue;
-          if (ra & REF_LEAF) {
-            const LeafEntry x = leaf_of(lt, ra), y = leaf_of(H.leaf_tab, rb);
-            if (x.start != y.start || x.count != y.count) mismatches[3]++;
-          }
-        }
-    }
-  }
-  return TDTK_OK;
-}
-
-// ---- host-only diagnostics -----------------------------------------------------------------
-int tdtk_host_tree_layout(const double* xyz, size_t M, int bucket_size, int32_t* perm_out, uint64_t stats[4])
-{
-  HostTree H;
-  std::string err;
-  if (!build_tree(xyz, M, bucket_size, H, err)) { set_error(err); return TDTK_EINVAL; }
-  if (perm_out)
-    for (size_t k = 0; k < M; k++) perm_out[k] = H.pts[k].orig;
-  if (stats) { stats[0] = H.n_internal; stats[1] = H.n_leaves; stats[2] = H.max_depth; stats[3] = H.max_leaf_points; }
-  return TDTK_OK;
-}
 int tdtk_host_m4inv(const double in[16], double out[16]) { return m4inv(in, out); }
 void tdtk_host_mmult(const double a[16], const double b[16], double out[16]) { mmult(a, b, out); }
 void tdtk_host_euler_to_matrix4(const double rPos[3], const double rPosTheta[3], double out[16]) { euler_to_matrix4(rPos, rPosTheta, out); }
@@ -2886,10 +1358,7 @@ int tdtk_solve_spd(const double* G, const double* B, int n, double* x)
 // Diagnostics (off by default): while on, every pass of tdtk_icp_match also hashes its correspondences on the device (k_idx_hash:
 // the K5 hash of SURVEY 8(c) over the caller-order index array) -- the loop's indices can then be compared with a CPU run of the reference's search
 // iteration by iteration at sizes where downloading a million indices per iteration is not an option.
-static std::atomic<int> g_icp_hashes{0};
 constexpr int ICP_HASH_CAP = 1024;
-// the words of the calling thread's last tdtk_icp_match, whatever device it ran on (no context is looked up, none created)
-static thread_local std::vector<uint64_t> t_last_hashes;
 int tdtk_icp_index_hashes(int on)
 {
   if (on < 0) return g_icp_hashes.load(std::memory_order_relaxed);     // a question, not a switch

@@ -1,4 +1,4 @@
-// Kernel argument blocks and launcher prototypes shared by kernels.hip and api.cpp.
+// Kernel argument blocks and launcher prototypes shared by kernels.hip and the api*.cpp files.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -397,7 +397,7 @@ constexpr bool BUCKET_Q16 = false;
 constexpr bool BUCKET_Q16 = true;
 #endif
 
-// One bucket of up to 4 * GRP_TRIP points, scanned through its fp32 shadow groups (tree_pad_buckets in api.cpp: buckets are
+// One bucket of up to 4 * GRP_TRIP points, scanned through its fp32 shadow groups (tree_pad_buckets in api_tree.cpp: buckets are
 // padded to whole groups of four slots, `start` is a multiple of 4).  pb = the fp64 point array, o0 = byte offset of the
 // bucket in it.  On return best / bk are what the reference's leaf loop (kdTreeImpl.h:351-357) leaves behind.
 __device__ __forceinline__ void bucket_scan_groups(const char* __restrict__ t_grp, const char* __restrict__ pb, const int start,
