@@ -53,6 +53,20 @@ def handle_pointcloud(pointmodel, environment, trajectory, radius, cmethod, buck
     return mask.astype(bool), int(num.value)
 
 
+def segment_colliding(environment, colliding=None, sqRad2=20.0, bucketSize=20, device=0):
+    """segment_colliding (src/collision/segment_colliding.cc:55-102): the colliding points in groups, every point joined
+    with the points of fixedRangeSearch(p, sqRad2) around it (the default 20 is the literal of line 61).  Returns the groups
+    as arrays of ascending environment indices, in ascending order of their smallest member: the connected components of
+    that relation (tdtk_cluster_radius), not what the reference's bookkeeping leaves of them (include/tdtk_hip.h).
+    `environment` is [M][3] or a KDtree over it; `colliding` [M] the mask of handle_pointcloud (None: every point)."""
+    tree = environment if isinstance(environment, KDtree) else KDtree(environment, bucketSize, device)
+    labels, n = tree.clusters(sqRad2, subset=colliding)
+    members = np.flatnonzero(labels >= 0)
+    order = members[np.argsort(labels[members], kind="stable")]
+    counts = np.bincount(labels[members], minlength=n)
+    return np.split(order, np.cumsum(counts)[:-1]) if n else []
+
+
 def calculate_collidingdist(environment, colliding, bucketSize=20, device=0, want_unreached=False):
     """calculate_collidingdist (collision_model.cc:637-712): for every colliding point, in ascending index, the float
     distance to the nearest non-colliding point (1000.0 where none lies within 1000; want_unreached: how many)."""

@@ -89,6 +89,9 @@ static int query_begin(Ctx* c, const tdtk_tree* t, const double* q, const double
   return query_prepare(c, t, dq, K, a, dv);
 }
 
+// tdtk_kernel_timing(1): HIP events around the count walk of a list query and the link walk of the clustering
+static bool walk_timed() { return g_kernel_timing.load(std::memory_order_relaxed) > 0; }
+
 // The list queries -- the fixed radius (mode < 0; d2 nullable) and the four shape walks of query.hip (mode: ShapeMode, v
 // their second vector) -- in two walks: the count walk into WS_KPOS, the scan into WS_D2 (WS_ARENA its scratch), the offsets
 // to the host, and, where the caller's capacity holds the total, the fill walk into WS_IDX (and WS_TMPB for d2).
@@ -112,7 +115,10 @@ static int list_query(const char* name, const char* noun, int mode, const tdtk_t
   a.counts = c->ws[WS_KPOS].as<uint32_t>();
   unsigned long long* d_off = c->ws[WS_D2].as<unsigned long long>();
   HIPCHK(hipMemsetAsync(a.counts + K, 0, sizeof(uint32_t), s));
+  const bool timed = walk_timed();      // tdtk_last_kernel_ms: the count walk
+  if (timed) HIPCHK(hipEventRecord(c->e0, s));
   HIPCHK(mode < 0 ? launch_range_count(a, s) : launch_shape_count(a, mode, s));
+  if (timed) { HIPCHK(hipEventRecord(c->e1, s)); c->ev_pending = true; }
   HIPCHK(launch_range_scan(a.counts, d_off, K, c->ws[WS_ARENA].p, tmpb, s));
   HIPCHK(hipMemcpyAsync(offsets, d_off, (K + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -403,6 +409,89 @@ int tdtk_collision_depth_axis(const double* env_xyz, size_t M, const uint8_t* co
   HIPCHK(launch_collide_depth_finish(d_min, nc, c->ws[WS_IDX].as<float>(), s));
   HIPCHK(hipMemcpyAsync(dist, c->ws[WS_IDX].p, nc * sizeof(float), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  return TDTK_OK;
+}
+
+}  // extern "C"
+
+// ---- radius clustering (query.hip, "radius clustering"; cluster_lane.h) ---------------------------------------------------
+static std::atomic<int> g_cluster_grid_cap{0};
+
+extern "C" {
+
+int tdtk_cluster_grid_cap(int blocks)
+{
+  return g_cluster_grid_cap.exchange(blocks > 0 ? blocks : 0, std::memory_order_relaxed);
+}
+
+int tdtk_cluster_radius(const tdtk_tree* t, double sqRad2, const uint8_t* subset, const double* normals, double min_abs_cos,
+                        uint32_t min_size, int32_t* labels, uint64_t* n_clusters, int32_t* first, uint32_t* sizes)
+{
+  if (!t || !labels || !n_clusters) { set_error("NULL argument"); return TDTK_EINVAL; }
+  if (!std::isfinite(sqRad2)) { set_error("sqRad2 must be finite"); return TDTK_EINVAL; }
+  if (normals && !(min_abs_cos >= 0.0 && min_abs_cos <= 1.0)) { set_error("min_abs_cos must lie in [0, 1]"); return TDTK_EINVAL; }
+  Ctx* c;
+  int rc;
+  if ((rc = get_ctx(t->device, &c))) return rc;
+  hipStream_t s = c->stream;
+  const size_t M = t->M, S = t->dev.n_slots;
+  // WS_KPOS: parent | ckey | csize, by slot.  WS_D2: cflag | cnum, [M + 1] each.  WS_IDX: labels | first | sizes, [M] each.
+  // WS_TMPA: the normals, WS_TMPB: the subset.  Nothing here has the size of a neighbour list
+  const size_t tmpb = scan_u32_temp_bytes(M + 1);
+  if ((rc = c->ws[WS_KPOS].ensure(3 * S * sizeof(uint32_t)))) return rc;
+  if ((rc = c->ws[WS_D2].ensure(2 * (M + 1) * sizeof(uint32_t)))) return rc;
+  if ((rc = c->ws[WS_IDX].ensure(3 * M * sizeof(uint32_t)))) return rc;
+  if ((rc = c->ws[WS_ARENA].ensure(tmpb + 256))) return rc;
+  if (normals && (rc = c->ws[WS_TMPA].ensure(3 * M * sizeof(double)))) return rc;
+  if (subset && (rc = c->ws[WS_TMPB].ensure(M))) return rc;
+  QueryArgs a{};
+  a.nodes = t->dev.nodes; a.pts = t->dev.pts; a.leaf_tab = t->dev.leaf_tab;
+  a.root_ref = t->dev.root_ref; a.cb = t->dev.cb; a.cmask = t->dev.cmask;
+  a.n = S;
+  a.r2 = sqRad2;
+  a.parent = c->ws[WS_KPOS].as<uint32_t>(); a.ckey = a.parent + S; a.csize = a.ckey + S;
+  a.cflag = c->ws[WS_D2].as<uint32_t>();
+  uint32_t* d_num = a.cflag + (M + 1);
+  a.cnum = d_num;
+  a.labels = c->ws[WS_IDX].as<int32_t>(); a.cfirst = a.labels + M; a.csizes_out = reinterpret_cast<uint32_t*>(a.cfirst + M);
+  a.min_size = min_size;
+  if (subset) {
+    HIPCHK(hipMemcpyAsync(c->ws[WS_TMPB].p, subset, M, hipMemcpyHostToDevice, s));
+    a.subset = c->ws[WS_TMPB].as<uint8_t>();
+  }
+  if (normals) {
+    HIPCHK(hipMemcpyAsync(c->ws[WS_TMPA].p, normals, 3 * M * sizeof(double), hipMemcpyHostToDevice, s));
+    a.cnormals = c->ws[WS_TMPA].as<double>();
+    a.min_cos = min_abs_cos;
+  }
+  HIPCHK(launch_cluster_init(a, s));
+  if (sqRad2 > 0) {      // otherwise no Dist2 is below it: every list is empty, every node a component of its own
+    const size_t ovf = query_overflow_entries(S, t->info.max_depth);
+    if (ovf) {
+      if ((rc = c->ws[WS_OVF_M2].ensure(ovf * sizeof(double)))) return rc;
+      if ((rc = c->ws[WS_OVF_REF].ensure(ovf * sizeof(uint32_t)))) return rc;
+      a.ovf_m2 = c->ws[WS_OVF_M2].as<double>();
+      a.ovf_ref = c->ws[WS_OVF_REF].as<uint32_t>();
+    }
+    const bool timed = walk_timed();    // tdtk_last_kernel_ms: the link walk
+    if (timed) HIPCHK(hipEventRecord(c->e0, s));
+    HIPCHK(launch_cluster_link(a, (uint32_t)g_cluster_grid_cap.load(std::memory_order_relaxed), s));
+    if (timed) { HIPCHK(hipEventRecord(c->e1, s)); c->ev_pending = true; }
+  }
+  HIPCHK(hipMemsetAsync(a.cflag, 0, (M + 1) * sizeof(uint32_t), s));
+  HIPCHK(launch_cluster_flatten(a, s));
+  HIPCHK(launch_scan_u32(a.cflag, d_num, M + 1, c->ws[WS_ARENA].p, tmpb, s));
+  HIPCHK(launch_cluster_label(a, s));
+  uint32_t n = 0;
+  HIPCHK(hipMemcpyAsync(labels, a.labels, M * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&n, d_num + M, sizeof n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *n_clusters = n;
+  if (n && (first || sizes)) {
+    if (first) HIPCHK(hipMemcpyAsync(first, a.cfirst, n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (sizes) HIPCHK(hipMemcpyAsync(sizes, a.csizes_out, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
   return TDTK_OK;
 }
 

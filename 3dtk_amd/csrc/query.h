@@ -24,6 +24,11 @@ hipError_t launch_collide_count(const uint8_t* mask, size_t M, unsigned long lon
 hipError_t launch_collide_depth_init(unsigned long long* dmin, size_t M, hipStream_t s);
 hipError_t launch_collide_depth_axis(const QueryArgs& a, hipStream_t s);          // a.dmin
 hipError_t launch_collide_depth_finish(const unsigned long long* dmin, size_t M, float* dist, hipStream_t s);
+// radius clustering (cluster_lane.h): a.n the tree's slots, a.parent / ckey / csize, a.subset, a.cnormals, a.min_cos, a.r2
+hipError_t launch_cluster_init(const QueryArgs& a, hipStream_t s);
+hipError_t launch_cluster_link(const QueryArgs& a, uint32_t max_blocks, hipStream_t s);   // max_blocks: a smaller grid (0: none)
+hipError_t launch_cluster_flatten(const QueryArgs& a, hipStream_t s);             // + a.cflag (zeroed), a.min_size
+hipError_t launch_cluster_label(const QueryArgs& a, hipStream_t s);               // a.cnum; a.labels, a.cfirst, a.csizes_out
 size_t range_scan_temp_bytes(size_t n);
 hipError_t launch_range_scan(const uint32_t* counts, unsigned long long* offsets, size_t n, void* tmp, size_t tmp_bytes,
                              hipStream_t s);

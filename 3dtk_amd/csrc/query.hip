@@ -3,7 +3,8 @@
 // _FixedRangeSearch (kdTreeImpl.h:585-625), _KNNRangeSearch (kdTreeImpl.h:684-745), calculateNormalsKNN / calculateNormalsRange with calculateNormal's PCA (normals.cc:369-439,
 // 442-516, 518-558), _fixedRangeSearchAlongDir / _fixedRangeSearchBetween2Points / _AABBSearch / _segmentSearch_all /
 // _segmentSearch_1NearestPoint (kdTreeImpl.h:432-577, 747-913); and collision_model's marking and axis depth fused over the
-// range and segment walks (collision_model.cc:312-430, 714-800).
+// range and segment walks (collision_model.cc:312-430, 714-800); and radius clustering, the connected components of the
+// fixed-radius graph (segment_colliding.cc:55-102), over the range walk under an emitter that hooks a union-find.
 //
 // This file holds what needs the device: the kernarg block, the lane stack's set-up, the register list, list_normal, the
 // kernels and the launchers.  The walks and everything else a lane does, with the rules of every walk, are in query_lane.h.
@@ -15,6 +16,7 @@
 #include "eigen3.h"
 #include "query.h"
 #include "query_lane.h"
+#include "cluster_lane.h"
 
 namespace tdtk {
 
@@ -546,6 +548,28 @@ __global__ void __launch_bounds__(256) k_collide_depth_finish(const unsigned lon
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < M; i += T) dist[i] = collide_depth_value(dmin[i]);
 }
 
+// ---- radius clustering (the per-item bodies and the argument for the union-find: cluster_lane.h) --------------------
+// a.n is the tree's slot count.  The link kernel has the launch shape of the collision kernels; the others are one pass over
+// the slots without a walk
+__global__ void __launch_bounds__(Q_BLOCK) k_cluster_link(const QueryArgs a_)
+{
+  const QueryArgs& a = q_args();
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) cluster_link_item(a, (uint32_t)q.i, q.st);
+}
+
+template <int STEP>
+__global__ void __launch_bounds__(256) k_cluster_pass(const QueryArgs a)
+{
+  const size_t T = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += T) {
+    if (STEP == 0) cluster_init_item(a, (uint32_t)i);
+    else if (STEP == 1) cluster_flatten_item(a, (uint32_t)i);
+    else if (STEP == 2) cluster_flag_item(a, (uint32_t)i);
+    else cluster_label_item(a, (uint32_t)i);
+  }
+}
+
 // ---- launchers -------------------------------------------------------------------------------------------------
 static uint32_t q_grid(size_t n, int block)
 {
@@ -652,6 +676,41 @@ hipError_t launch_collide_depth_finish(const unsigned long long* dmin, size_t M,
 {
   if (!M) return hipSuccess;
   hipLaunchKernelGGL(k_collide_depth_finish, dim3(q_grid(M, 256)), dim3(256), 0, s, dmin, M, dist);
+  return hipGetLastError();
+}
+
+// radius clustering: a.n slots.  max_blocks caps the link kernel's grid below q_grid's (0: q_grid's own) -- the result does not
+// depend on it; the overflow area is sized for q_grid(a.n), which is never smaller
+hipError_t launch_cluster_init(const QueryArgs& a, hipStream_t s)
+{
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_cluster_pass<0>, dim3(q_grid(a.n, 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_cluster_link(const QueryArgs& a, uint32_t max_blocks, hipStream_t s)
+{
+  if (!a.n) return hipSuccess;
+  uint32_t grid = q_grid(a.n, Q_BLOCK);
+  if (max_blocks && max_blocks < grid) grid = max_blocks;
+  hipLaunchKernelGGL(k_cluster_link, dim3(grid), dim3(Q_BLOCK), 0, s, a);
+  return hipGetLastError();
+}
+
+// flatten, then (a.cflag zeroed by the caller) the flags of the kept components
+hipError_t launch_cluster_flatten(const QueryArgs& a, hipStream_t s)
+{
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_cluster_pass<1>, dim3(q_grid(a.n, 256)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(k_cluster_pass<2>, dim3(q_grid(a.n, 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// behind the scan of a.cflag into a.cnum: a.labels, a.cfirst, a.csizes_out
+hipError_t launch_cluster_label(const QueryArgs& a, hipStream_t s)
+{
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_cluster_pass<3>, dim3(q_grid(a.n, 256)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -43,6 +43,20 @@ struct QueryArgs {
   size_t P;                    // model points
   uint8_t* mask;               // marking: [M], 1 where the model touches the tree's point (input order)
   unsigned long long* dmin;    // depth along the model's axis: [M] the bits of the smallest squared distance
+  // radius clustering (cluster_lane.h): n is the tree's slot count (TreeDev::n_slots), the queries are the tree's own points
+  // in leaf order (pts), r2 the squared radius.  Slot space: parent / ckey / csize; input-index space: everything else
+  uint32_t* parent;            // [n] union-find links
+  uint32_t* ckey;              // [n] at a root: the smallest input index of its component (0xFFFFFFFF: none)
+  uint32_t* csize;             // [n] at a root: the members of its component
+  const uint8_t* subset;       // [M] the nodes (nullable: every point)
+  const double* cnormals;      // [M][3] (nullable: no smoothness predicate)
+  double min_cos;              // an edge needs fabs(n_i . n_j) >= min_cos
+  uint32_t min_size;           // components below it are dropped
+  uint32_t* cflag;             // [M + 1] 1 at the key of every kept component; cnum: its exclusive scan (cnum[M]: n_clusters)
+  const uint32_t* cnum;
+  int32_t* labels;             // [M]
+  int32_t* cfirst;             // [M], the first n_clusters written
+  uint32_t* csizes_out;        // [M], the first n_clusters written
 };
 
 // the four list queries of the shape walks (launch_shape_count / launch_shape_fill)

@@ -289,6 +289,35 @@ class KDtree:
         n = int(total.value)
         return offsets, idx[:n].copy(), d2[:n].copy()
 
+    def clusters(self, sqRad2, subset=None, normals=None, max_angle_deg=None, min_size=1, want_sizes=False):
+        """tdtk_cluster_radius: the connected components of the fixed-radius graph over the tree's points (i and j joined
+        when Dist2 < sqRad2).  subset [n] (truthy: a node), normals [n][3] with max_angle_deg (an edge also needs the angle
+        between the two normals, or their opposites, to be at most that).  Returns (labels [n] int32, n_clusters), plus
+        (first, sizes) [n_clusters] with want_sizes: clusters in ascending order of their smallest member, -1 for points
+        outside the subset or in components below min_size."""
+        labels = np.empty(self.n, np.int32)
+        n = C.c_uint64(0)
+        sub = nrm = None
+        cos = 0.0
+        if subset is not None:
+            sub = np.ascontiguousarray(np.asarray(subset).astype(bool).astype(np.uint8))
+            if len(sub) != self.n:
+                raise ValueError("subset must have one entry per point of the tree")
+        if normals is not None:
+            nrm = f64(normals).reshape(-1, 3)
+            if len(nrm) != self.n:
+                raise ValueError("normals must have one row per point of the tree")
+            if max_angle_deg is None:
+                raise ValueError("normals need max_angle_deg")
+            cos = min(1.0, max(0.0, float(np.cos(np.deg2rad(float(max_angle_deg))))))
+        first = np.empty(self.n if want_sizes else 0, np.int32)
+        sizes = np.empty(self.n if want_sizes else 0, np.uint32)
+        check(lib().tdtk_cluster_radius(self._h, float(sqRad2), sub.ctypes.data if sub is not None else None,
+                                        dptr(nrm) if nrm is not None else None, cos, int(min_size), iptr(labels), C.byref(n),
+                                        first.ctypes.data if want_sizes else None, sizes.ctypes.data if want_sizes else None))
+        k = int(n.value)
+        return (labels, k, first[:k].copy(), sizes[:k].copy()) if want_sizes else (labels, k)
+
     def _shape_lists(self, fn, p, v, *maxdist2):
         """one of the four CSR list queries (tdtk_fixed_range_search's contract): (offsets [K+1] uint64, idx [offsets[K]]).
         Sizes the lists from the first call's total and asks again when they do not fit."""

@@ -242,6 +242,38 @@ int tdtk_collision_depth_closest(const double* env_xyz, size_t M, const uint8_t*
  * result is the reference's at any number of threads.  TDTK_EINVAL as tdtk_collision_mark, and with no colliding point. */
 int tdtk_collision_depth_axis(const double* env_xyz, size_t M, const uint8_t* colliding, const double* model, size_t P,
                               const double* frames, size_t F, double radius, int bucket, int device, float* dist);
+/* Radius (Euclidean) clustering: the connected components of the fixed-radius graph over the tree's points -- what
+ * src/collision/segment_colliding.cc:55-102 groups the colliding points by (its radius is the literal 20 of :61).
+ * RELATION: points i and j are joined exactly when j is in KDtreeIndexed::fixedRangeSearch(p_i, sqRad2), that is
+ * Dist2(p_i, p_j) < sqRad2 -- a strict '<', Dist2 = (dx*dx + dy*dy) + dz*dz in fp64 without FMA contraction, as everywhere
+ * in this library.  The relation is symmetric bit for bit and does not depend on the bucket size.
+ * DEVIATION: the result is pinned to that relation, NOT to the bookkeeping of segment_colliding.cc, which does not
+ * produce the components of its own relation: line 77 clears the list line 76 has just appended to when the neighbour is
+ * the point itself, and line 100 clears group2points[it], indexed by a POINT, where the merged group current_group was
+ * meant -- members are lost and groups survive empty or merged twice (tests/test_clusters_host.py keeps the evidence).
+ * NODES: the points with subset[i] != 0 (subset NULL: all M = n_points points; indices are those of the xyz given to
+ * tdtk_tree_create, counted through the concatenation for trees built from scans).  A point outside the subset gets label
+ * -1 and bridges nothing: clustering a subset on the full tree gives the partition a tree over the subset alone gives
+ * (segment_colliding's use: it reads the scan of colliding points).
+ * EDGES: Dist2 < sqRad2 and, when normals [M][3] is given, fabs((nx_i*nx_j + ny_i*ny_j) + nz_i*nz_j) >= min_abs_cos,
+ * evaluated in this sense (a NaN gives no edge).  This smoothness predicate is THIS LIBRARY'S OWN addition (the
+ * order-independent form of planar segmentation); the reference has no counterpart.  normals == NULL ignores min_abs_cos.
+ * CANONICAL NUMBERING: a component's key is its smallest member index.  Components with fewer than min_size members are
+ * dropped, their points get -1 (min_size 0 and 1 keep everything).  The kept components are numbered 0 .. n_clusters-1 in
+ * ascending key order; labels [M]: that number; first (nullable) [M]: first[c] the key, sizes (nullable) [M]: sizes[c] the
+ * member count of cluster c -- only the first n_clusters entries of both are written.  The output does not depend on the
+ * launch geometry, on the order of the atomics, on the bucket size or on earlier calls.
+ * sqRad2 <= 0 launches no walk: range lists are empty, every node is a component of its own.  (A point with a NaN
+ * coordinate would be one at any radius, not even its own neighbour -- but no tree holds one: tdtk_tree_create refuses
+ * non-finite coordinates, and the reference's constructor does not return on them.)
+ * TDTK_EINVAL, checked in this order before anything is launched or written: NULL t, labels or n_clusters; sqRad2
+ * non-finite; normals given and min_abs_cos outside [0, 1] or NaN.
+ * Nothing of the size of the neighbour lists exists anywhere: a lock-free union-find in leaf order (cluster_lane.h). */
+int tdtk_cluster_radius(const tdtk_tree* t, double sqRad2, const uint8_t* subset, const double* normals, double min_abs_cos,
+                        uint32_t min_size, int32_t* labels, uint64_t* n_clusters, int32_t* first, uint32_t* sizes);
+/* The largest grid (workgroups) the link kernel of tdtk_cluster_radius may take, process-wide; 0 (the default): no cap of
+ * its own.  A testing aid like tdtk_kernel_timing -- the labels do not depend on it.  Returns the previous setting. */
+int tdtk_cluster_grid_cap(int blocks);
 /* calculateNormalsKNN (normals.cc:442-516; calculateNormal :518-558): a KDtree(points, bucket) and, for every point, its
  * k nearest neighbours (itself included), their mean and covariance, the eigenvector of the smallest eigenvalue
  * (newmat EigenValues), oriented so that n . (p - rPos) >= 0, normalised.  normals_out [n][3] in point order (the

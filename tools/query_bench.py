@@ -26,6 +26,15 @@ Marking with both methods on the resident tree, and both depth calls end to end 
 sub-cloud included); next to them collision_model's loops over the reference library (tools/ref_query_loop.cc) on
 --ref-threads threads, whole, where oracle/_ref exists; --only-collision runs nothing else.
 
+--clusters adds radius clustering (tdtk_cluster_radius) on a 1M-point uniform cloud (density 1) at two radii: the
+fixed-radius leg's (20.6 neighbours per point: one giant component) and one near the percolation threshold (3 neighbours per
+point: many mid-sized components).  Per radius, in the same run: (1) the cluster call end to end and its link kernel alone,
+(2) the count walk of tdtk_fixed_range_search on the same inputs -- the same walk without the unions -- (both kernels from
+HIP events, tdtk_kernel_timing), (3) what a caller had to do without the entry point: tdtk_fixed_range_search end to end plus
+a union-find over its lists on the host (numpy, the fixture generator's), (4) the reference library's fixedRangeSearch loop
+over all points on ONE host thread, as segment_colliding's loop is serial (where oracle/_ref exists); --only-clusters runs
+nothing else.
+
 Kernel times: run the same command under `rocprofv3 --kernel-trace --stats` (k_knn_reg, k_range_count / k_range_fill,
 k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest, k_knn_adaptive_reg / k_knn_adaptive_lds, k_ann_adaptive, k_knnr_reg / k_knnr_lds,
 k_collide_mark, k_collide_depth_axis)."""
@@ -277,6 +286,67 @@ def collision_legs(tdtk, reps, threads):
     return out
 
 
+def cluster_legs(tdtk, reps):
+    """tdtk_cluster_radius next to the count walk, to the lists + host union-find, and to the reference's serial loop"""
+    import ctypes as C
+    spec = importlib.util.spec_from_file_location("make_golden_clusters", os.path.join(ROOT, "tests", "golden", "make_golden_clusters.py"))
+    mg = importlib.util.module_from_spec(spec); spec.loader.exec_module(mg)
+    pts = np.random.default_rng(2033).uniform(-50, 50, (1_000_000, 3))
+    kd = tdtk.KDtree(pts, 20)
+    L = tdtk.lib()
+    out = {}
+
+    def kernel_ms(fn):
+        """min over reps warm runs of the kernel the library's events bracket in fn (the link walk / the count walk)"""
+        was = L.tdtk_kernel_timing(1)
+        ms = C.c_double(0.0)
+        ts = []
+        try:
+            for i in range(reps + 1):
+                fn()
+                L.tdtk_last_kernel_ms(C.byref(ms))
+                if i:
+                    ts.append(ms.value)
+        finally:
+            L.tdtk_kernel_timing(was)
+        return round(min(ts), 3)
+
+    legs = (("20nn", (20.0 * 3 / (4 * np.pi)) ** (2.0 / 3.0)), ("3nn", (3.0 * 3 / (4 * np.pi)) ** (2.0 / 3.0)))
+    for tag, r2 in legs:
+        out["clusters_%s_1M" % tag] = timed(lambda: kd.clusters(r2), reps)
+        out["clusters_%s_1M_link_kernel_ms" % tag] = kernel_ms(lambda: kd.clusters(r2))
+        labels, k, first, sizes = kd.clusters(r2, want_sizes=True)
+        out["clusters_%s_1M_n" % tag] = k
+        out["clusters_%s_1M_largest" % tag] = int(sizes.max())
+        out["clusters_%s_1M_of_100_or_more" % tag] = int((sizes >= 100).sum())
+        out["range_%s_1M" % tag] = timed(lambda: kd.fixedRangeSearchBatch(pts, r2), reps)
+        out["range_%s_1M_count_kernel_ms" % tag] = kernel_ms(lambda: kd.fixedRangeSearchBatch(pts, r2))
+        off, idx, _ = kd.fixedRangeSearchBatch(pts, r2)
+        out["range_%s_1M_mean_list" % tag] = round(float(off[-1]) / len(pts), 2)
+        ei = np.repeat(np.arange(len(pts)), np.diff(off.astype(np.int64)))
+
+        def host_uf():
+            return mg.canonical(mg.components(len(pts), ei, idx.astype(np.int64)))
+        out["host_union_find_%s_1M" % tag] = timed(host_uf, reps)
+        out["clusters_%s_1M_equal_host_union_find" % tag] = bool(np.array_equal(host_uf()[0], labels))
+    from oracle import orc
+    if not orc.have_ref():
+        return out
+    Lq = _ref_loop_lib()
+    Lq.ref_query_loop.restype = C.c_double
+    Lq.ref_query_loop.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.c_int, C.c_int, C.c_double,
+                                  C.c_int, C.POINTER(C.c_ulonglong)]
+    t = mg.ColRef(pts, 20)
+    fn = C.cast(t.c_range, C.c_void_p)
+    qp = t.pts.ctypes.data_as(C.POINTER(C.c_double))
+    found = C.c_ulonglong(0)
+    for tag, r2 in legs:
+        Lq.ref_query_loop(fn, t.kdi, qp, 2000, 1, 0, float(r2), 1, C.byref(found))     # warm
+        ms = Lq.ref_query_loop(fn, t.kdi, qp, len(pts), 1, 0, float(r2), 1, C.byref(found))
+        out["ref_host_1thread_range_loop_%s_1M_ms" % tag] = round(ms, 1)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000000,10000000")
@@ -291,6 +361,8 @@ def main():
     ap.add_argument("--only-hybrid", action="store_true", help="those legs alone")
     ap.add_argument("--collision", action="store_true", help="add the collision-detection legs (1M points, 3M items)")
     ap.add_argument("--only-collision", action="store_true", help="those legs alone")
+    ap.add_argument("--clusters", action="store_true", help="add the radius-clustering legs (1M points, two radii)")
+    ap.add_argument("--only-clusters", action="store_true", help="those legs alone")
     args = ap.parse_args()
     tdtk = importlib.import_module("3dtk_amd")
     if tdtk.device_count() < 1:
@@ -320,6 +392,11 @@ def main():
     if args.collision or args.only_collision:
         out.update(collision_legs(tdtk, args.reps, args.ref_threads))
         if args.only_collision:
+            print(json.dumps(out))
+            return
+    if args.clusters or args.only_clusters:
+        out.update(cluster_legs(tdtk, args.reps))
+        if args.only_clusters:
             print(json.dumps(out))
             return
     for M in [int(s) for s in args.sizes.split(",")]:
