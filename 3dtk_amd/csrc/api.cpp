@@ -2751,10 +2751,16 @@ int tdtk_graph_solve_update(int backend, int nlinks, const int32_t* from, const 
       sum_position_diff += std::sqrt(a1[12] * a1[12] + a1[13] * a1[13] + a1[14] * a1[14]);
     }
   } else {
-    // gapx6D::doGraphSlam6D (gapx6D.cc:323-542).  state = T (3n), kept over the iterations of one call
-    if (!state) { set_error("gapx6D needs its translation state vector"); return TDTK_EINVAL; }
+    // gapx6D::doGraphSlam6D (gapx6D.cc:323-542).  state = T (3n) | B (3n x 3n) | A (3n), all kept over the iterations
+    // of one call as the reference keeps them: T accumulates (:467-471); the rotation system's B is zeroed before the
+    // loop only (:359-366); and the one vector A serves both systems -- zeroed after the rotation solve (:458), filled
+    // by the translation step (:459-462) and not zeroed again, so the rotation system of iteration k + 1 starts from
+    // the translation system's right hand side of iteration k:  (B_1 + ... + B_k) X = A_trans,k-1 + A_rot,k
+    if (!state) { set_error("gapx6D needs its state vector"); return TDTK_EINVAL; }
     const int N = 3 * n;
-    std::vector<double> B((size_t)N * N, 0.0), A((size_t)N, 0.0), X((size_t)N);
+    double* B = state + (size_t)N;
+    double* A = state + (size_t)N + (size_t)N * N;
+    std::vector<double> X((size_t)N);
     for (int l = 0; l < nlinks; l++) {
       const double* b = blocks + (size_t)l * Bn;
       if (b[0] == 0.0) continue;
@@ -2777,10 +2783,13 @@ int tdtk_graph_solve_update(int backend, int nlinks, const int32_t* from, const 
       std::vector<double> S((size_t)N * N);
       for (int i = 0; i < N; i++)
         for (int j = i; j < N; j++) S[(size_t)i * N + j] = S[(size_t)j * N + i] = B[(size_t)i * N + j];
-      if (!solve_spd_dense(N, S.data(), A.data(), X.data(), 0.00001)) { set_error("matrix is not positive definite"); return TDTK_ESOLVE; }
+      std::vector<double> rhs(A, A + N);
+      if (!solve_spd_dense(N, S.data(), rhs.data(), X.data(), 0.00001)) { set_error("matrix is not positive definite"); return TDTK_ESOLVE; }
     }
-    // translation system (genBAtransForLinkedPair, gapx6D.cc:76-137)
-    std::vector<double> Bt((size_t)n * n, 0.0), At((size_t)N, 0.0), Bti((size_t)n * n);
+    // translation system (genBAtransForLinkedPair, gapx6D.cc:76-137), into the same A
+    std::vector<double> Bt((size_t)n * n, 0.0), Bti((size_t)n * n);
+    double* At = A;
+    std::fill(At, At + N, 0.0);
     auto rot_apply = [&](const double* x, const double* p, double* out) {
       double a16[16];
       const double zero[3] = {0, 0, 0};

@@ -270,12 +270,13 @@ GRAPH_LUMEULER, GRAPH_LUMQUAT, GRAPH_GHELIX, GRAPH_GAPX = 1, 2, 3, 4      # the 
 
 def graph_state(backend, nscans):
     """the vector a back-end carries over the iterations of one doGraphSlam6D call: ghelix6DQ2's B | bd
-    (ghelix6DQ2.cc:329-330), gapx6D's T (gapx6D.cc:356); None for the LUM back-ends"""
+    (ghelix6DQ2.cc:329-330), gapx6D's T | B | A (gapx6D.cc:359-366, :458-462: the rotation system's matrix is zeroed before the
+    loop only, and its right hand side starts from the translation system's of the iteration before); None for the LUM back-ends"""
     n = nscans - 1
     if backend == GRAPH_GHELIX:
         return np.zeros((6 * n) * (6 * n) + 6 * n)
     if backend == GRAPH_GAPX:
-        return np.zeros(3 * n)
+        return np.zeros(3 * n + (3 * n) * (3 * n) + 3 * n)
     return None
 
 
@@ -387,7 +388,7 @@ def ghelix_iteration(gr, allScans, max_dist_match2, state, group=None, device=No
 
 
 def gapx_iteration(gr, allScans, max_dist_match2, T, group=None, device=None):
-    """gapx6D::doGraphSlam6D, one iteration (src/slam6d/gapx6D.cc:323-542); T = graph_state(4, n)"""
+    """gapx6D::doGraphSlam6D, one iteration (src/slam6d/gapx6D.cc:323-542); T = graph_state(4, nscans)"""
     return graph_iteration(GRAPH_GAPX, gr, allScans, max_dist_match2, T, group, device)
 
 

@@ -1390,9 +1390,8 @@ class gapx6D(_graphSlam6D_setters):
         self.group = group
 
     def doGraphSlam6D(self, gr, allScans, nrIt, device=None):
-        from .graphslam import gapx_iteration
-        n = gr.getNrScans() - 1
-        T = np.zeros(3 * n)                 # not reset between iterations (gapx6D.cc:356,463-468)
+        from .graphslam import gapx_iteration, graph_state
+        T = graph_state(4, gr.getNrScans())     # T, B and A: not reset between iterations (gapx6D.cc:359-366, 458-471)
         ret = float("inf")
         it = 0
         while it < nrIt and ret > self.epsilonLUM:

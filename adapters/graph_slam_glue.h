@@ -26,9 +26,9 @@ double hip_graph_slam(int backend, GraphT& gr, std::vector<ScanT*>& allScans, in
   const int nscans = gr.getNrScans(), nlinks = gr.getNrLinks(), n = nscans - 1;
   int rank = 0, world = 1;
   if (comm) tdtk_comm_info(comm, &rank, &world, 0);
-  // what ghelix6DQ2 / gapx6D carry over the iterations of one call (ghelix6DQ2.cc:329-330, gapx6D.cc:356)
+  // what ghelix6DQ2 / gapx6D carry over the iterations of one call (ghelix6DQ2.cc:329-330; gapx6D.cc:359-366, :458-462: T, B and A)
   std::vector<double> state(backend == TDTK_GRAPH_GHELIX ? (size_t)36 * n * n + 6 * n
-                            : backend == TDTK_GRAPH_GAPX ? (size_t)3 * n : 0, 0.0);
+                            : backend == TDTK_GRAPH_GAPX ? (size_t)6 * n + (size_t)9 * n * n : 0, 0.0);
   std::vector<int32_t> from(nlinks), to(nlinks), owner(nlinks);
   for (int i = 0; i < nlinks; i++) { from[i] = gr.getLink(i, 0); to[i] = gr.getLink(i, 1); }
   std::vector<uint64_t> npts(nscans);

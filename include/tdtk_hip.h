@@ -412,7 +412,7 @@ int tdtk_links_pair_sums(int nlinks, const tdtk_tree* const* first, const double
  *   1..nscans-1: transMat / dalignxf [nscans][16], rPos / rPosTheta [nscans][3] are updated in place, resident
  *   scans (scans[i] may be NULL) are moved, xf_out [nscans][32] (nullable) receives the one or two transforms
  *   applied per scan.  state: ghelix6DQ2's B | bd ((6n)^2 + 6n doubles, zeroed once per doGraphSlam6D call),
- *   gapx6D's T (3n, likewise); NULL for the LUM back-ends.  *ret = what doGraphSlam6D's loop tests.       */
+ *   gapx6D's T | B | A (3n + (3n)^2 + 3n, likewise); NULL for the LUM back-ends.  *ret = what doGraphSlam6D's loop tests.       */
 enum { TDTK_GRAPH_LUMEULER = 1, TDTK_GRAPH_LUMQUAT = 2, TDTK_GRAPH_GHELIX = 3, TDTK_GRAPH_GAPX = 4 };
 int tdtk_graph_block_doubles(int backend);
 int tdtk_graph_link_blocks(int backend, int nlinks, const tdtk_tree* const* first, const double* first_dalignxf,

@@ -6,9 +6,11 @@ The heavy per-point work is done by oracle/oracle.c (oracle/orc.py).
 
 Each function cites the reference file:line it follows.  PINNED by tests/test_oracle_vs_ref.py
 against the reference's own minimizer TUs (oracle/_ref) and the committed fixtures in
-tests/golden/: the ten minimizers and the match loop.  PARITY UNPINNED (their TUs need Boost /
-SuiteSparse, so they cannot be compiled here; restated by reading): the graph back-ends, the
-sparse solve, the clpairs graph, Point_Point_Error.
+tests/golden/: the ten minimizers and the match loop; by tests/test_graph_backends_reference_host.py
+against k16_graph_backends.npz (the reference's own lum6Deuler.cc / lum6Dquat.cc / ghelix6DQ2.cc /
+gapx6D.cc / graphSlam6D.cc, compiled by the fixture's generator): the graph back-ends' per-link
+blocks, scatter rules, drop rule and pose updates.  PARITY UNPINNED (restated by reading):
+CSparse's factorisation, the clpairs graph, Point_Point_Error.
 
 The eigen / SVD / Cholesky kernels use numpy.linalg (LAPACK) where the reference uses a
 closed-form quartic + LU (icp6Dquat.cc:405-513), newmat SVD and Numerical-Recipes Cholesky:
@@ -1042,7 +1044,7 @@ def elch_close_loop_slerp(scans, first, last, edges, algo, max_dist_match2, max_
 
 
 # ---------------------------------------------------------------------------------------
-# lum6DQuat (-G 2), src/slam6d/lum6Dquat.cc   (parity unpinned: the TU needs scan.h -> Boost)
+# lum6DQuat (-G 2), src/slam6d/lum6Dquat.cc   (pinned: tests/test_graph_backends_reference_host.py)
 # ---------------------------------------------------------------------------------------
 def covariance_quat(first, second, maxdist2):
     """lum6DQuat::covarianceQuat (lum6Dquat.cc:81-248) -> (C 7x7, CD 7, m, ss)"""
@@ -1072,8 +1074,9 @@ def covariance_quat(first, second, maxdist2):
     e1 = dy - (D[1] + y * D[3] + z * D[4] - x * D[6])
     e2 = dz - (D[2] + z * D[3] - y * D[4] + x * D[5])
     ss = float((e0 * e0 + e1 * e1 + e2 * e2).sum()) / (2 * m - 3)
-    ssi = 1.0 / ss
-    return MM * ssi, MZ * ssi, m, ss
+    with np.errstate(divide="ignore", invalid="ignore"):      # no guard here (unlike covarianceEuler): ss == 0 gives inf / NaN
+        ssi = np.float64(1.0) / np.float64(ss)
+        return MM * ssi, MZ * ssi, m, ss
 
 
 def lumquat_pose_update(scan, Xi):
@@ -1124,7 +1127,7 @@ def lumquat_iteration(links, scans, maxdist2):
 
 
 # ---------------------------------------------------------------------------------------
-# ghelix6DQ2 (-G 3), src/slam6d/ghelix6DQ2.cc   (parity unpinned, as above)
+# ghelix6DQ2 (-G 3), src/slam6d/ghelix6DQ2.cc   (pinned, as above)
 # ---------------------------------------------------------------------------------------
 def helix_compute_rt(ccs):
     """icp6D_HELIX::computeRt (icp6Dhelix.cc:144-206) for one 6-vector"""
@@ -1246,31 +1249,15 @@ def solve_chol_upper(G, B):
     return np.linalg.solve(L.T, np.linalg.solve(L, B))
 
 
-def gapx_iteration(links, scans, maxdist2, T=None):
-    """one iteration of gapx6D::doGraphSlam6D (gapx6D.cc:323-542).  T (translation vector) keeps
-    accumulating across iterations of one call, as the reference's does.  Returns (ret, T, X)."""
+def gapx_translate_and_move(links, scans, cms, cds, X, T, A=None):
+    """the rest of an iteration of gapx6D::doGraphSlam6D once X is solved (gapx6D.cc:456-529): the translation system
+    (genBAtransForLinkedPair, :76-137), T += Bt^-1 A, the pose update.  T is updated in place, and so is A (3n) if given:
+    it is left holding the translation system's right hand side, as the reference's is.  -> sum of |T_i|"""
     n = len(scans) - 1
-    B = np.zeros((3 * n, 3 * n)); A = np.zeros(3 * n)
-    T = np.zeros(3 * n) if T is None else T
-    cms, cds = [], []
-    sum_position_diff = 0.0
-    for (f, sx) in links:
-        r = get_pt_pairs(scans[f], scans[sx], maxdist2)
-        cms.append(r["cm"]); cds.append(r["cd"])
-        if r["n"] <= 1:
-            continue
-        MkMkt, DkDkt, MkDkt, DkMkt, Ak1, Ak2 = gapx_link_blocks(r["p1"], r["p2"], r["cm"])
-        a, b = f - 1, sx - 1
-        if f != 0:
-            A[a * 3:a * 3 + 3] += Ak1
-            B[a * 3:a * 3 + 3, a * 3:a * 3 + 3] += MkMkt
-            B[a * 3:a * 3 + 3, b * 3:b * 3 + 3] += DkMkt
-            B[b * 3:b * 3 + 3, a * 3:a * 3 + 3] += MkDkt
-        A[b * 3:b * 3 + 3] += Ak2
-        B[b * 3:b * 3 + 3, b * 3:b * 3 + 3] += DkDkt
-        sum_position_diff += 1.0                         # genBArotForLinkedPair returns 1.0 (sic)
-    X = solve_chol_upper(B, A)
-    Bt = np.zeros((n, n)); A = np.zeros(3 * n)
+    tot = 0.0
+    Bt = np.zeros((n, n))
+    A = np.zeros(3 * n) if A is None else A
+    A[:] = 0.0
     for (f, sx), cm, cd in zip(links, cms, cds):         # genBAtransForLinkedPair (gapx6D.cc:76-137)
         x = X[(f - 1) * 3:(f - 1) * 3 + 3] if f != 0 else np.zeros(3)
         pm = cm.copy(); orc.transform_points(compute_rt(x, np.zeros(3)), pm.reshape(1, 3))
@@ -1289,8 +1276,56 @@ def gapx_iteration(links, scans, maxdist2, T=None):
     for i in range(1, len(scans)):
         dx = T[(i - 1) * 3:(i - 1) * 3 + 3]
         scans[i].transform(compute_rt(X[(i - 1) * 3:(i - 1) * 3 + 3], dx))
-        sum_position_diff += float(np.sqrt(dx[0] * dx[0] + dx[1] * dx[1] + dx[2] * dx[2]))
-    return sum_position_diff / len(scans), T, X
+        tot += float(np.sqrt(dx[0] * dx[0] + dx[1] * dx[1] + dx[2] * dx[2]))
+    return tot
+
+
+class GapxState:
+    """what gapx6D::doGraphSlam6D keeps over the iterations of one call: the translations T, the rotation system's
+    matrix B and the right hand side A that both systems share"""
+
+    def __init__(self, n, T=None):
+        self.T = np.zeros(3 * n) if T is None else np.asarray(T, np.float64)
+        self.B = np.zeros((3 * n, 3 * n))
+        self.A = np.zeros(3 * n)
+
+    def copy(self):
+        c = GapxState(len(self.T) // 3, self.T.copy())
+        c.B, c.A = self.B.copy(), self.A.copy()
+        return c
+
+
+def gapx_iteration(links, scans, maxdist2, state=None):
+    """one iteration of gapx6D::doGraphSlam6D (gapx6D.cc:323-542).  T (translation vector) keeps
+    accumulating across iterations of one call, as the reference's does -- and so does the rotation
+    system's matrix B, which is zeroed before the loop only (:359-366).  The vector A serves both
+    systems: zeroed after the rotation solve (:458), filled by the translation step and not zeroed
+    again, so the next iteration's rotation system starts from it.  Pass the returned GapxState back
+    in for the next iteration (None, or a bare T, starts B and A at zero).  Returns (ret, state, X)."""
+    n = len(scans) - 1
+    if not isinstance(state, GapxState):
+        state = GapxState(n, state)
+    T, B, A = state.T, state.B, state.A
+    cms, cds = [], []
+    sum_position_diff = 0.0
+    for (f, sx) in links:
+        r = get_pt_pairs(scans[f], scans[sx], maxdist2)
+        cms.append(r["cm"]); cds.append(r["cd"])
+        if r["n"] <= 1:
+            continue
+        MkMkt, DkDkt, MkDkt, DkMkt, Ak1, Ak2 = gapx_link_blocks(r["p1"], r["p2"], r["cm"])
+        a, b = f - 1, sx - 1
+        if f != 0:
+            A[a * 3:a * 3 + 3] += Ak1
+            B[a * 3:a * 3 + 3, a * 3:a * 3 + 3] += MkMkt
+            B[a * 3:a * 3 + 3, b * 3:b * 3 + 3] += DkMkt
+            B[b * 3:b * 3 + 3, a * 3:a * 3 + 3] += MkDkt
+        A[b * 3:b * 3 + 3] += Ak2
+        B[b * 3:b * 3 + 3, b * 3:b * 3 + 3] += DkDkt
+        sum_position_diff += 1.0                         # genBArotForLinkedPair returns 1.0 (sic)
+    X = solve_chol_upper(B, A)
+    sum_position_diff += gapx_translate_and_move(links, scans, cms, cds, X, T, A)
+    return sum_position_diff / len(scans), state, X
 
 
 # ---------------------------------------------------------------------------------------

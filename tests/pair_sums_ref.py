@@ -14,7 +14,8 @@ per column
 
 `finished` turns S into everything finish_sums (api.cpp) hands out, and `lum_link` into the MM / MZ / ss of
 tdtk_lum_links.  napx_A / napx_B are evaluated directly about the true data centroid, not through finish_sums'
-L A0 L^T transport.
+L A0 L^T transport.  The per-link blocks of the graph back-ends (tdtk_graph_link_blocks: lum6DQuat, ghelix6DQ2, gapx6D, and
+lum6DEuler's reference form) are at the end of the file, each in the reference's form and in the library's.
 
 The bound on a raw column
 -------------------------
@@ -585,3 +586,358 @@ def check_struct(s, fin, disc, producer):
         else:
             assert fin.n == 1 and f in CENTRED, (producer, f)
     print("pair-sums %-28s worst |error| / tolerance = %.3f  (n = %d)" % (producer, worst, fin.n))
+
+
+# ---- the graph back-ends' per-link blocks (lum6DQuat, ghelix6DQ2, gapx6D) -----------------------------------------------
+# Two forms per back-end.  The REFERENCE form evaluates the reference's own formulas term by term over the pair list in
+# np.longdouble: its values are what both the library and the reference are compared with.  Run over `VE` -- E for a whole
+# column of pairs at once, every +, -, * charged one rounding u |r| exactly as E does, halving free -- the same program
+# gives the tolerance of the reference itself: a pair's term carries the roundings it was computed with, and a left-to-right
+# fp64 sum of n of them is within gamma(n-1) sum |t| + sum e_t of their exact sum (Higham 4.2 again; no count is written
+# down by hand, the class counts).  The LIBRARY form starts from `finished` -- finish_sums' outputs with their tolerances
+# -- and runs the algebra of tdtk_graph_link_blocks (api.cpp), operation by operation, over E.
+# Inverses: both newmat's MM.i() (Crout LU, partial pivoting) and the library's invert_dense (Gauss-Jordan, partial pivoting)
+# are modelled by the Gauss-Jordan sweep of `_invert_E`; the first-order bound of one elimination with partial pivoting
+# stands for the other, whose operations are the same multiplications and subtractions in another order.
+class VE:
+    """values v[n] and first-order error bounds of a column of fp64 results (0-d arrays for scalars).  The bound has two
+    parts: e[n], the roundings, which add up in absolute value; and g[3][n], what an error of the three coordinates of one
+    shared input -- the centroid gapx6D centres on -- does to the result, signed and already multiplied by that input's own
+    bound, so that it cancels over a sum as the real thing does ((p1 - c) - (p2 - c) does not depend on c at all)."""
+    __slots__ = ("v", "e", "g")
+
+    def __init__(self, v, e=None, g=None):
+        self.v = np.asarray(v, LD)
+        self.e = np.zeros_like(self.v) if e is None else np.asarray(e, LD)
+        self.g = g
+
+    @staticmethod
+    def of(x):
+        if isinstance(x, VE):
+            return x
+        if isinstance(x, E):
+            return VE(x.v, x.e)
+        return VE(x)
+
+    @staticmethod
+    def shared(value, bound, axis):
+        """coordinate `axis` of the shared input: exact value, error up to `bound`"""
+        g = [LD(0), LD(0), LD(0)]
+        g[axis] = LD(bound)
+        return VE(value, None, g)
+
+    @staticmethod
+    def _g(a, fa, b, fb):
+        if a.g is None and b.g is None:
+            return None
+        za = a.g if a.g is not None else [LD(0)] * 3
+        zb = b.g if b.g is not None else [LD(0)] * 3
+        return [fa * za[k] + fb * zb[k] for k in range(3)]
+
+    def __add__(self, o):
+        o = VE.of(o)
+        v = self.v + o.v
+        return VE(v, self.e + o.e + U * np.abs(v), VE._g(self, 1, o, 1))
+    __radd__ = __add__
+
+    def __neg__(self):
+        return VE(-self.v, self.e, None if self.g is None else [-x for x in self.g])
+
+    def __sub__(self, o):
+        return self + (-VE.of(o))
+
+    def __rsub__(self, o):
+        return VE.of(o) + (-self)
+
+    def __mul__(self, o):
+        o = VE.of(o)
+        v = self.v * o.v
+        return VE(v, np.abs(self.v) * o.e + np.abs(o.v) * self.e + U * np.abs(v), VE._g(self, o.v, o, self.v))
+    __rmul__ = __mul__
+
+    def half(self):
+        return VE(self.v / 2, self.e / 2, None if self.g is None else [x / 2 for x in self.g])          # exact in fp64
+
+    def sum(self):
+        """a left-to-right (or any other) fp64 sum of the column -> E"""
+        n = self.v.size
+        shared = sum(abs(np.sum(np.broadcast_to(x, self.v.shape))) for x in self.g) if self.g is not None else 0
+        return E(self.v.sum(), self.e.sum() + gamma(n - 1) * np.abs(self.v).sum() + shared)
+
+
+def _invert_E(a, n):
+    """Gauss-Jordan with partial pivoting (invert_dense, linalg.cpp) over E: a [n][n] of E -> inverse [n][n] of E"""
+    a = [row[:] for row in a]
+    b = [[E(1.0 if r == c else 0.0) for c in range(n)] for r in range(n)]
+    for c in range(n):
+        piv = max(range(c, n), key=lambda r: (abs(a[r][c].v), -r))
+        if piv != c:
+            a[piv], a[c] = a[c], a[piv]; b[piv], b[c] = b[c], b[piv]
+        inv = 1.0 / a[c][c]
+        for r in range(n):
+            if r == c:
+                continue
+            f = a[r][c] * inv
+            if f.v == 0:
+                continue
+            for k in range(n):
+                a[r][k] = a[r][k] - f * a[c][k]
+                b[r][k] = b[r][k] - f * b[c][k]
+        for k in range(n):
+            a[c][k] = a[c][k] * inv
+            b[c][k] = b[c][k] * inv
+    return b
+
+
+def _matvec_E(M, x, n):
+    out = []
+    for r in range(n):
+        v = E(0.0)
+        for k in range(n):
+            v = v + M[r][k] * x[k]
+        out.append(v)
+    return out
+
+
+def _keep(p1, p2, drop):
+    p1 = np.asarray(p1, float).reshape(-1, 3); p2 = np.asarray(p2, float).reshape(-1, 3)
+    if drop is not None:
+        k = np.ones(len(p1), bool); k[drop] = False
+        p1, p2 = p1[k], p2[k]
+    return p1, p2
+
+
+def _quat_MM(m, sx, sy, sz, xpypz, ypz, xpz, xpy, xy, xz, yz):
+    """lum6Dquat.cc:167-188 / api.cpp: the symmetric 7 x 7 MM from its sums (E values)"""
+    MM = [[E(0.0) for _ in range(7)] for _ in range(7)]
+
+    def put(r, c, v):
+        MM[r][c] = v; MM[c][r] = v
+    put(0, 0, E(float(m))); put(1, 1, E(float(m))); put(2, 2, E(float(m)))
+    put(3, 3, xpypz); put(4, 4, ypz); put(5, 5, xpz); put(6, 6, xpy)
+    put(0, 3, sx); put(0, 5, -sz); put(0, 6, sy)
+    put(1, 3, sy); put(1, 4, sz); put(1, 6, -sx)
+    put(2, 3, sz); put(2, 4, -sy); put(2, 5, sx)
+    put(4, 5, -xy); put(4, 6, -xz); put(5, 6, -yz)
+    return MM
+
+
+class Link:
+    """q[name]: list of E (value, tolerance); n: pairs; ss (lum6DQuat only): E"""
+
+    def __init__(self, n):
+        self.n = n; self.q = {}; self.ss = None
+
+    def values(self, name):
+        return np.array([x.v for x in self.q[name]], LD)
+
+    def tols(self, name):
+        return np.array([x.e for x in self.q[name]], LD)
+
+
+def quat_link(p1, p2, drop=None):
+    """REFERENCE form of lum6DQuat::covarianceQuat (lum6Dquat.cc:129-215): C (49), CD (7) and MM, MZ, ss, term by term
+    and in the reference's order of operations.  None for n <= 2."""
+    p1, p2 = _keep(p1, p2, drop)
+    m = len(p1)
+    L = Link(m)
+    if m <= 2:
+        return L
+    ak = [VE(p1[:, a]) for a in range(3)]; bk = [VE(p2[:, a]) for a in range(3)]
+    x, y, z = [(ak[a] + bk[a]).half() for a in range(3)]
+    dx, dy, dz = [ak[a] - bk[a] for a in range(3)]
+    sx, sy, sz = x.sum(), y.sum(), z.sum()
+    xpy = (x * x + y * y).sum(); xpz = (x * x + z * z).sum(); ypz = (y * y + z * z).sum()
+    xpypz = (x * x + y * y + z * z).sum()
+    xy = (x * y).sum(); xz = (x * z).sum(); yz = (y * z).sum()
+    MZ = [dx.sum(), dy.sum(), dz.sum(), (x * dx + y * dy + z * dz).sum(), (z * dy - y * dz).sum(), (x * dz - z * dx).sum(),
+          (y * dx - x * dy).sum()]
+    MM = _quat_MM(m, sx, sy, sz, xpypz, ypz, xpz, xpy, xy, xz, yz)
+    D = [VE.of(d) for d in _matvec_E(_invert_E(MM, 7), MZ, 7)]
+    e0 = dx - (D[0] + x * D[3] - z * D[5] + y * D[6])
+    e1 = dy - (D[1] + y * D[3] + z * D[4] - x * D[6])
+    e2 = dz - (D[2] + z * D[3] - y * D[4] + x * D[5])
+    ss = (e0 * e0 + e1 * e1 + e2 * e2).sum() / (2.0 * m - 3.0)
+    L.ss = ss
+    L.q["MM"] = [v for row in MM for v in row]; L.q["MZ"] = MZ
+    if ss.v > 0:
+        si = 1.0 / ss
+        L.q["C"] = [v * si for v in L.q["MM"]]; L.q["CD"] = [v * si for v in MZ]
+    return L
+
+
+def euler_link(p1, p2, drop=None):
+    """REFERENCE form of lum6DEuler::covarianceEuler (lum6Deuler.cc:141-232): C (36), CD (6), MM, MZ, ss; below the guard
+    `ss < 1e-13` there is no C (the reference hands out zeros)"""
+    p1, p2 = _keep(p1, p2, drop)
+    m = len(p1)
+    L = Link(m)
+    if m <= 2:
+        return L
+    ak = [VE(p1[:, a]) for a in range(3)]; bk = [VE(p2[:, a]) for a in range(3)]
+    x, y, z = [(ak[a] + bk[a]).half() for a in range(3)]
+    dx, dy, dz = [ak[a] - bk[a] for a in range(3)]
+    sx, sy, sz = x.sum(), y.sum(), z.sum()
+    xpy = (x * x + y * y).sum(); xpz = (x * x + z * z).sum(); ypz = (y * y + z * z).sum()
+    xy = (x * y).sum(); xz = (x * z).sum(); yz = (y * z).sum()
+    MZ = [dx.sum(), dy.sum(), dz.sum(), (-z * dy + y * dz).sum(), (-y * dx + x * dy).sum(), (z * dx - x * dz).sum()]
+    MM = [[E(0.0) for _ in range(6)] for _ in range(6)]
+
+    def put(r, c, v):
+        MM[r][c] = v; MM[c][r] = v
+    put(0, 0, E(float(m))); put(1, 1, E(float(m))); put(2, 2, E(float(m)))
+    put(3, 3, ypz); put(4, 4, xpy); put(5, 5, xpz)
+    put(0, 4, -sy); put(0, 5, sz); put(1, 3, -sz); put(1, 4, sx); put(2, 3, sy); put(2, 5, -sx)
+    put(3, 4, -xz); put(3, 5, -xy); put(4, 5, -yz)
+    D = [VE.of(d) for d in _matvec_E(_invert_E(MM, 6), MZ, 6)]
+    e0 = dx - (D[0] - y * D[4] + z * D[5])
+    e1 = dy - (D[1] - z * D[3] + x * D[4])
+    e2 = dz - (D[2] + y * D[3] - x * D[5])
+    ss = (e0 * e0 + e1 * e1 + e2 * e2).sum() / (2.0 * m - 3.0)
+    L.ss = ss
+    L.q["MM"] = [v for row in MM for v in row]; L.q["MZ"] = MZ
+    if ss.v >= 0.0000000000001:
+        si = 1.0 / ss
+        L.q["C"] = [v * si for v in L.q["MM"]]; L.q["CD"] = [v * si for v in MZ]
+    return L
+
+
+def quat_link_lib(p1, p2, shift, drop=None, full=None):
+    """LIBRARY form: finish_sums (want LUM), then tdtk_graph_link_blocks' lum6DQuat branch: MM[3][3] from the three
+    second-moment sums halved, ss from the normal equations (sum - D . MZ) / (2m - 3) through invert_dense"""
+    fin = finished(p1, p2, None, shift, WANT_LUM, None, drop, full)
+    m = fin.n
+    L = Link(m); L.fin = fin
+    if m <= 2:
+        return L
+    lum = [E(v, e) for v, e in zip(fin.ref["lum"], fin.tol["lum"])]
+    udot = E(fin.ref["lum_udot"][0], fin.tol["lum_udot"][0]); ssum = E(fin.ref["sum"][0], fin.tol["sum"][0])
+    sx, sy, sz, xpy, xpz, ypz, xy, xz, yz = lum[:9]
+    MZ = [lum[9], lum[10], lum[11], udot, -lum[12], -lum[14], -lum[13]]
+    MM = _quat_MM(m, sx, sy, sz, (xpy + xpz + ypz) / 2.0, ypz, xpz, xpy, xy, xz, yz)
+    D = _matvec_E(_invert_E(MM, 7), MZ, 7)
+    dmz = E(0.0)
+    for r in range(7):
+        dmz = dmz + D[r] * MZ[r]
+    ss = (ssum - dmz) / (2.0 * float(m) - 3.0)
+    L.ss = ss
+    L.q["MM"] = [v for row in MM for v in row]; L.q["MZ"] = MZ
+    if ss.v > 0:
+        L.q["C"] = [v / ss for v in L.q["MM"]]; L.q["CD"] = [v / ss for v in MZ]
+    return L
+
+
+def helix_link(p1, p2, drop=None):
+    """REFERENCE form of ghelix6DQ2::genBBdForLinkedPair (ghelix6DQ2.cc:107-150): Blk (36, the block the scatter adds),
+    bd1 (6), bd2 (6)"""
+    p1, p2 = _keep(p1, p2, drop)
+    n = len(p1)
+    L = Link(n)
+    a = [VE(p1[:, k]) for k in range(3)]; b = [VE(p2[:, k]) for k in range(3)]
+    p1x, p1y, p1z = a; p2x, p2y, p2z = b
+    px2, py2, pz2 = p2x * p2x, p2y * p2y, p2z * p2z
+    b40, b50, b42 = (-p2z).sum(), p2y.sum(), p2x.sum()
+    b00, b10, b20 = (pz2 + py2).sum(), (p2y * -p2x).sum(), (-p2z * p2x).sum()
+    b11, b21, b22 = (pz2 + px2).sum(), (p2z * -p2y).sum(), (px2 + py2).sum()
+    dX, dY, dZ = p1x - p2x, p1y - p2y, p1z - p2z
+    bd1 = [(-p1z * dY + p1y * dZ).sum(), (p1z * dX - p1x * dZ).sum(), (-p1y * dX + p1x * dY).sum(), dX.sum(), dY.sum(), dZ.sum()]
+    bd2 = [(-p2z * -dY + p2y * -dZ).sum(), (p2z * -dX - p2x * -dZ).sum(), (-p2y * -dX + p2x * -dY).sum(), (-dX).sum(),
+           (-dY).sum(), (-dZ).sum()]
+    B = [[E(0.0) for _ in range(6)] for _ in range(6)]
+
+    def put(r, c, v):
+        B[r][c] = v; B[c][r] = v
+    for k in (3, 4, 5):
+        B[k][k] = E(float(n))
+    put(0, 4, b40); put(1, 3, -b40); put(0, 5, b50); put(2, 3, -b50); put(2, 4, b42); put(1, 5, -b42)
+    put(0, 1, b10); put(0, 2, b20); put(1, 2, b21)
+    B[0][0], B[1][1], B[2][2] = b00, b11, b22
+    L.q["Blk"] = [v for row in B for v in row]; L.q["bd1"] = bd1; L.q["bd2"] = bd2
+    return L
+
+
+def helix_link_lib(p1, p2, shift, drop=None, full=None):
+    """LIBRARY form: finish_sums (want MOM2), then the ghelix6DQ2 branch: raw moments as centred + m c c^T, bd1 the
+    antisymmetric part of Si + m cm cd^T; bd2 is not computed, the scatter uses -bd1"""
+    fin = finished(p1, p2, None, shift, WANT_MOM2, None, drop, full)
+    n = fin.n
+    L = Link(n); L.fin = fin
+    if n <= 1:
+        return L
+
+    def Es(name):
+        return [E(v, e) for v, e in zip(fin.ref[name], fin.tol[name])]
+    cm, cd, dd, Si = Es("centroid_m"), Es("centroid_d"), Es("mom_dd"), Es("Si")
+    m = float(n)
+    ddm = [[dd[0], dd[1], dd[2]], [dd[1], dd[3], dd[4]], [dd[2], dd[4], dd[5]]]
+    DD = [[ddm[r][c] + m * cd[r] * cd[c] for c in range(3)] for r in range(3)]
+    X = [[Si[r * 3 + c] + m * cm[r] * cd[c] for c in range(3)] for r in range(3)]
+    s2 = [m * cd[k] for k in range(3)]
+    B = [[E(0.0) for _ in range(6)] for _ in range(6)]
+
+    def put(r, c, v):
+        B[r][c] = v; B[c][r] = v
+    for k in (3, 4, 5):
+        B[k][k] = E(m)
+    put(0, 4, -s2[2]); put(1, 3, s2[2]); put(0, 5, s2[1]); put(2, 3, -s2[1]); put(2, 4, s2[0]); put(1, 5, -s2[0])
+    put(0, 1, -DD[0][1]); put(0, 2, -DD[0][2]); put(1, 2, -DD[1][2])
+    B[0][0], B[1][1], B[2][2] = DD[2][2] + DD[1][1], DD[2][2] + DD[0][0], DD[0][0] + DD[1][1]
+    bd1 = [X[2][1] - X[1][2], X[0][2] - X[2][0], X[1][0] - X[0][1]] + [m * (cm[k] - cd[k]) for k in range(3)]
+    L.q["Blk"] = [v for row in B for v in row]; L.q["bd1"] = bd1; L.q["bd2"] = [-v for v in bd1]
+    return L
+
+
+def centroids(p1, p2, drop=None):
+    """the pair list's centroids as Scan::getPtPairs forms them (a running fp64 sum, then one division): E values about
+    the exact centroid"""
+    p1, p2 = _keep(p1, p2, drop)
+    n = len(p1)
+    out = []
+    for p in (p1, p2):
+        out.append([VE(p[:, a]).sum() / float(n) for a in range(3)] if n else [E(0.0)] * 3)
+    return out
+
+
+def gapx_link(p1, p2, drop=None):
+    """REFERENCE form of gapx6D::genBArotForLinkedPair (gapx6D.cc:184-275), both points centred on centroids_m -- the
+    centroid as an E value, so that what its own rounding does to every term is part of the tolerance: MkMkt, DkDkt, MkDkt,
+    DkMkt (9 each, `p1x * p2x + p1y + p2y` as written), Ak1, Ak2, cm, cd"""
+    p1, p2 = _keep(p1, p2, drop)
+    n = len(p1)
+    L = Link(n)
+    cm, cd = centroids(p1, p2)
+    L.q["cm"] = cm; L.q["cd"] = cd
+    if n == 0:
+        return L
+    c = [VE.shared(cm[a].v, cm[a].e, a) for a in range(3)]
+    p1x, p1y, p1z = [VE(p1[:, a]) - c[a] for a in range(3)]
+    p2x, p2y, p2z = [VE(p2[:, a]) - c[a] for a in range(3)]
+    p1x2, p1y2, p1z2, p2x2, p2y2, p2z2 = p1x * p1x, p1y * p1y, p1z * p1z, p2x * p2x, p2y * p2y, p2z * p2z
+    d33 = (p1x * p2x + p1y + p2y).sum(); d22 = (p1x * p2x + p1z + p2z).sum(); d11 = (p1y * p2y + p1z + p2z).sum()
+    m01, m02, m12 = -(p1x * p1y).sum(), -(p1x * p1z).sum(), -(p1y * p1z).sum()
+    e01, e02, e12 = -(p2x * p2y).sum(), -(p2x * p2z).sum(), -(p2y * p2z).sum()
+    L.q["MkMkt"] = [(p1y2 + p1z2).sum(), m01, m02, m01, (p1x2 + p1z2).sum(), m12, m02, m12, (p1x2 + p1y2).sum()]
+    L.q["DkDkt"] = [(p2y2 + p2z2).sum(), e01, e02, e01, (p2x2 + p2z2).sum(), e12, e02, e12, (p2x2 + p2y2).sum()]
+    a01, a02, a12 = -(p1y * p2x).sum(), -(p1z * p2x).sum(), -(p1z * p2y).sum()
+    c01, c02, c12 = -(p2y * p1x).sum(), -(p2z * p1x).sum(), -(p2z * p1y).sum()
+    L.q["MkDkt"] = [d11, a01, a02, a01, d22, a12, a02, a12, d33]
+    L.q["DkMkt"] = [d11, c01, c02, c01, d22, c12, c02, c12, d33]
+    L.q["Ak1"] = [-(((p1z - p2z) * p2y - (p1y - p2y) * p2z).sum()), -(((p1x - p2x) * p2z - (p1z - p2z) * p2x).sum()),
+                  -(((p1y - p2y) * p2x - (p1x - p2x) * p2y).sum())]
+    L.q["Ak2"] = [((p1z - p2z) * p1y - (p1y - p2y) * p1z).sum(), ((p1x - p2x) * p1z - (p1z - p2z) * p1x).sum(),
+                  ((p1y - p2y) * p1x - (p1x - p2x) * p1y).sum()]
+    return L
+
+
+def gapx_link_lib(p1, p2, shift, drop=None, full=None):
+    """LIBRARY form: finish_sums (want GAPX) hands out the blocks as they are copied into the link block"""
+    fin = finished(p1, p2, None, shift, WANT_GAPX, None, drop, full)
+    L = Link(fin.n); L.fin = fin
+    for name, f in (("cm", "centroid_m"), ("cd", "centroid_d"), ("MkMkt", "gapx_MkMkt"), ("DkDkt", "gapx_DkDkt"),
+                    ("MkDkt", "gapx_MkDkt"), ("DkMkt", "gapx_DkMkt"), ("Ak1", "gapx_Ak1"), ("Ak2", "gapx_Ak2")):
+        L.q[name] = [E(v, e) for v, e in zip(fin.ref[f], fin.tol[f])]
+    return L
+
+
+REF_LINK = {1: euler_link, 2: quat_link, 3: helix_link, 4: gapx_link}
+LIB_LINK = {2: quat_link_lib, 3: helix_link_lib, 4: gapx_link_lib}
