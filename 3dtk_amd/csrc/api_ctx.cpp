@@ -298,8 +298,8 @@ void scan_queue_move(tdtk_scan* s, const double* A16)
 }
 
 // switches of single families, kept with the rest of the state
-std::atomic<int> g_kernel_timing{-1};     // api.cpp: kernel_timing
-std::atomic<int> g_icp_hashes{0};         // api.cpp: tdtk_icp_index_hashes
+std::atomic<int> g_kernel_timing{-1};     // api_search.cpp: kernel_timing
+std::atomic<int> g_icp_hashes{0};         // api_icp.cpp: tdtk_icp_index_hashes
 // the words of the calling thread's last tdtk_icp_match, whatever device it ran on (no context is looked up, none created)
 thread_local std::vector<uint64_t> t_last_hashes;
 

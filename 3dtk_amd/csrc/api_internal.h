@@ -166,8 +166,8 @@ extern std::atomic<int> g_ctx_live;             // host threads that hold a cont
 extern std::atomic<uint64_t> g_respeculated;   // tree builds whose speculative cuts failed the final check
 extern std::atomic<uint64_t> g_handle_uid;     // the next tree / scan handle's number
 extern std::recursive_mutex g_moves_mu;        // guards every scan's pending / npend / ax..az and the x <-> ax swap
-extern std::atomic<int> g_kernel_timing;       // api.cpp: kernel_timing
-extern std::atomic<int> g_icp_hashes;          // api.cpp: tdtk_icp_index_hashes
+extern std::atomic<int> g_kernel_timing;       // api_search.cpp: kernel_timing
+extern std::atomic<int> g_icp_hashes;          // api_icp.cpp: tdtk_icp_index_hashes
 extern thread_local std::vector<uint64_t> t_last_hashes;
 // longest chain a scan may carry: a rank that never reads a scan (seven of eight ranks, for most scans) carries it out
 // once per this many queued transforms -- one trip of the points through HBM per 16 rounds instead of one per round
@@ -193,6 +193,22 @@ int tree_finish(Ctx* c, tdtk_tree* t, size_t M);
 int tree_check_args(size_t M, int bucket_size);
 // api_query.cpp
 int adaptive_check_args(const double* xyz, size_t n, int kmin, int kmax, const double* rPos, const double* normals_out);
+// api_search.cpp
+constexpr uint64_t SUMS_ARMED = 0x7FF8DEADBEEF0001ull;   // a NaN no sum can produce: the word a host arms before it watches for a result
+int prepare_overflow_in(DevBuf& bm2, DevBuf& bref, const tdtk_tree* t, size_t nq, SearchArgs& a);
+bool kernel_timing();
+int run_search(Ctx* c, const tdtk_tree* t, SearchArgs& a, int dirmode, bool count, hipStream_t s, bool timed);
+int collect_ms(Ctx* c, double* ms, double* sums_ms = nullptr);
+int fuse_mode(size_t N);
+void finish_sums(const double* acc, const double shift[3], size_t nq, unsigned want, tdtk_pair_sums* o);
+double search_margin(const tdtk_tree* t, double maxd2);
+void pass_shift(const tdtk_tree* t, const double* A16, double out[3]);
+int scan_pass(Ctx* c, const tdtk_tree* model, const double* A16, tdtk_scan* data, int pmode, double maxd2,
+              unsigned want, const double* lum_D, const double* pending, bool do_search, double* acc_out,
+              double shift_out[3], bool warm = false, const unsigned char* skip = nullptr);
+int scan_idx_to_host(Ctx* c, const tdtk_tree* model, tdtk_scan* data, int32_t* idx_out);
+// api_scan.cpp
+int queue_scan_moves(Ctx* c, const std::vector<tdtk_scan*>& moved);
 
 }  // namespace tdtk
 

@@ -73,7 +73,7 @@ struct SearchArgs {
   // hit's d2 + 2 tie.  0: every visit makes the quick check.
   double tie;
   // warm: what the previous hit's d2 is widened by (twice this) to give the starting radius -- the rounding of the reference's
-  // quick check and split test (api.cpp: search_margin), so that no node holding the previous hit, or a nearer point, can be cut
+  // quick check and split test (api_search.cpp: search_margin), so that no node holding the previous hit, or a nearer point, can be cut
   // off by a rounding at a radius this tight.  Set whenever warm is; tie (above) is either 0 or equal to it.
   double margin;
   int warm;     // kpos holds the previous pass's hits of the SAME queries in the SAME tree: start each search with

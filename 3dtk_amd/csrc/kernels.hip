@@ -355,7 +355,7 @@ __device__ __forceinline__ uint32_t descend_which(const double splitval, const u
 // "Prunes only what lies at or beyond closest_d2" holds up to the ROUNDING of the tests themselves (the quick check's
 // a = max|q - c| - h carries ~2^-50 (3 absmax + R)): at a radius one ulp above the hit's own distance a rounding could cut off
 // the very node that holds the hit when q - p is almost axis-aligned, where the reference, walking with maxdist2, visits it.
-// The radius is therefore d2 + 2 * SearchArgs::margin (api.cpp: search_margin bounds that rounding, times four).
+// The radius is therefore d2 + 2 * SearchArgs::margin (api_search.cpp: search_margin bounds that rounding, times four).
 static __device__ __forceinline__ double warm_radius_kp(const SearchArgs& a, const int kp, const double qx, const double qy,
                                                         const double qz)
 {
@@ -1620,7 +1620,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   // per-lane mode -- round 5 -- one checking lane made its whole wave issue three loads per trip).  What a lane walks is the
   // reference's walk plus subtrees the reference would have cut off there; the order is the reference's, a point of such a
   // subtree lies at d2 >= closest_d2 - tie by the very test that was skipped (tie bounds 2 E R + E^2, E the rounding of
-  // fabs(q - center) - half-width against the exact face distance, R the search radius: api.cpp, search_tie), and the strict
+  // fabs(q - center) - half-width against the exact face distance, R the search radius: api_search.cpp, search_tie), and the strict
   // `<` never takes an equal one.  So as long as no accepted point improved closest_d2 by `tie` or less -- `thin` -- every
   // acceptance is one the reference makes, in its order: same index, same d2, same ties.
   // None of this needs a previous hit: an acceptance needs d2 < closest_d2 <= maxd2, hence |q| <= absmax + R, which is the
@@ -2368,7 +2368,7 @@ __global__ void __launch_bounds__(256) k_final(const double* __restrict__ partia
 {
   __shared__ double red[4];
   const int k = blockIdx.x;
-  // `out` may be pinned host memory the host is watching word by word (await_sums in api.cpp): each sum is published
+  // `out` may be pinned host memory the host is watching word by word (await_sums in api_search.cpp): each sum is published
   // with a store of system scope
   if (k >= ncols) {   // a column the pass did not fill (its rows hold +0.0): the same +0.0 without reading them
     if (threadIdx.x == 0) __hip_atomic_store(&out[k], 0.0, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);

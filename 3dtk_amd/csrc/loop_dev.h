@@ -6,7 +6,7 @@
 // (icp6Dquat.cc:38-144), launches the next search.  At 15K points that trip is a third of the iteration.  Here:
 //   * k_final's reduction of the partial rows, in k_final's association (256 row-striding adders per column, wave sums, a
 //     4-entry pass), so the 17 sums are the sums the host path reads, bit for bit;
-//   * finish_sums' centroids and centred covariance (api.cpp), Horn's matrix as linalg.cpp builds it;
+//   * finish_sums' centroids and centred covariance (api_search.cpp), Horn's matrix as linalg.cpp builds it;
 //   * the largest eigenvalue of that traceless symmetric 4x4 by Newton's iteration on its characteristic polynomial, started
 //     from an upper bound (all four roots are real, so Newton from above descends monotonically onto the largest) -- the
 //     reference takes the same polynomial and solves it in closed form (icp6Dquat.cc:405-513, Ferrari);
@@ -131,7 +131,7 @@ __device__ __forceinline__ bool largest_eigenvector(const Sym4& Q, double q[4])
   return v0 == v0 && v1 == v1 && v2 == v2 && v3 == v3;
 }
 
-// the 17 base sums about `shift` -> alignxf, RMS (finish_sums of api.cpp + align_from_sums' QUAT branch of linalg.cpp)
+// the 17 base sums about `shift` -> alignxf, RMS (finish_sums of api_search.cpp + align_from_sums' QUAT branch of linalg.cpp)
 __device__ __forceinline__ bool loop_quat_align(const double* acc, const double shift[3], double xf[16], double& rms)
 {
   const double n = acc[ACC_N];

@@ -355,7 +355,7 @@ void orc_find_closest(const orc_tree *t, const double *q, size_t K, double maxdi
 /* ---- the GPU kernel's "quick check deferred", stated on the reference's tree (test infrastructure for the ARGUMENT) ----------
  * 3dtk_amd/csrc/kernels.hip (search_refill_body<.., DEFER>) lets a query that starts from a previous hit walk WITHOUT the quick
  * check of kdTreeImpl.h:360-368 and searches it again, with every check, if it ever accepted a point that improved closest_d2
- * by `tie` or less (api.cpp: search_tie).  This is that rule on the pointer tree above, check skipped at EVERY node (the kernel
+ * by `tie` or less (api_search.cpp: search_tie).  This is that rule on the pointer tree above, check skipped at EVERY node (the kernel
  * skips it at some): tests/test_oracle_vs_ref.py runs it over clouds built to sit on the roundings the argument is about --
  * lattices with axis-aligned queries, twins 1e-12 apart, coordinates far from the origin -- and asks for orc_find_closest's
  * answer, index and d2, every time.  Nothing in the product calls it. */

@@ -12,7 +12,7 @@ per column
                                 bounded by what its roundings scale with, not by what is left after the cancellation
     IN_k = sum_i sum_a |d t_ik / d p1_a| u |p1_a|      (see "input term")
 
-`finished` turns S into everything finish_sums (api.cpp) hands out, and `lum_link` into the MM / MZ / ss of
+`finished` turns S into everything finish_sums (api_search.cpp) hands out, and `lum_link` into the MM / MZ / ss of
 tdtk_lum_links.  napx_A / napx_B are evaluated directly about the true data centroid, not through finish_sums'
 L A0 L^T transport.  The per-link blocks of the graph back-ends (tdtk_graph_link_blocks: lum6DQuat, ghelix6DQ2, gapx6D, and
 lum6DEuler's reference form) are at the end of the file, each in the reference's form and in the library's.
@@ -295,7 +295,7 @@ FIELDS = ("sum", "centroid_m", "centroid_d", "Si", "apx_A", "apx_B", "napx_A", "
 
 
 def _finish_E(raw, shift, want, has_D):
-    """finish_sums (api.cpp), operation by operation, over E(S_k, tol_k).  -> {field: list of E}; fields `want` does not
+    """finish_sums (api_search.cpp), operation by operation, over E(S_k, tol_k).  -> {field: list of E}; fields `want` does not
     ask for are absent (the library leaves them 0)."""
     tol = raw.tol
     acc = [E(raw.S[k], tol[k]) for k in range(ACC_TOTAL)]
@@ -444,7 +444,7 @@ def discrimination(p1, p2, pn, shift, want, D=None, fin=None):
 
 # ---- tdtk_lum_links ---------------------------------------------------------------------------------------------------
 def lum_link(p1, p2, drop=None, full=None):
-    """m, MM (36), MZ (6), ss of one lum6DEuler link (api.cpp tdtk_lum_links) as E values; ss through invert_dense's
+    """m, MM (36), MZ (6), ss of one lum6DEuler link (api_links.cpp tdtk_lum_links) as E values; ss through invert_dense's
     Gauss-Jordan elimination with partial pivoting, hand-written here over E.  m <= 2: MM, MZ, ss are None (the library
     hands out zero blocks)."""
     raw = raw_sums(p1, p2, None, [0.0, 0.0, 0.0], WANT_LUM | NO_CROSS, None, drop, full)
@@ -543,7 +543,7 @@ def make_inputs(N, pattern="all", far=False, seed=1):
 
 
 def shift_of(model, A):
-    """scan_pass' accumulation point: the model's box centre moved by A (api.cpp)"""
+    """the accumulation point of a pass: the model's box centre moved by A (pass_shift, api_search.cpp)"""
     c = 0.5 * (model.min(0) + model.max(0))
     return np.array([c[0] * A[k] + c[1] * A[4 + k] + c[2] * A[8 + k] + A[12 + k] for k in range(3)])
 
@@ -595,7 +595,7 @@ def check_struct(s, fin, disc, producer):
 # gives the tolerance of the reference itself: a pair's term carries the roundings it was computed with, and a left-to-right
 # fp64 sum of n of them is within gamma(n-1) sum |t| + sum e_t of their exact sum (Higham 4.2 again; no count is written
 # down by hand, the class counts).  The LIBRARY form starts from `finished` -- finish_sums' outputs with their tolerances
-# -- and runs the algebra of tdtk_graph_link_blocks (api.cpp), operation by operation, over E.
+# -- and runs the algebra of tdtk_graph_link_blocks (api_graph.cpp), operation by operation, over E.
 # Inverses: both newmat's MM.i() (Crout LU, partial pivoting) and the library's invert_dense (Gauss-Jordan, partial pivoting)
 # are modelled by the Gauss-Jordan sweep of `_invert_E`; the first-order bound of one elimination with partial pivoting
 # stands for the other, whose operations are the same multiplications and subtractions in another order.
@@ -708,7 +708,7 @@ def _keep(p1, p2, drop):
 
 
 def _quat_MM(m, sx, sy, sz, xpypz, ypz, xpz, xpy, xy, xz, yz):
-    """lum6Dquat.cc:167-188 / api.cpp: the symmetric 7 x 7 MM from its sums (E values)"""
+    """lum6Dquat.cc:167-188 / api_graph.cpp: the symmetric 7 x 7 MM from its sums (E values)"""
     MM = [[E(0.0) for _ in range(7)] for _ in range(7)]
 
     def put(r, c, v):

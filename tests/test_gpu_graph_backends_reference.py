@@ -159,7 +159,7 @@ def test_link_blocks(tdtk, orc, gpu, fx, case, backend):
             return float(np.min(np.where(t[moved] > 0, move[moved] / np.where(t[moved] > 0, t[moved], 1), np.inf))) if moved.any() else None
     unresolved = ("C", "CD") if (k <= 2 and case in SS_UNRESOLVED[k]) else ()
     if k <= 2 and not np.any(blk):
-        # the normal-equation ss came out under the guard (ss < 1e-13, api.cpp) and the library handed out a zero block where
+        # the normal-equation ss came out under the guard (ss < 1e-13, api_links.cpp / api_graph.cpp) and the library handed out a zero block where
         # the reference uses the link.  Admissible only where ss is unresolved and its tolerance reaches down to the guard
         assert unresolved and float(ref.ss.v - lib.ss.e) < 0.0000000000001, (case, k, float(ref.ss.v), float(lib.ss.e))
         print("graph-blocks %-10s %-14s ZERO BLOCK: ss = %.3g is inside its tolerance %.3g of the guard  (n = %d)"

@@ -233,7 +233,7 @@ def test_reference_and_restatement_blocks_within_derived_tolerance(fx, orc, case
 
 # ---- tdtk_graph_solve_update against the fixture --------------------------------------------------------------------------
 def repack(k, ref_blocks, npairs):
-    """the reference's per-link quantities in tdtk_graph_block_doubles layout (api.cpp tdtk_graph_link_blocks)"""
+    """the reference's per-link quantities in tdtk_graph_block_doubles layout (api_graph.cpp tdtk_graph_link_blocks)"""
     nl = len(ref_blocks)
     out = np.zeros((nl, {1: 42, 2: 56, 3: 43, 4: 49}[k]))
     for l in range(nl):
