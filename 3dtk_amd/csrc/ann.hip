@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 
+#include "arena.h"
 #include "kernels.h"
 #include "part_scan.h"
 #include "eigen3.h"
@@ -1103,55 +1104,49 @@ static inline uint32_t cdiv(size_t a, size_t b) { return (uint32_t)((a + b - 1) 
     if (_e != hipSuccess) { res.err = _e; return res; }  \
   } while (0)
 
-// (lab library: 256 guard bytes behind every region of the arena, as in build.hip)
-#ifdef TDTK_LAB
-constexpr size_t ANN_GUARD = 256;
-static thread_local std::vector<size_t>* g_ann_guard_sink = nullptr;
-struct AnnGuardList { uint32_t n; uint32_t pad; size_t off[60]; };
-__global__ void __launch_bounds__(64) k_ann_guard_fill(char* arena, AnnGuardList G)
+// the arena of an ANN tree build (lab library: 256 guard bytes behind every region, as in build.hip -- arena.h)
+struct AnnArena {
+  Region<uint32_t> perm, seg_of; Region<double> cx, cy, cz;
+  Region<char> spare0, spare1;                     // 256 bytes each, unused: they keep the offsets of what follows
+  Region<unsigned long long> LR, AB;
+  Region<uint32_t> posL, posR;
+  Region<ASeg> segA, segB, small_cells;
+  Region<AMeasU> meas; Region<ADec> dec;
+  Region<unsigned long long> cnt, cnt_next;        // the cells' counts, those of the next level
+  Region<void> tmp; Region<uint32_t> small;
+  Region<double> bbox_partial, box;
+  Region<AMeasU> meas_next;                        // meas of the next level
+  Region<uint32_t> lvl;                            // cells per level; behind them the levels' "points on a plane" flags
+  Region<char> scan_state;                         // state of the one-launch scans (sort.hip's, k_ann_part_scan's)
+  Region<ASeg> mid_cells;                          // k_ann_mid
+  size_t scan_tmp = 0, total = 0;
+  GuardList guards{};
+};
+static AnnArena carve_ann_arena(size_t M)
 {
-  if (blockIdx.x < G.n) reinterpret_cast<uint32_t*>(arena + G.off[blockIdx.x])[threadIdx.x] = 0x5AC35AC3u ^ blockIdx.x;
-}
-__global__ void __launch_bounds__(64) k_ann_guard_check(const char* arena, AnnGuardList G, uint32_t* bad)
-{
-  if (blockIdx.x < G.n && reinterpret_cast<const uint32_t*>(arena + G.off[blockIdx.x])[threadIdx.x] != (0x5AC35AC3u ^ blockIdx.x))
-    atomicMax(bad, blockIdx.x + 1u);
-}
-#else
-constexpr size_t ANN_GUARD = 0;
-#endif
-static size_t ann_layout(size_t M, size_t* O, size_t* scan_tmp_out)
-{
-  size_t scan_tmp = 0;
+  AnnArena A;
   {
     unsigned long long* z8 = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, scan_tmp, z8, z8, 0ull, M + 1, rocprim::plus<unsigned long long>(), (hipStream_t)0);
+    (void)rocprim::exclusive_scan(nullptr, A.scan_tmp, z8, z8, 0ull, M + 1, rocprim::plus<unsigned long long>(), (hipStream_t)0);
   }
   const size_t n1 = M + 1, nlarge = M / (ANN_SMALL + 1) + 2, nsmall = M / 2 + 2;
-  size_t off = 0;
-  int k = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off; off += (bytes + 255) & ~(size_t)255;
-#ifdef TDTK_LAB
-    if (g_ann_guard_sink) g_ann_guard_sink->push_back(off);
-#endif
-    off += ANN_GUARD;
-    if (O) O[k] = o; k++; return o; };
-  take(4 * n1); take(4 * n1); take(8 * n1); take(8 * n1); take(8 * n1);      // 0 perm 1 segof 2 cx 3 cy 4 cz
-  take(256); take(256); take(8 * n1); take(8 * n1);                          // 5, 6 spare 7 LR 8 AB
-  take(4 * n1); take(4 * n1);                                                // 9 posL 10 posR
-  take(sizeof(ASeg) * nlarge); take(sizeof(ASeg) * nlarge); take(sizeof(ASeg) * nsmall);   // 11 segA 12 segB 13 small cells
-  take(sizeof(AMeasU) * nlarge); take(sizeof(ADec) * nlarge); take(8 * nlarge); take(8 * nlarge);   // 14 meas 15 dec 16 counts 17 counts of the next level
-  take(scan_tmp + 256); take(256);                                           // 18 tmp 19 small
-  take(bbox_temp_bytes() + 256); take(256);                                  // 20 bbox partials 21 box
-  take(sizeof(AMeasU) * nlarge);                                             // 22 meas of the next level
-  take(8 * (ANN_MAX_LEVELS + 2));                                            // 23 cells per level; behind them the levels' "points on a plane" flags
-  take(std::max(scan_pair27_state_bytes(n1), part_state_bytes(n1)));         // 24 state of the one-launch scans (sort.hip's, k_ann_part_scan's)
-  take(sizeof(ASeg) * nlarge);                                               // 25 mid cells (k_ann_mid)
-  if (scan_tmp_out) *scan_tmp_out = scan_tmp;
-  return off;
+  ArenaCarver c;
+  c.take(A.perm, 4 * n1); c.take(A.seg_of, 4 * n1); c.take(A.cx, 8 * n1); c.take(A.cy, 8 * n1); c.take(A.cz, 8 * n1);
+  c.take(A.spare0, 256); c.take(A.spare1, 256); c.take(A.LR, 8 * n1); c.take(A.AB, 8 * n1);
+  c.take(A.posL, 4 * n1); c.take(A.posR, 4 * n1);
+  c.take(A.segA, sizeof(ASeg) * nlarge); c.take(A.segB, sizeof(ASeg) * nlarge); c.take(A.small_cells, sizeof(ASeg) * nsmall);
+  c.take(A.meas, sizeof(AMeasU) * nlarge); c.take(A.dec, sizeof(ADec) * nlarge); c.take(A.cnt, 8 * nlarge); c.take(A.cnt_next, 8 * nlarge);
+  c.take(A.tmp, A.scan_tmp + 256); c.take(A.small, 256);
+  c.take(A.bbox_partial, bbox_temp_bytes() + 256); c.take(A.box, 256);
+  c.take(A.meas_next, sizeof(AMeasU) * nlarge);
+  c.take(A.lvl, 8 * (ANN_MAX_LEVELS + 2));
+  c.take(A.scan_state, std::max(scan_pair27_state_bytes(n1), part_state_bytes(n1)));
+  c.take(A.mid_cells, sizeof(ASeg) * nlarge);
+  A.total = c.off;
+  A.guards = c.guards;
+  return A;
 }
-size_t ann_build_arena_bytes(size_t M) { return ann_layout(M, nullptr, nullptr); }
+size_t ann_build_arena_bytes(size_t M) { return carve_ann_arena(M).total; }
 
 // Builds on `s` inside the caller's scratch.  nodes (M-1 records, may be null for M == 1), pts (M records) and
 // bb (6 doubles) are caller-owned device memory and are final when this returns.
@@ -1161,35 +1156,24 @@ AnnBuildResult ann_build_tree(const double* d_xyz, size_t M_, void* arena_, AnnN
   AnnBuildResult res{};
   const uint32_t M = (uint32_t)M_;
   char* arena = static_cast<char*>(arena_);
-  size_t scan_tmp = 0;
-  size_t O[32];
-  (void)ann_layout(M_, O, &scan_tmp);
-#ifdef TDTK_LAB
-  AnnGuardList guards{};
-  {
-    std::vector<size_t> g;
-    g_ann_guard_sink = &g;
-    (void)ann_layout(M_, nullptr, nullptr);
-    g_ann_guard_sink = nullptr;
-    guards.n = (uint32_t)std::min<size_t>(g.size(), 60);
-    for (uint32_t k = 0; k < guards.n; k++) guards.off[k] = g[k];
-    if (guards.n) hipLaunchKernelGGL(k_ann_guard_fill, dim3(guards.n), dim3(64), 0, s, arena, guards);
-  }
-#endif
+  const AnnArena A = carve_ann_arena(M_);
+  const size_t scan_tmp = A.scan_tmp;
+  arena_guards_arm(arena, A.guards, s);
   const size_t n1 = (size_t)M + 1;
-  uint32_t* perm = (uint32_t*)(arena + O[0]); uint32_t* seg_of = (uint32_t*)(arena + O[1]);
-  double *cx = (double*)(arena + O[2]), *cy = (double*)(arena + O[3]), *cz = (double*)(arena + O[4]);
-  unsigned long long *LR = (unsigned long long*)(arena + O[7]), *AB = (unsigned long long*)(arena + O[8]);
-  uint32_t *posL = (uint32_t*)(arena + O[9]), *posR = (uint32_t*)(arena + O[10]);
-  ASeg *segs = (ASeg*)(arena + O[11]), *next = (ASeg*)(arena + O[12]), *small_list = (ASeg*)(arena + O[13]);
-  AMeasU* meas = (AMeasU*)(arena + O[14]); AMeasU* meas_next = (AMeasU*)(arena + O[22]); ADec* dec = (ADec*)(arena + O[15]);
-  unsigned long long *cnt = (unsigned long long*)(arena + O[16]), *cnt_next = (unsigned long long*)(arena + O[17]);
-  void* tmp = arena + O[18];
-  uint32_t* small = (uint32_t*)(arena + O[19]);
-  double* partial = (double*)(arena + O[20]); double* box = (double*)(arena + O[21]);
+  uint32_t* perm = A.perm.in(arena); uint32_t* seg_of = A.seg_of.in(arena);
+  double *cx = A.cx.in(arena), *cy = A.cy.in(arena), *cz = A.cz.in(arena);
+  unsigned long long *LR = A.LR.in(arena), *AB = A.AB.in(arena);
+  uint32_t *posL = A.posL.in(arena), *posR = A.posR.in(arena);
+  ASeg *segs = A.segA.in(arena), *next = A.segB.in(arena), *small_list = A.small_cells.in(arena);
+  AMeasU* meas = A.meas.in(arena); AMeasU* meas_next = A.meas_next.in(arena); ADec* dec = A.dec.in(arena);
+  unsigned long long *cnt = A.cnt.in(arena), *cnt_next = A.cnt_next.in(arena);
+  void* tmp = A.tmp.in(arena);
+  uint32_t* small = A.small.in(arena);
+  double* partial = A.bbox_partial.in(arena); double* box = A.box.in(arena);
+  char* const scan_state = A.scan_state.in(arena);
 
-  uint32_t* lvl = (uint32_t*)(arena + O[23]);
-  ASeg* mid_list = (ASeg*)(arena + O[25]);
+  uint32_t* lvl = A.lvl.in(arena);
+  ASeg* mid_list = A.mid_cells.in(arena);
   // cells of at most this many points leave the level loop for k_ann_mid (TDTK_ANN_MID=0: the level loop down to 64-point cells,
   // the round-2 form)
   static const uint32_t mid_cap = [] { const char* e = getenv("TDTK_ANN_MID"); return (e && e[0] == '0') ? ANN_SMALL : ANN_MID; }();
@@ -1199,7 +1183,8 @@ AnnBuildResult ann_build_tree(const double* d_xyz, size_t M_, void* arena_, AnnN
   // the partition's scans in one launch each while the positions fit their 27-bit counters (TDTK_OWN_SCAN=0: rocPRIM's two)
   static const bool own_scan_env = [] { const char* e = getenv("TDTK_OWN_SCAN"); return !(e && e[0] == '0'); }();
   const bool own_scan = own_scan_env && n1 < ((size_t)1 << 27);
-  if (own_scan) ACHK(hipMemsetAsync(arena + O[24], 0, std::max(scan_pair27_state_bytes(n1), part_state_bytes(n1)), s));
+  const bool part_env = [] { const char* e = lab_env("TDTK_ANN_PART"); return !(e && e[0] == '0'); }();
+  if (own_scan) ACHK(hipMemsetAsync(scan_state, 0, std::max(scan_pair27_state_bytes(n1), part_state_bytes(n1)), s));
   hipLaunchKernelGGL(k_ann_init, dim3(cdiv(M, 256)), dim3(256), 0, s, d_xyz, M, perm, seg_of, cx, cy, cz, small + 2, mid_cap);
   ACHK(launch_bbox(d_xyz, M, partial, box, s));
   hipLaunchKernelGGL(k_ann_root, dim3(1), dim3(1), 0, s, box, M, segs, small_list, small, bb, meas, cnt, lvl, mid_list, mid_cap);
@@ -1216,22 +1201,25 @@ AnnBuildResult ann_build_tree(const double* d_xyz, size_t M_, void* arena_, AnnN
       hipLaunchKernelGGL(k_ann_measure, dim3(cdiv(M, 256 * MEAS_ITERS)), dim3(256), 0, s, seg_of, M, cx, cy, cz, meas,
                          level ? (const ASeg*)next : (const ASeg*)nullptr, level ? (const ADec*)dec : (const ADec*)nullptr);
       hipLaunchKernelGGL(k_ann_decide, dim3(cdiv(bound, 256)), dim3(256), 0, s, segs, lvl + level, meas, dec);
+      // The level's two passes use the one-launch scans' epochs 2 level + 1 and 2 level + 2, which run to 254.  The second is
+      // even, so both are below 255 or neither is: ONE condition says that this level's scans are the one-launch ones, and
+      // with that, that its "points on a plane" flag may be raised (pass 1) and may gate pass 2 (the gate needs every kernel
+      // of the pass to honour it: with rocPRIM's scan, which does not, the pass runs ungated and no flag is handed out).
+      const bool one_launch = own_scan && 2u * level + 2u < 255u;
+      uint32_t* const flag = one_launch ? eqf + level : nullptr;
       // (the cells' counts: inside the first pass's scan when that is the one-launch one -- k_ann_part_scan<1> --, else a pass of their own)
-      const bool part2_level = [] { const char* e = lab_env("TDTK_ANN_PART"); return !(e && e[0] == '0'); }() && own_scan && 2u * level + 2u < 255u;
+      const bool part2_level = part_env && one_launch;
       if (!part2_level) hipLaunchKernelGGL(k_ann_count, dim3(cdiv(M, 256 * MEAS_ITERS)), dim3(256), 0, s, seg_of, M, dec, cx, cy, cz, cnt);
       // the library's first Hoare pass, then its second one on what lies right of br1
       for (int pass = 1; pass <= 2; pass++) {
-        // (the gate needs every kernel of the pass to honour it: with rocPRIM's scan, which does not, the pass runs ungated)
-        const bool one_launch = own_scan && 2u * level + (uint32_t)pass < 255u;
         if (part2_level) {      // (lab, TDTK_ANN_PART=0: round 3's four launches)
           // a Hoare pass = a scan that writes the index list + the swaps
           const uint32_t ntiles = cdiv(M, PS_TILE), nbw = cdiv(M, 256u * APW_ROWS);
-          uint32_t* counter = reinterpret_cast<uint32_t*>(arena + O[24]);
-          unsigned long long* status = reinterpret_cast<unsigned long long*>(arena + O[24] + 64);
-          uint32_t* const flag = eqf + level;
+          uint32_t* counter = reinterpret_cast<uint32_t*>(scan_state);
+          unsigned long long* status = reinterpret_cast<unsigned long long*>(scan_state + 64);
           if (pass == 1) {
             hipLaunchKernelGGL(k_ann_part_scan<1>, dim3(ntiles), dim3(PS_THREADS), 0, s, seg_of, segs, dec, cnt, cx, cy, cz, M, posL, status, counter,
-                               2u * level + 1u, ntiles, small + 2, (2u * level + 2u < 255u) ? flag : (uint32_t*)nullptr);
+                               2u * level + 1u, ntiles, small + 2, flag);
             hipLaunchKernelGGL(k_ann_part_swap<1>, dim3(nbw), dim3(256), 0, s, posL, seg_of, segs, cnt, M, perm, cx, cy, cz, (const uint32_t*)nullptr);
           } else {
             hipLaunchKernelGGL(k_ann_part_scan<2>, dim3(ntiles), dim3(PS_THREADS), 0, s, seg_of, segs, dec, cnt, cx, cy, cz, M, posL, status, counter,
@@ -1240,15 +1228,13 @@ AnnBuildResult ann_build_tree(const double* d_xyz, size_t M_, void* arena_, AnnN
           }
           continue;
         }
-        uint32_t* const flag = one_launch ? eqf + level : nullptr;
         const uint32_t* const gate = (pass == 2) ? flag : nullptr;
         if (pass == 1)
-          hipLaunchKernelGGL(k_ann_misplaced<1>, dim3(cdiv(n1, 256)), dim3(256), 0, s, seg_of, segs, dec, cnt, cx, cy, cz, M, LR,
-                             (own_scan && 2u * level + 2u < 255u) ? eqf + level : (uint32_t*)nullptr);
+          hipLaunchKernelGGL(k_ann_misplaced<1>, dim3(cdiv(n1, 256)), dim3(256), 0, s, seg_of, segs, dec, cnt, cx, cy, cz, M, LR, flag);
         else
           hipLaunchKernelGGL(k_ann_misplaced<2>, dim3(cdiv(n1, 256)), dim3(256), 0, s, seg_of, segs, dec, cnt, cx, cy, cz, M, LR, flag);
         if (one_launch) {
-          ACHK(launch_scan_pair27(LR, AB, n1, arena + O[24], 2u * level + (uint32_t)pass, small + 2, s, gate));
+          ACHK(launch_scan_pair27(LR, AB, n1, scan_state, 2u * level + (uint32_t)pass, small + 2, s, gate));
         } else {
           size_t st = scan_tmp;
           ACHK(rocprim::exclusive_scan(tmp, st, LR, AB, 0ull, n1, rocprim::plus<unsigned long long>(), s));
@@ -1294,21 +1280,11 @@ AnnBuildResult ann_build_tree(const double* d_xyz, size_t M_, void* arena_, AnnN
   ACHK(hipStreamSynchronize(s));
   ACHK(hipGetLastError());
   if (h_small[2]) { res.err = hipErrorInvalidValue; res.degenerate = true; return res; }
-#ifdef TDTK_LAB
-  if (guards.n) {
-    uint32_t* bad = small + 40;      // (a word of `small` nothing else uses)
-    uint32_t h_bad = 0;
-    (void)hipMemsetAsync(bad, 0, 4, s);
-    hipLaunchKernelGGL(k_ann_guard_check, dim3(guards.n), dim3(64), 0, s, arena, guards, bad);
-    (void)hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s);
-    (void)hipStreamSynchronize(s);
-    if (h_bad) {
-      fprintf(stderr, "ANN tree build: arena guard %u of %u overwritten (M = %u)\n", h_bad - 1u, guards.n, M);
-      res.err = hipErrorAssert;
-      return res;
-    }
+  if (const uint32_t h_bad = arena_guards_check(arena, A.guards, small + 40, s)) {      // (lab; a word of `small` nothing else uses)
+    fprintf(stderr, "ANN tree build: arena guard %u of %u overwritten (M = %u)\n", h_bad - 1u, A.guards.n, M);
+    res.err = hipErrorAssert;
+    return res;
   }
-#endif
   res.root_ref = h_small[0];
   res.max_depth = h_small[1];
   res.levels = level;

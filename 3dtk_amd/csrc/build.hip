@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 
+#include "arena.h"
 #include "kernels.h"
 #include "part_scan.h"
 
@@ -388,20 +389,18 @@ __global__ void __launch_bounds__(256) k_measure_node(const BSeg* __restrict__ s
 // replace -- 4.2 ns per point of the longest node: 160 us for 39K points -- so the threshold grows with the cloud
 // (M / 200: never more than the eight top levels, which are the speculated ones), and the node threshold with it.
 #define BIG_LEVEL_MAX 49152u
-static uint32_t build_big_level_min(size_t M)
+// (small_rule, grow: the plan's switches TDTK_BUILD_BIGMIN / TDTK_BUILD_BIGGROW -- make_build_plan)
+static uint32_t build_big_level_min(size_t M, bool small_rule, bool grow)
 {
-  const bool grow_env = [] { const char* e = lab_env("TDTK_BUILD_BIGGROW"); return !(e && e[0] == '0'); }();
-  static const bool small_env = [] { const char* e = lab_env("TDTK_BUILD_BIGMIN"); return !(e && e[0] == '0'); }();
-  if (small_env && M <= (size_t)BIG_MIN_SMALL * 16u) return BIG_MIN_SMALL / 2u;
-  if (!grow_env) return BIG_MIN / 2u;
+  if (small_rule && M <= (size_t)BIG_MIN_SMALL * 16u) return BIG_MIN_SMALL / 2u;
+  if (!grow) return BIG_MIN / 2u;
   const size_t t = M / 200u;
   return (uint32_t)(t < BIG_MIN / 2u ? BIG_MIN / 2u : (t > BIG_LEVEL_MAX ? BIG_LEVEL_MAX : t));
 }
-static uint32_t build_big_min(size_t M)
+static uint32_t build_big_min(size_t M, bool small_rule, uint32_t big_level_min)
 {
-  static const bool small_env = [] { const char* e = lab_env("TDTK_BUILD_BIGMIN"); return !(e && e[0] == '0'); }();
-  if (small_env && M <= (size_t)BIG_MIN_SMALL * 16u) return BIG_MIN_SMALL;   // (15K points 572 -> 545 us; 40K equal; 81K 710 -> 772: the side streams' chains then outlast the levels)
-  const uint32_t t = build_big_level_min(M) / 3u * 2u;
+  if (small_rule && M <= (size_t)BIG_MIN_SMALL * 16u) return BIG_MIN_SMALL;   // (15K points 572 -> 545 us; 40K equal; 81K 710 -> 772: the side streams' chains then outlast the levels)
+  const uint32_t t = big_level_min / 3u * 2u;
   return t > BIG_MIN ? t : BIG_MIN;
 }
 #define BIG_ANY 0xFFFFu        // BSum.eb of the neutral element
@@ -873,7 +872,6 @@ struct BSpecLevel {
 struct BPart { double lo[3], hi[3], sum[3]; };
 #define BIG_PB 512u
 #define BIG_SPEC_MAX 24
-#define SPEC_SLOTS 14          // buffers per speculated level (spec_layout)
 struct BSpecAll { BSpecLevel L[BIG_SPEC_MAX]; int n; };
 
 // (a kernel's by-value argument block read through the kernarg segment pointer: see kernarg_block in kernels.hip)
@@ -1695,23 +1693,14 @@ static inline int bits_for(uint64_t v)
   return b;
 }
 
-#define BCHK(expr)                                 \
-  do {                                             \
-    hipError_t _e = (expr);                        \
-    if (_e != hipSuccess) { res.err = _e; goto fail; } \
+#define BCHK(expr)                       \
+  do {                                   \
+    hipError_t _e = (expr);              \
+    if (_e != hipSuccess) return _e;     \
   } while (0)
 
-// bytes of scratch a build over M points needs (every temporary, and the node / bucket records while their
-// number is still unknown)
-static size_t build_layout(size_t M, size_t* offs, size_t* scan_tmp_out);
-static size_t spec_layout(size_t M, size_t base, size_t* SO, int* nlev_out);
-// Lab library: every region of the arena is followed by 256 guard bytes, filled with a pattern before a build and looked
-// at behind it -- a region written past its end (the hand-over bug of round 4: a million root records into a table of
-// 8192) fails the build it happens in, whatever it would have hit.  The product's layout has no guards.
+// ---- the arena guards of the lab library (arena.h): one pattern, one kernel pair, both tree builders ----------------
 #ifdef TDTK_LAB
-constexpr size_t ARENA_GUARD = 256;
-static thread_local std::vector<size_t>* g_guard_sink = nullptr;      // the layout functions push the offset of every guard
-struct GuardList { uint32_t n; uint32_t pad; size_t off[250]; };
 __global__ void __launch_bounds__(64) k_guard_fill(char* arena, GuardList G)
 {
   if (blockIdx.x < G.n) reinterpret_cast<uint32_t*>(arena + G.off[blockIdx.x])[threadIdx.x] = 0xA5C3A5C3u ^ blockIdx.x;
@@ -1721,640 +1710,88 @@ __global__ void __launch_bounds__(64) k_guard_check(const char* arena, GuardList
   if (blockIdx.x < G.n && reinterpret_cast<const uint32_t*>(arena + G.off[blockIdx.x])[threadIdx.x] != (0xA5C3A5C3u ^ blockIdx.x))
     atomicMax(bad, blockIdx.x + 1u);
 }
-#else
-constexpr size_t ARENA_GUARD = 0;
 #endif
-static inline void arena_guard(size_t& off)
+void arena_guards_arm(char* arena, const GuardList& G, hipStream_t s)
 {
 #ifdef TDTK_LAB
-  if (g_guard_sink) g_guard_sink->push_back(off);
+  if (G.n) hipLaunchKernelGGL(k_guard_fill, dim3(G.n), dim3(64), 0, s, arena, G);
 #endif
-  off += ARENA_GUARD;
 }
-size_t device_build_arena_bytes(size_t M, bool with_background_chain)
+uint32_t arena_guards_check(char* arena, const GuardList& G, uint32_t* d_bad, hipStream_t s)
 {
-  const size_t base = build_layout(M, nullptr, nullptr);
-  return with_background_chain ? spec_layout(M, base, nullptr, nullptr) : base;
+  uint32_t h_bad = 0;
+#ifdef TDTK_LAB
+  if (!G.n) return 0;
+  (void)hipMemsetAsync(d_bad, 0, 4, s);
+  hipLaunchKernelGGL(k_guard_check, dim3(G.n), dim3(64), 0, s, arena, G, d_bad);
+  (void)hipMemcpyAsync(&h_bad, d_bad, 4, hipMemcpyDeviceToHost, s);
+  (void)hipStreamSynchronize(s);
+#endif
+  return h_bad;
 }
 
-// Builds on `s` inside the caller's scratch `arena_` (>= device_build_arena_bytes(M), reused from build to build:
-// no hipMalloc / hipFree of hundreds of MB per tree, and no device-wide sync from hipFree while another thread's
-// kernels run).  On success the caller owns res.{nodes,node_r,pts,leaf_tab}, from the handle pool (pool.cpp) at their sizes.
-DevBuildResult device_build_tree(const double* d_xyz, size_t M_, int bucket, void* arena_, hipStream_t s, const BuildSide* side,
-                                 int no_finish)
-{
-  DevBuildResult res{};
-  const uint32_t M = (uint32_t)M_;
-  char* arena = static_cast<char*>(arena_);
-  KdNode* nodes = nullptr; double* node_r = nullptr; LeafEntry* leaf_tab = nullptr; KdPoint* pts = nullptr;
-  KdNode* f_nodes = nullptr; double* f_r = nullptr; LeafEntry* f_leaf = nullptr;
-  uint32_t node_count = 0, leaf_count = 0, depth = 0;
-  uint32_t h_spec_err = 0;
-  bool tail_enqueued = false;
-  bool spec_on = false;
-  bool spec_suspect = false;   // the failure may be the speculation's doing (see `fail`)
-  size_t scan_tmp = 0;
-  size_t O[48];
-  (void)build_layout(M_, O, &scan_tmp);
-#ifdef TDTK_LAB
-  GuardList guards{};
-  {
-    std::vector<size_t> g;
-    g_guard_sink = &g;
-    // (the speculative levels' regions only when the caller has them: without background streams the arena ends at the base
-    // layout -- device_build_arena_bytes(M, false))
-    const size_t base = build_layout(M_, nullptr, nullptr);
-    if (side && side->s2) (void)spec_layout(M_, base, nullptr, nullptr);
-    g_guard_sink = nullptr;
-    guards.n = (uint32_t)std::min<size_t>(g.size(), 250);
-    for (uint32_t k = 0; k < guards.n; k++) guards.off[k] = g[k];
-    if (guards.n) hipLaunchKernelGGL(k_guard_fill, dim3(guards.n), dim3(64), 0, s, arena, guards);
-    // (TDTK_GUARD_SELFTEST=1: one word behind the sixth region is overwritten on purpose -- the build must fail)
-    if (guards.n > 5 && lab_env("TDTK_GUARD_SELFTEST")) (void)hipMemsetAsync(arena + guards.off[5] + 8, 0, 4, s);
-  }
-#endif
-  const size_t n1 = (size_t)M + 1;
-  const size_t o_perm = O[0], o_segof = O[1], o_cx = O[2], o_cy = O[3], o_cz = O[4], o_f = O[5], o_F = O[6], o_isL = O[7],
-               o_A = O[8], o_posL = O[9], o_posR = O[10], o_segA = O[11], o_segB = O[12], o_meas = O[13], o_kind = O[14],
-               o_axis = O[15], o_split = O[16], o_irank = O[17], o_tmp = O[18], o_small = O[19], o_nodes = O[20],
-               o_r = O[21], o_leaf = O[22], o_lvl = O[23];
-  (void)o_f; (void)o_F;
-  nodes = (KdNode*)(arena + o_nodes); node_r = (double*)(arena + o_r); leaf_tab = (LeafEntry*)(arena + o_leaf);
-  BCHK((hipError_t)pool_malloc_raw((void**)&pts, sizeof(KdPoint) * (size_t)M));
-  {
-    uint32_t* perm = (uint32_t*)(arena + o_perm); uint32_t* seg_of = (uint32_t*)(arena + o_segof);
-    double *cx = (double*)(arena + o_cx), *cy = (double*)(arena + o_cy), *cz = (double*)(arena + o_cz);
-    uint32_t *nleft = (uint32_t*)(arena + o_F), *posL = (uint32_t*)(arena + o_posL), *posR = (uint32_t*)(arena + o_posR);
-    BLevel* lvl = (BLevel*)(arena + o_lvl);
-    unsigned long long *LR = (unsigned long long*)(arena + o_isL), *AB = (unsigned long long*)(arena + o_A);
-    BSeg* segs = (BSeg*)(arena + o_segA); BSeg* next = (BSeg*)(arena + o_segB);
-    BMeas* meas = (BMeas*)(arena + o_meas);
-    uint32_t *kind = (uint32_t*)(arena + o_kind), *axis = (uint32_t*)(arena + o_axis), *irank = (uint32_t*)(arena + o_irank);
-    double* splitval = (double*)(arena + o_split);
-    void* tmp = arena + o_tmp;
-    BPiece* pieces = (BPiece*)(arena + O[24]);
-    BPre *prein = (BPre*)(arena + O[25]), *preout = (BPre*)(arena + O[26]);
-    BSum *own = (BSum*)(arena + O[27]), *comp = (BSum*)(arena + O[28]);
-    uint32_t* wlist = (uint32_t*)(arena + O[29]);
-    const uint32_t nblocks = cdiv(M, BIG_CH);
-    static const bool chain_only = [] { const char* e = lab_env("TDTK_BUILD_CHAIN"); return e && e[0] == '1'; }();
-    const uint32_t big_min = build_big_min(M_);
-    const bool use_big = !chain_only && M >= big_min;
-    const uint32_t big_level_min = build_big_level_min(M_);
-    // TDTK_MEASURE=axis: round 2's wave per (node, axis) for the nodes below the piecewise path (k_measure); default: a wave
-    // per node (k_measure_node).  With TDTK_BUILD_CHAIN=1 (no piecewise path: chains of any length) the long-chain kernel.
-    static const bool measure_axis_env = [] { const char* e = lab_env("TDTK_MEASURE"); return e && e[0] == 'a'; }();
-    const bool measure_per_axis_always = measure_axis_env || chain_only;
-    const int big_dbg_all = lab_env("TDTK_BIG_DEBUG") ? atoi(lab_env("TDTK_BIG_DEBUG")) : 0;
-    // speculative splits: TDTK_BUILD_SPEC=0 builds in order; TDTK_BUILD_SPEC_FAULT=1 (tests) cuts every big node elsewhere than
-    // the exact sum would, so that the final check fails and the in-order path takes over
-    static const bool spec_env = [] { const char* e = getenv("TDTK_BUILD_SPEC"); return !(e && e[0] == '0'); }();
-    static const int spec_fault = [] { const char* e = lab_env("TDTK_BUILD_SPEC_FAULT"); return (e && e[0] == '1') ? 1 : 0; }();
-    const bool spec = spec_env && side && side->s2 && use_big && !big_dbg_all;
-    spec_on = spec;
-    BSpecAll SP;
-    SP.n = 0;
-    size_t SO[BIG_SPEC_MAX * SPEC_SLOTS + 5];
-    int spec_levels = 0;
-    void *tmp2 = nullptr, *tmp3 = nullptr, *tmp4 = nullptr;
-    if (spec) {
-      (void)spec_layout(M_, build_layout(M_, nullptr, nullptr), SO, &spec_levels);
-      tmp2 = arena + SO[(size_t)BIG_SPEC_MAX * SPEC_SLOTS];
-      tmp3 = arena + SO[(size_t)BIG_SPEC_MAX * SPEC_SLOTS + 2];
-      tmp4 = arena + SO[(size_t)BIG_SPEC_MAX * SPEC_SLOTS + 3];
-    }
-    const int big_dbg = big_dbg_all & (3 | 16);   // 1: never trust a folded run, 2: walk every piece, 4: garbage in the arena, 8: compare with the chain
-    if (big_dbg_all & 4) BCHK(hipMemsetAsync(arena, 0xFF, build_layout(M_, nullptr, nullptr), s));
-    uint32_t* small = (uint32_t*)(arena + o_small);  // [0] root_ref [1] max_leaf [2] err
-    // the partition's scan in one launch while the positions fit its 27-bit counters (TDTK_OWN_SCAN=0: rocPRIM's two)
-    static const bool own_scan_env = [] { const char* e = lab_env("TDTK_OWN_SCAN"); return !(e && e[0] == '0'); }();
-    const bool own_scan = own_scan_env && n1 < ((size_t)1 << 27);
-    const size_t o_scanstate = O[31];
-    if (own_scan) BCHK(hipMemsetAsync(arena + o_scanstate, 0, std::max(scan_pair27_state_bytes(n1), part_state_bytes(n1)), s));
-    hipLaunchKernelGGL(k_init, dim3(cdiv(M, 256)), dim3(256), 0, s, d_xyz, M, perm, seg_of, cx, cy, cz, small, lvl, segs);
+// ---- the words of `small` (256 bytes of the arena that the kernels and the host talk through) -----------------------
+enum SmallWord : uint32_t {
+  SM_ROOT_REF = 0,     // the root's reference
+  SM_MAX_LEAF = 1,     // the largest bucket
+  SM_ERR = 2,          // the error word: an empty child / non-finite coordinates, and the two bits below
+  SM_SPEC_ERR = 3,     // speculated cuts the exact sums would have made elsewhere (k_spec_patch)
+  SM_FIN_MAXN = 4,     // k_fin_maxn: the largest node of the level about to be handed over ...
+  SM_FIN_NODES = 5,    // ... and its number of nodes
+  SM_LOOK_WORDS = 8,   // what one look of the host copies: words 0 .. 7
+  SM_FIN_TRACE = 15,   // FIN_TRACE: the magic word that makes subtree 0 time its phases ...
+  SM_FIN_PHASES = 16,  // ... and the ten words it leaves them in
+  SM_GUARD_BAD = 40,   // lab: the guard check's answer (a word nothing else uses)
+};
+enum : uint32_t {
+  ERR_SCAN_TIMEOUT = 0x10000u,   // the one-launch scan gave up waiting (sort.hip, k_part_scan): not an input problem
+  ERR_DEEP_SUBTREE = 0x20000u,   // a subtree deeper than the finishers' tables: the build is redone level by level
+};
 
-    // Levels are enqueued in batches; how many nodes a level has, and where its node / bucket records start, is
-    // known on the device only (lvl[]).  The host looks once after a first batch as deep as a balanced tree gets
-    // down to bucket-sized nodes, then every two levels; per-node kernels are launched over an upper bound of the
-    // level's node count (what the last look saw, doubled per level since) and return past the real count.
-    // diagnostics (TDTK_BUILD_TRACE=1): an event at the start of every level on the build's stream; the elapsed times are
-    // printed when the build is done -- what a level costs when no profiler is serialising the launches
-    static const bool lvl_trace = [] { const char* e = lab_env("TDTK_BUILD_TRACE"); return e && (e[0] == '1' || e[0] == '2'); }();
-    static const bool fin_trace = [] { const char* e = lab_env("TDTK_BUILD_TRACE"); return e && e[0] == '2'; }();
-    std::vector<hipEvent_t> lvl_ev;
-    uint32_t level = 0, known = 1, known_at = 0;
-    uint32_t batch = 1;
-    for (size_t c = (size_t)(bucket > 0 ? bucket : 1); c < M_; c <<= 1) batch++;
-    batch += 2;   // mean splits do not halve: a 1M-point cloud is 18-19 levels deep, not 17, and a level past the end of the
-                  // tree costs less than the host's look (it moves nothing)
-    // The level from which every node is finished by one workgroup (k_fin_subtrees): the first at which a balanced node
-    // holds at most FIN_HANDOFF points.  TDTK_BUILD_FINISH=0 (lab): level by level to the end.
-    uint32_t fin_level = 0xFFFFFFFFu;
-    const uint32_t fin_cap = fin_max_subtrees(M_);
-    {
-      static const bool fin_env = [] { const char* e = lab_env("TDTK_BUILD_FINISH"); return !(e && e[0] == '0'); }();
-      uint32_t L = 0;
-      // (round 6: a cloud of two million points and more goes on by levels until a balanced node fits a wave's finisher --
-      //  two or three more levels of launches against most of the workgroup finisher's time; TDTK_BUILD_HANDOFF, lab)
-      const uint32_t handoff_env = [] { const char* e = lab_env("TDTK_BUILD_HANDOFF"); return e ? (uint32_t)atoi(e) : 0u; }();
-      const uint32_t handoff = handoff_env ? handoff_env : (M_ >= FIN_HANDOFF_WAVE_FROM ? FIN_HANDOFF_WAVE : FIN_HANDOFF);
-      while ((M_ >> L) > handoff) L++;
-      if (fin_env && no_finish == 0 && bucket >= 6 && L < 31 && (1u << L) <= fin_cap && !big_dbg_all) fin_level = L;
-    }
-    if (fin_level != 0xFFFFFFFFu) batch = fin_level;
-    // From chain_from on the exact sums of a speculated level are plain chains in the background (k_chain_exact) -- 4.2 ns
-    // per point of the level's largest node, which must end before the build does.  A balanced cloud's do; a cloud with a
-    // third of its points in one tight cluster has a 1.3M-point node on levels 5 .. 10 of 4M points, and its chains (5.6 ms)
-    // were what the build waited for.  So a build of two million points and more -- where a look costs a few per cent of a
-    // level -- looks at the largest node before the first such level (and before every further one while it is too large):
-    // beyond M / 17 points the level takes the piecewise path.
-    // chain_from: the first level whose balanced node's chain (4.2 ns a point) is a small share of what a build of this
-    // size takes -- 20 000 + M / 50 points, the sixth level at the latest: level 0 for a 15K-point scan, 1 at 40K, 2 at 81K,
-    // 4 at 300K, 5 from 1M on (measured: 4 at 1M is 8 % slower, 3 at 300K 4 %).  On small clouds this is not about bandwidth
-    // but about the HOST: a level's piecewise path is nine launches on the side streams, and enqueuing them (3-4 us
-    // apiece) was what a level of a 15K .. 40K-point build took (15K: 0.50 -> 0.41 ms, lab library).
-    const uint32_t chain_from = [&] {
-      const char* e = lab_env("TDTK_BUILD_CHAINFROM");
-      if (e) return (uint32_t)atoi(e);
-      const size_t thresh = 20000u + M_ / 50u;
-      uint32_t L = 0;
-      while (L < 5u && (M_ >> L) > thresh) L++;
-      return L;
-    }();
-    bool chain_ok = true;
-    bool chain_look = spec && M_ >= 2000000u && fin_level != 0xFFFFFFFFu && chain_from < fin_level && chain_from < (uint32_t)spec_levels;
-    if (chain_look) batch = chain_from;
-    // The host's looks at the device land in pinned memory when the caller has some (a copy into pageable memory is a
-    // synchronisation of its own): h_small = small[0 .. 7] (root reference, largest bucket, error word, check word, the
-    // hand-over level's largest node and node count), hl = the level counters.
-    std::vector<unsigned char> h_pageable;
-    unsigned char* const hst = (side && side->h_pin) ? static_cast<unsigned char*>(side->h_pin) : (h_pageable.resize(65536), h_pageable.data());
-    uint32_t* const h_small = reinterpret_cast<uint32_t*>(hst);
-    BLevel* const hl = reinterpret_cast<BLevel*>(hst + 64);
-    static_assert(64 + sizeof(BLevel) * (BUILD_MAX_LEVELS + 2) <= 65536, "the staging block holds every level's counters");
-    std::memset(hst, 0, 64);
-    bool have_max = false, fin_retry = false;
-    uint32_t fin_nodes = 0, fin_maxn = 0;     // nodes of the level about to be handed over, the largest of them (k_fin_maxn)
-    for (;;) {
-      if (level == fin_level) {
-        // does the level's largest node fit a workgroup's LDS?  (An unbalanced cloud -- a real scan -- takes a level or two more.)
-        if (!have_max) {
-          hipLaunchKernelGGL(k_fin_maxn, dim3(1), dim3(256), 0, s, segs, lvl + level, small + 4);
-          BCHK(hipMemcpyAsync(h_small, small, 32, hipMemcpyDeviceToHost, s));
-          BCHK(hipStreamSynchronize(s));
-        }
-        have_max = false;
-        const uint32_t h_max[2] = {h_small[4], h_small[5]};
-        fin_nodes = h_max[1]; fin_maxn = h_max[0];
-        if (h_max[0] > FIN_LDS && h_max[1] * 2u <= fin_cap && fin_level + 1u < 31u) {
-          fin_level++;              // one more level by its own launches (below), then look again
-          known = h_max[1]; known_at = level;
-          batch = 1;
-        } else if (h_max[0] > FIN_LDS || h_max[1] > fin_cap) {
-          // too many nodes for the tables, or a node too large with no room for a wider level: on by levels -- and a look at
-          // every batch's end whether the level has thinned out (round 6: a cloud with a third of its points in one tight
-          // cluster is in that state for nine levels, until the sparse rest has ended in buckets; it used to stay by levels
-          // to the last bucket, eight levels more)
-          fin_level = 0xFFFFFFFFu;
-          fin_retry = no_finish == 0;
-          known = h_max[1]; known_at = level;
-          batch = 2;
-        }
-      }
-      if (level == fin_level) {
-        // hand the level over: its nodes become the roots of subtrees.  As many workgroups as the level HAS nodes (counted
-        // just above; the tables hold FIN_MAX_SUBTREES): 2^level of them -- right for a balanced tree -- is a million by the
-        // time a lopsided cloud (one dense cluster that stays above FIN_LDS for sixteen levels) is handed over, and the
-        // copy of that many root records ran over the arena (found by tools/fuzz_parity.py --seed 4401, round 4).
-        const uint32_t tmax = fin_nodes ? fin_nodes : 1u;
-        BSeg* roots = (BSeg*)(arena + O[37]);
-        FinTab* ftab = (FinTab*)(arena + O[38]);
-        FinOff* foff = (FinOff*)(arena + O[39]);
-        BCHK(hipMemcpyAsync(roots, segs, sizeof(BSeg) * tmax, hipMemcpyDeviceToDevice, s));
-        if (fin_trace) { const uint32_t magic = 0x7157u; BCHK(hipMemcpyAsync(small + 15, &magic, 4, hipMemcpyHostToDevice, s)); }
-        if (lvl_trace) { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); lvl_ev.push_back(e); } }
-        {
-          FinArgs fa;
-          fa.roots = roots; fa.lvH = lvl + fin_level; fa.cx = cx; fa.cy = cy; fa.cz = cz; fa.perm = perm;
-          fa.segA = (BSeg*)(arena + o_segA); fa.segB = (BSeg*)(arena + o_segB); fa.meas = meas;
-          fa.kind = (uint32_t*)(arena + O[35]); fa.axis = axis; fa.splitval = splitval; fa.irank = (uint32_t*)(arena + O[36]); fa.nleft = nleft;
-          fa.nodes_st = (KdNode*)(arena + O[32]); fa.r_st = (double*)(arena + O[33]); fa.leaf_st = (LeafEntry*)(arena + O[34]);
-          fa.tab = ftab; fa.bucket = (uint32_t)bucket; fa.small = small;
-          fa.sub_nlev = (uint32_t*)(arena + O[41]); fa.sub_maxleaf = (uint32_t*)(arena + O[42]);
-          const bool half_env = [] { const char* e = lab_env("TDTK_BUILD_FINHALF"); return !(e && e[0] == '0'); }();
-          // subtrees of at most FIN_LDS_HALF points two workgroups to a compute unit, then (if the level has any) the larger ones
-          // ... and in front of both, the subtrees of at most FW_CAP points, a wave each
-          const bool wave_env = [] { const char* e = lab_env("TDTK_BUILD_FINWAVE"); return !(e && e[0] == '0'); }();
-          fa.n_lo = 0u; fa.skip_big = 1u;
-          fa.dbg_levels = lab_env("TDTK_FW_DEBUG") ? (uint32_t)atoi(lab_env("TDTK_FW_DEBUG")) : 0u;
-          // (by size only when the level has more subtrees than the chip has room for at once: below that the launches would
-          //  run one after the other where one launch runs them side by side -- the dat/ scan 0.97 -> 1.13 ms)
-          const bool staged = tmax > 1024u;
-          if (wave_env && staged) { hipLaunchKernelGGL(k_fin_wave, dim3(cdiv(tmax, FW_WAVES)), dim3(WAVE * FW_WAVES), 0, s, fa); fa.n_lo = FW_CAP; }
-          if (half_env && staged && fin_maxn > fa.n_lo) { hipLaunchKernelGGL(k_fin_subtrees_half, dim3(tmax), dim3(FIN_T), 0, s, fa); fa.n_lo = FIN_LDS_HALF; }
-          fa.skip_big = 0u;
-          if (fin_maxn > fa.n_lo) hipLaunchKernelGGL(k_fin_subtrees, dim3(tmax), dim3(FIN_T), 0, s, fa);
-        }
-        uint32_t* ftot = (uint32_t*)(arena + O[40]);
-        hipLaunchKernelGGL(k_fin_offsets, dim3(FIN_LV + 1u), dim3(FO_T), 0, s, ftab, foff, lvl + fin_level, ftot, (const uint32_t*)(arena + O[41]),
-                           (const uint32_t*)(arena + O[42]), small + 1);
-        hipLaunchKernelGGL(k_fin_place, dim3(tmax), dim3(256), 0, s, ftab, foff, ftot, roots, lvl + fin_level, (const KdNode*)(arena + O[32]),
-                           (const double*)(arena + O[33]), (const LeafEntry*)(arena + O[34]), nodes, node_r, leaf_tab, small + 0);
-        level = fin_level + FIN_LV + 2u;
-        // what follows the levels does not wait for the host's look: the check of the speculated cuts and the point array
-        // are enqueued now, their results come back with the level counters
-        // (the point array first: it does not need the exact sums, and at a million points the build is waiting for the root's)
-        hipLaunchKernelGGL(k_points, dim3(cdiv(M, 256)), dim3(256), 0, s, perm, cx, cy, cz, M, pts);
-        if (spec && SP.n) {
-          BCHK(hipEventRecord(side->e2, side->s2));
-          BCHK(hipStreamWaitEvent(s, side->e2, 0));
-          if (side->s3) { BCHK(hipEventRecord(side->e3, side->s3)); BCHK(hipStreamWaitEvent(s, side->e3, 0)); }
-          if (side->s4) { BCHK(hipEventRecord(side->e4, side->s4)); BCHK(hipStreamWaitEvent(s, side->e4, 0)); }
-          hipLaunchKernelGGL(k_spec_count, dim3(cdiv(M, 1024)), dim3(256), 0, s, SP, lvl, cx, cy, cz, M);
-          hipLaunchKernelGGL(k_spec_patch, dim3(4), dim3(256), 0, s, SP, lvl, nodes, small + 3);
-        }
-        tail_enqueued = true;
-        BCHK(hipMemcpyAsync(hl, lvl, sizeof(BLevel) * (level + 1), hipMemcpyDeviceToHost, s));
-        BCHK(hipMemcpyAsync(h_small, small, 32, hipMemcpyDeviceToHost, s));
-        BCHK(hipStreamSynchronize(s));
-        if (spec && SP.n) h_spec_err = h_small[3];
-        if (fin_trace) {
-          uint32_t ph[10];
-          if (hipMemcpy(ph, small + 16, sizeof ph, hipMemcpyDeviceToHost) == hipSuccess) {
-            fprintf(stderr, "FIN_TRACE subtree 0 (100 MHz ticks -> us):");
-            const char* nm[10] = {"", "measure (wave: measure+emit)", "decide (wave: scan)", "rank (wave: children+swap)", "emit+count (wave: write-back)", "mark+children", "scan", "swaplist", "swap+relabel", ""};
-            for (int k = 1; k < 9; k++) fprintf(stderr, " %s %.1f", nm[k], ph[k] / 100.0);
-            fprintf(stderr, "\n");
-          }
-        }
-        if (h_small[2] & 0x20000u) {       // a subtree deeper than the tables: level by level, then
-          if (spec_on) { (void)hipStreamSynchronize(side->s2); if (side->s3) (void)hipStreamSynchronize(side->s3); if (side->s4) (void)hipStreamSynchronize(side->s4); }
-          if (pts) pool_free(pts);
-          for (hipEvent_t x : lvl_ev) (void)hipEventDestroy(x);
-          return device_build_tree(d_xyz, M_, bucket, arena_, s, side, 1);
-        }
-        if (h_small[2]) {
-          res.err = hipErrorInvalidValue; res.degenerate = true;
-          spec_suspect = true;
-          goto fail;
-        }
-        break;
-      }
-      for (uint32_t b = 0; b < batch && level < BUILD_MAX_LEVELS; b++, level++) {
-        size_t bound = (size_t)known << ((level - known_at) < 31 ? (level - known_at) : 31);
-        if (bound > M) bound = M;
-        // the nodes of a level are the children of the level above's internal nodes: disjoint runs of more than
-        // `bucket` points each, two children per run (at 1M points and buckets of 20 the doubling bound reaches the
-        // point count at level 16, sixty times the nodes there are)
-        const size_t cap = 2 * (M_ / ((size_t)(bucket > 0 ? bucket : 0) + 1));
-        if (level > 0 && bound > cap) bound = cap;
-        if (bound < 1) bound = 1;
-        const BLevel* lv = lvl + level;
-        if (lvl_trace) { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); lvl_ev.push_back(e); } }
-        // the piecewise path runs while a balanced node is at least half its threshold (below that level the chain in
-        // k_measure takes every node, whatever its size: an empty pass of the piecewise kernels costs 75 us)
-        const bool big_level = use_big && ((M_ >> level) >= big_level_min);
-        // a wave per node while the nodes of a balanced tree hold at most 128 points (three chains in one wave issue 24
-        // cycles per point where three waves need 10: level 7 of a 1M-point tree 253 us against 46, level 12 equal,
-        // level 16 74 against 139)
-        const bool measure_per_axis = measure_per_axis_always || (M_ >> level) > 128;
-        bool spec_this = big_level && spec && SP.n < spec_levels && SP.n < BIG_SPEC_MAX;
-        // a speculated level's chains of small nodes ride in the launch of its partial sums (k_level_front, below)
-        static const bool merge_env = [] { const char* e = lab_env("TDTK_BUILD_MERGE"); return !(e && e[0] == '0'); }();
-        const bool front_merged = spec_this && measure_per_axis && merge_env;
-        bool nodes_done = false;
-        if (front_merged) {}
-        else if (measure_per_axis)
-          hipLaunchKernelGGL(k_measure, dim3(cdiv(bound * 3 * WAVE, 256)), dim3(256), 0, s, segs, lv, cx, cy, cz, meas,
-                             big_level ? big_min : 0xFFFFFFFFu);
-        else
-          hipLaunchKernelGGL(k_measure_node, dim3(cdiv(bound * WAVE, 256)), dim3(256), 0, s, segs, lv, cx, cy, cz, meas,
-                             big_level ? big_min : 0xFFFFFFFFu);
-        if (spec_this) {
-          // this level from the plain sums; its exact sums on the second stream, from a snapshot of the coordinates
-          BSpecLevel& L = SP.L[SP.n];
-          const size_t* o = SO + (size_t)SP.n * SPEC_SLOTS;
-          L.pieces = (BPiece*)(arena + o[0]); L.preout = (BPre*)(arena + o[1]); L.own = (BSum*)(arena + o[2]);
-          L.comp = (BSum*)(arena + o[3]); L.wlist = (uint32_t*)(arena + o[4]); L.snap = (double*)(arena + o[5]);
-          L.segs = (BSeg*)(arena + o[6]); L.axis = (uint32_t*)(arena + o[7]); L.node = (uint32_t*)(arena + o[8]);
-          L.nleft = (uint32_t*)(arena + o[9]); L.cnt = (uint32_t*)(arena + o[10]); L.exact = (BMeas*)(arena + o[11]);
-          L.level = level; L.pad = 0;
-          SP.n++;
-          const size_t nsl = (size_t)nblocks * 2 * 3, nsl1 = (size_t)nblocks * 2;
-          L.prein = (BPre*)(arena + o[12]); L.seg_of = (uint32_t*)(arena + o[13]);
-          BPart* part = (BPart*)(arena + SO[(size_t)BIG_SPEC_MAX * SPEC_SLOTS + 1]);
-          double *sx = L.snap, *sy = L.snap + n1, *sz = L.snap + 2 * n1;
-          if (front_merged) {
-            const uint32_t nbp = cdiv(M, BIG_PB);
-            hipLaunchKernelGGL(k_level_front, dim3(nbp + cdiv(bound * 3 * WAVE, 256)), dim3(256), 0, s, segs, lv, seg_of, cx, cy, cz, M,
-                               part, L.snap, L.seg_of, (uint32_t)n1, nbp, meas, big_min);
-          } else {
-            hipLaunchKernelGGL(k_big_partials, dim3(cdiv(M, BIG_PB)), dim3(256), 0, s, segs, seg_of, cx, cy, cz, M, part, big_min);
-          }
-          if (merge_env && bound <= 16) {
-            // at most sixteen nodes: their plain sums, the decisions and the records in one workgroup
-            hipLaunchKernelGGL(k_nodes_small_approx, dim3(1), dim3(1024), 0, s, segs, lvl + level, (uint32_t)bound, meas, (uint32_t)bucket,
-                               kind, axis, splitval, nleft, irank, nodes, node_r, leaf_tab, small + 0, small + 1, part, L, spec_fault, big_min);
-            nodes_done = true;
-          } else {
-            hipLaunchKernelGGL(k_big_approx, dim3(cdiv(bound * WAVE, 256)), dim3(256), 0, s, segs, lv, part, meas, L, spec_fault, big_min);
-          }
-          if (!front_merged) hipLaunchKernelGGL(k_spec_snapshot, dim3(cdiv(M, 256)), dim3(256), 0, s, seg_of, cx, cy, cz, M, (uint32_t)n1, L.snap, L.seg_of);
-          // the exact chain of this level, all of it, on the snapshot.  The chains of different levels do not depend on each
-          // other: the root's (1.3 ms of one wave) runs on one background stream, every other level's on the second -- in a
-          // single stream the levels' chains queue up behind the root's and together outlast the build
-          // (round 6: ... and the second stream was then the build's critical path at 1M points -- the chains of levels 1 and 2,
-          // 0.6 and 0.4 ms, and five more levels' 0.12 ms each in a row outlast levels + finisher by 0.8 ms: the levels below
-          // the root alternate between two streams)
-          const bool use3 = side->s3 && (SP.n - 1) != 0;
-          const bool use4 = use3 && side->s4 && ((SP.n - 1) & 1) == 0;
-          hipStream_t sb = use4 ? side->s4 : (use3 ? side->s3 : side->s2);
-          void* tmpb = use4 ? tmp4 : (use3 ? tmp3 : tmp2);
-          BCHK(hipEventRecord(side->e1, s));
-          BCHK(hipStreamWaitEvent(sb, side->e1, 0));
-          // from the sixth level on (a balanced node's chain: M / 32 adds of 4.2 ns, a seventh of what the build takes) the
-          // exact sums are plain chains (TDTK_BUILD_CHAINFROM, lab: another level; 99: never)
-          if (level >= chain_from && chain_ok) {
-            hipLaunchKernelGGL(k_chain_exact, dim3(cdiv(bound * 3 * WAVE, 256)), dim3(256), 0, sb, L.segs, lv, sx, sy, sz, L.exact, L.axis, big_min);
-          } else {
-          hipLaunchKernelGGL(k_big_stats, dim3(cdiv(nblocks, 256 / WAVE)), dim3(256), 0, sb, L.segs, L.seg_of, sx, sy, sz, M,
-                             nblocks, L.pieces, L.prein, big_min, (const uint32_t*)L.axis);
-          size_t stb = scan_tmp;
-          BCHK(rocprim::inclusive_scan(tmpb, stb, L.prein, L.preout, nsl, BPreOp(), sb));
-          hipLaunchKernelGGL(k_big_emulate, dim3(cdiv(nsl1, 64)), dim3(64), 0, sb, L.segs, sx, sy, sz, nblocks,
-                             L.pieces, L.preout, L.own, big_dbg, (const uint32_t*)L.axis);
-          stb = scan_tmp;
-          BSum ident;
-          ident.T0 = ident.T1 = ident.mn0 = ident.mn1 = ident.mx0 = ident.mx1 = 0; ident.eb = BIG_ANY; ident.reset = 0u; ident.cnt = 0u; ident.pad = 0u;
-          BCHK(rocprim::exclusive_scan(tmpb, stb, L.own, L.comp, ident, nsl1, BSumOp(), sb));
-          hipLaunchKernelGGL(k_big_list, dim3(cdiv(nsl1, 256)), dim3(256), 0, sb, L.own, L.comp, (uint32_t)nsl1, L.wlist);
-          hipLaunchKernelGGL(k_big_stitch, dim3(cdiv(bound * 3 * WAVE, 256)), dim3(256), 0, sb, L.segs, lv, sx, sy, sz,
-                             nblocks, L.pieces, L.preout, L.own, L.comp, L.wlist, L.exact, big_dbg, big_min, (const uint32_t*)L.axis);
-          }
-        } else if (big_level) {
-          const size_t nsl = (size_t)nblocks * 2 * 3;
-          hipLaunchKernelGGL(k_big_stats, dim3(cdiv(nblocks, 256 / WAVE)), dim3(256), 0, s, segs, seg_of, cx, cy, cz, M,
-                             nblocks, pieces, prein, big_min);
-          size_t stb = scan_tmp;
-          BCHK(rocprim::inclusive_scan(tmp, stb, prein, preout, nsl, BPreOp(), s));
-          const size_t nsl1 = (size_t)nblocks * 2;
-          hipLaunchKernelGGL(k_big_emulate, dim3(cdiv(nsl1, 64)), dim3(64), 0, s, segs, cx, cy, cz, nblocks, pieces, preout,
-                             own, big_dbg);
-          stb = scan_tmp;
-          BSum ident;   // exclusive: comp[slot] = everything since the last reset BEFORE the slot = the run in front of it
-          ident.T0 = ident.T1 = ident.mn0 = ident.mn1 = ident.mx0 = ident.mx1 = 0; ident.eb = BIG_ANY; ident.reset = 0u; ident.cnt = 0u; ident.pad = 0u;
-          BCHK(rocprim::exclusive_scan(tmp, stb, own, comp, ident, nsl1, BSumOp(), s));
-          hipLaunchKernelGGL(k_big_list, dim3(cdiv(nsl1, 256)), dim3(256), 0, s, own, comp, (uint32_t)nsl1, wlist);
-          hipLaunchKernelGGL(k_big_stitch, dim3(cdiv(bound * 3 * WAVE, 256)), dim3(256), 0, s, segs, lv, cx, cy, cz, nblocks,
-                             pieces, preout, own, comp, wlist, meas, big_dbg, big_min);
-          if (big_dbg_all & 8) {
-            BMeas* meas2 = (BMeas*)(arena + O[30]);
-            hipLaunchKernelGGL(k_measure, dim3(cdiv(bound * 3 * WAVE, 256)), dim3(256), 0, s, segs, lv, cx, cy, cz, meas2, 0xFFFFFFFFu);
-            hipLaunchKernelGGL(k_big_dbg_compare, dim3(cdiv(bound, 256)), dim3(256), 0, s, segs, lv, meas, meas2, level, big_min);
-          }
-        }
-        size_t st = scan_tmp;
-        if (nodes_done) {}
-        else if (bound + 1 <= 1024) {
-          hipLaunchKernelGGL(k_nodes_small, dim3(1), dim3(1024), 0, s, segs, lvl + level, (uint32_t)bound, meas, (uint32_t)bucket,
-                             kind, axis, splitval, nleft, irank, nodes, node_r, leaf_tab, small + 0, small + 1);
-        } else {
-          hipLaunchKernelGGL(k_decide, dim3(cdiv(bound + 1, 256)), dim3(256), 0, s, segs, lv, (uint32_t)bound, meas,
-                             (uint32_t)bucket, kind, axis, splitval, nleft);
-          BCHK(rocprim::exclusive_scan(tmp, st, kind, irank, 0u, bound + 1, rocprim::plus<uint32_t>(), s));
-          hipLaunchKernelGGL(k_emit, dim3(cdiv(bound, 256)), dim3(256), 0, s, segs, lvl + level, meas, kind, axis, splitval,
-                             irank, nodes, node_r, leaf_tab, small + 0, small + 1);
-        }
-        // the partition pass (with no internal node at this level it moves nothing): two passes over the points while the
-        // one-launch scan's conditions hold (TDTK_BUILD_PART=0, lab: round 3's five)
-        const bool part2_env = [] { const char* e = lab_env("TDTK_BUILD_PART"); return !(e && e[0] == '0'); }();
-        if (part2_env && own_scan && level < 255u) {
-          const uint32_t ntiles = cdiv(M, PS_TILE), nbw = cdiv(M, 256u * PW_ROWS);
-          uint32_t* counter = reinterpret_cast<uint32_t*>(arena + o_scanstate);
-          unsigned long long* status = reinterpret_cast<unsigned long long*>(arena + o_scanstate + 64);
-          hipLaunchKernelGGL(k_part_scan, dim3(ntiles), dim3(PS_THREADS), 0, s, seg_of, kind, segs, axis, splitval, cx, cy, cz, M, nleft, posL,
-                             status, counter, level + 1u, ntiles, small + 2);
-          if (spec_this)
-            hipLaunchKernelGGL(k_part_swap_keep, dim3(nbw + cdiv(bound, 256)), dim3(256), 0, s, posL, segs, kind, irank, nleft, M, seg_of,
-                               perm, cx, cy, cz, nbw, lv, next, small + 2, SP.L[SP.n - 1]);
-          else
-            hipLaunchKernelGGL(k_part_swap, dim3(nbw + cdiv(bound, 256)), dim3(256), 0, s, posL, segs, kind, irank, nleft, M, seg_of,
-                               perm, cx, cy, cz, nbw, lv, next, small + 2);
-          BSeg* t = segs; segs = next; next = t;
-          continue;
-        }
-        hipLaunchKernelGGL(k_count, dim3(cdiv(M, 256 * CNT_ITERS)), dim3(256), 0, s, seg_of, kind, axis, splitval, cx, cy,
-                           cz, M, nleft);
-        {
-          const uint32_t nbm = cdiv(n1, 256);
-          if (spec_this)
-            hipLaunchKernelGGL(k_misplaced_children_keep, dim3(nbm + cdiv(bound, 256)), dim3(256), 0, s, seg_of, kind, segs, axis,
-                               splitval, nleft, cx, cy, cz, M, LR, nbm, lv, irank, next, small + 2, SP.L[SP.n - 1]);
-          else
-            hipLaunchKernelGGL(k_misplaced_children, dim3(nbm + cdiv(bound, 256)), dim3(256), 0, s, seg_of, kind, segs, axis,
-                               splitval, nleft, cx, cy, cz, M, LR, nbm, lv, irank, next, small + 2);
-        }
-        if (own_scan && level < 255u) {
-          BCHK(launch_scan_pair27(LR, AB, n1, arena + o_scanstate, level + 1u, small + 2, s));    // one launch (sort.hip)
-        } else {
-          st = scan_tmp;
-          BCHK(rocprim::exclusive_scan(tmp, st, LR, AB, 0ull, n1, rocprim::plus<unsigned long long>(), s));
-        }
-        hipLaunchKernelGGL(k_swaplist, dim3(cdiv(M, 256)), dim3(256), 0, s, seg_of, segs, LR, AB, M, posL, posR);
-        {
-          const uint32_t nbs = cdiv((size_t)M / 2 + 1, 256);
-          hipLaunchKernelGGL(k_swap_relabel, dim3(nbs + cdiv(M, 256)), dim3(256), 0, s, posL, posR, AB + M, perm, cx, cy, cz, nbs,
-                             segs, kind, irank, nleft, M, seg_of);
-        }
-        BSeg* t = segs; segs = next; next = t;
-      }
-      // one look per batch: the level counters so far and the root reference / largest bucket / error word together -- and,
-      // when the next level is the one handed to the finisher, its largest node
-      if (level == fin_level || fin_retry) { hipLaunchKernelGGL(k_fin_maxn, dim3(1), dim3(256), 0, s, segs, lvl + level, small + 4); have_max = true; }
-      else if (chain_look) hipLaunchKernelGGL(k_fin_maxn, dim3(1), dim3(256), 0, s, segs, lvl + level, small + 4);
-      BCHK(hipMemcpyAsync(hl, lvl, sizeof(BLevel) * (level + 1), hipMemcpyDeviceToHost, s));
-      BCHK(hipMemcpyAsync(h_small, small, 32, hipMemcpyDeviceToHost, s));
-      BCHK(hipStreamSynchronize(s));
-      const BLevel nx = hl[level];
-      if (h_small[2] || (nx.nseg && level >= BUILD_MAX_LEVELS)) {
-        // an empty child / non-finite coordinates -- or, on a speculated level, a cut so far off the exact one that a
-        // child came out empty: only then is the in-order build asked what the input really is
-        res.err = hipErrorInvalidValue; res.degenerate = true;
-        spec_suspect = (h_small[2] & 0x10000u) == 0u;      // (bit 16: the one-launch scan gave up waiting, see below)
-        if (h_small[2] & 0x10000u) { res.err = hipErrorLaunchTimeOut; res.degenerate = false; }
-        goto fail;
-      }
-      if (nx.nseg == 0) break;
-      known = nx.nseg; known_at = level;
-      batch = 2;
-      if (chain_look) {
-        chain_ok = h_small[4] <= M_ / 17u;
-        if (chain_ok || level >= (uint32_t)spec_levels || level >= fin_level) chain_look = false;
-        batch = chain_look ? 1u : ((fin_level != 0xFFFFFFFFu && level < fin_level) ? fin_level - level : 2u);
-      }
-      if (fin_retry) {
-        if (h_small[4] <= FIN_LDS && h_small[5] <= fin_cap && level + FIN_LV + 3u < BUILD_MAX_LEVELS) { fin_level = level; fin_retry = false; }   // hand over now (the block at the loop's top)
-        else have_max = false;
-      }
-    }
-    if (lvl_trace && !lvl_ev.empty()) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); (void)hipEventSynchronize(e); lvl_ev.push_back(e); }
-      fprintf(stderr, "BUILD_TRACE M=%u:", M);
-      for (size_t k = 0; k + 1 < lvl_ev.size(); k++) { float ms = 0; (void)hipEventElapsedTime(&ms, lvl_ev[k], lvl_ev[k + 1]); fprintf(stderr, " L%zu %.0f", k, ms * 1e3f); }
-      float tot = 0; (void)hipEventElapsedTime(&tot, lvl_ev.front(), lvl_ev.back());
-      fprintf(stderr, " | levels total %.0f us\n", tot * 1e3f);
-      for (hipEvent_t x : lvl_ev) (void)hipEventDestroy(x);
-    }
-    {
-      // the first level without nodes: its counters are the totals, its index the depth of the tree
-      depth = 0;
-      while (depth < level && hl[depth].nseg) depth++;
-      node_count = hl[depth].node_base; leaf_count = hl[depth].leaf_base;
-    }
-    res.max_leaf = h_small[1];
-    res.cb = bits_for(res.max_leaf);
-    res.table_mode = (bits_for(M) + res.cb) > 30;
-    if (spec && SP.n && !tail_enqueued) {
-      // the exact sums have to be there now: check every big node's cut against them, give its record the exact value
-      BCHK(hipEventRecord(side->e2, side->s2));
-      BCHK(hipStreamWaitEvent(s, side->e2, 0));
-      if (side->s3) { BCHK(hipEventRecord(side->e3, side->s3)); BCHK(hipStreamWaitEvent(s, side->e3, 0)); }
-          if (side->s4) { BCHK(hipEventRecord(side->e4, side->s4)); BCHK(hipStreamWaitEvent(s, side->e4, 0)); }
-      hipLaunchKernelGGL(k_spec_count, dim3(cdiv(M, 1024)), dim3(256), 0, s, SP, lvl, cx, cy, cz, M);
-      hipLaunchKernelGGL(k_spec_patch, dim3(4), dim3(256), 0, s, SP, lvl, nodes, small + 3);
-      BCHK(hipMemcpyAsync(&h_spec_err, small + 3, 4, hipMemcpyDeviceToHost, s));
-    }
-    if (!tail_enqueued) hipLaunchKernelGGL(k_points, dim3(cdiv(M, 256)), dim3(256), 0, s, perm, cx, cy, cz, M, pts);
-    if (!res.table_mode)
-      hipLaunchKernelGGL(k_pack_refs, dim3(cdiv(node_count ? node_count : 1, 256)), dim3(256), 0, s, nodes, node_count,
-                         leaf_tab, (uint32_t)res.cb, small + 0);
-    // (the finisher's path has looked at everything already -- the check word, and a root that is a node keeps its reference
-    // through k_pack_refs: what is enqueued from here on is waited for by the caller's own synchronisation, tree_finish)
-    const bool no_last_look = tail_enqueued && !res.table_mode && !(h_small[0] & REF_LEAF);
-    if (no_last_look) res.root_ref = h_small[0];
-    else BCHK(hipMemcpyAsync(&res.root_ref, small + 0, 4, hipMemcpyDeviceToHost, s));
-    // the records move out of the scratch into allocations of their exact size
-    if (node_count) {
-      BCHK((hipError_t)pool_malloc_raw((void**)&f_nodes, sizeof(KdNode) * (size_t)node_count));
-      BCHK((hipError_t)pool_malloc_raw((void**)&f_r, sizeof(double) * (size_t)node_count));
-      BCHK(hipMemcpyAsync(f_nodes, nodes, sizeof(KdNode) * (size_t)node_count, hipMemcpyDeviceToDevice, s));
-      BCHK(hipMemcpyAsync(f_r, node_r, sizeof(double) * (size_t)node_count, hipMemcpyDeviceToDevice, s));
-    }
-    if (res.table_mode) {
-      BCHK((hipError_t)pool_malloc_raw((void**)&f_leaf, sizeof(LeafEntry) * (size_t)leaf_count));
-      BCHK(hipMemcpyAsync(f_leaf, leaf_tab, sizeof(LeafEntry) * (size_t)leaf_count, hipMemcpyDeviceToDevice, s));
-    }
-    if (!no_last_look) BCHK(hipStreamSynchronize(s));
-    BCHK(hipGetLastError());
-    if (kLab && lab_env("TDTK_SPEC_DUMP")) {
-      (void)hipStreamSynchronize(s);
-      fprintf(stderr, "SPEC_DUMP M=%u spec %d SP.n %d tail_enqueued %d fin_level %u level %u h_spec_err %u depth %u\n", M, (int)spec, (int)SP.n, (int)tail_enqueued,
-              fin_level, level, h_spec_err, depth);
-      for (int l = 0; l < (int)SP.n; l++) {
-        const BSpecLevel& L = SP.L[l];
-        uint32_t nd[4], nlf[4], cn[4], axs[4]; BMeas ex[4]; BSeg sg[4];
-        (void)hipMemcpy(nd, L.node, sizeof nd, hipMemcpyDeviceToHost); (void)hipMemcpy(nlf, L.nleft, sizeof nlf, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(cn, L.cnt, sizeof cn, hipMemcpyDeviceToHost); (void)hipMemcpy(axs, L.axis, sizeof axs, hipMemcpyDeviceToHost);
-        (void)hipMemcpy(ex, L.exact, sizeof ex, hipMemcpyDeviceToHost); (void)hipMemcpy(sg, L.segs, sizeof sg, hipMemcpyDeviceToHost);
-        for (int k = 0; k < 4; k++)
-          fprintf(stderr, "  spec level %u entry %d: node %08x seg(start %u n %u) axis %u nleft %u cnt %u exact mean (%.17g %.17g %.17g)\n", L.level, k, nd[k],
-                  sg[k].start, sg[k].n, axs[k], nlf[k], cn[k], ex[k].mean[0], ex[k].mean[1], ex[k].mean[2]);
-      }
-    }
-    if (h_spec_err) { res.err = hipErrorNotReady; spec_suspect = true; goto fail; }     // a cut the exact sum would have made elsewhere: in order, then
-  }
-#ifdef TDTK_LAB
-  if (guards.n) {
-    uint32_t* bad = (uint32_t*)(arena + O[19]) + 40;       // (a word of `small` nothing else uses)
-    uint32_t h_bad = 0;
-    if (spec_on) { (void)hipStreamSynchronize(side->s2); if (side->s3) (void)hipStreamSynchronize(side->s3); if (side->s4) (void)hipStreamSynchronize(side->s4); }
-    (void)hipMemsetAsync(bad, 0, 4, s);
-    hipLaunchKernelGGL(k_guard_check, dim3(guards.n), dim3(64), 0, s, arena, guards, bad);
-    (void)hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, s);
-    (void)hipStreamSynchronize(s);
-    if (h_bad) {
-      fprintf(stderr, "tree build: arena guard %u of %u overwritten (M = %u): a region was written past its end\n", h_bad - 1u, guards.n, M);
-      res.err = hipErrorAssert;
-      goto fail;
-    }
-  }
-#endif
-  res.nodes = f_nodes; res.node_r = f_r; res.leaf_tab = f_leaf; res.pts = pts;
-  res.n_internal = node_count; res.n_leaves = leaf_count; res.max_depth = depth;
-  return res;
-fail:
-  if (spec_on) { (void)hipStreamSynchronize(side->s2); if (side->s3) (void)hipStreamSynchronize(side->s3); if (side->s4) (void)hipStreamSynchronize(side->s4); }   // nothing of this build may still be running in the arena
-  if (f_nodes) pool_free(f_nodes);
-  if (f_r) pool_free(f_r);
-  if (f_leaf) pool_free(f_leaf);
-  if (pts) pool_free(pts);
-  if (spec_on && spec_suspect) {
-    // a failed check, or a degenerate split on a tree cut at the plain sums: the in-order build decides what the input
-    // really is.  (Anything else -- no memory, a failed launch -- is returned as it is: building twice would not help.)
-    (void)hipStreamSynchronize(s);
-    (void)hipGetLastError();
-    DevBuildResult again = device_build_tree(d_xyz, M_, bucket, arena_, s, nullptr, no_finish);
-    again.respeculated = again.err == hipSuccess;     // tdtk_build_respeculated counts cuts that really were off, not bad inputs
-    return again;
-  }
-  if (res.err == hipSuccess) res.err = hipErrorUnknown;
-  return res;
-}
-
-// the per-level buffers of the speculative build behind the main layout: SO[SPEC_SLOTS l + k] for level l,
-// SO[SPEC_SLOTS BIG_SPEC_MAX] the second stream's scan temporary, + 1 the block partials; returns the total size.  The
-// chain is long on the top levels only (two-sided coordinates), and a level's snapshot is 28 bytes per point: the
-// eight top levels are speculated, big levels below them (clouds of more than 2M points) go the in-order way.
+// ---- the arena: every temporary of a build, and the node / bucket records while their number is still unknown --------
+// the per-level buffers of the speculative build behind the base layout.  The chain is long on the top levels only
+// (two-sided coordinates), and a level's snapshot is 28 bytes per point: the eight top levels are speculated, big levels
+// below them (clouds of more than 2M points) go the in-order way.
 #define BIG_SPEC_LEVELS 8
-static size_t spec_layout(size_t M, size_t base, size_t* SO, int* nlev_out)
-{
-  const uint32_t BIG_MIN_M = build_big_min(M);
-  size_t off = (base + 255) & ~(size_t)255;
-  int nlev = 0;
-  if (M >= BIG_MIN_M)
-    for (uint32_t level = 0; level < BUILD_MAX_LEVELS && (M >> level) >= build_big_level_min(M) && nlev < BIG_SPEC_LEVELS; level++) nlev++;
-  if (getenv("TDTK_BUILD_SPEC") && getenv("TDTK_BUILD_SPEC")[0] == '0') nlev = 0;
-  const size_t n1 = M + 1, nsl = 6 * (M / BIG_CH + 2), nsl1 = nsl / 3 + 3;
-  auto take = [&](size_t bytes, size_t* slot) { if (slot) *slot = off; off += (bytes + 255) & ~(size_t)255; arena_guard(off); };
-  for (int l = 0; l < nlev; l++) {
-    size_t maxseg = (l < 40) ? ((size_t)1 << l) : n1;
-    if (maxseg > n1) maxseg = n1;
-    size_t* o = SO ? SO + (size_t)l * SPEC_SLOTS : nullptr;
-    take(sizeof(BPiece) * nsl, o ? o + 0 : nullptr);
-    take(sizeof(BPre) * nsl, o ? o + 1 : nullptr);
-    take(sizeof(BSum) * nsl1, o ? o + 2 : nullptr);
-    take(sizeof(BSum) * nsl1, o ? o + 3 : nullptr);
-    take(4 * (nsl1 + 1), o ? o + 4 : nullptr);
-    take(8 * 3 * n1, o ? o + 5 : nullptr);
-    take(sizeof(BSeg) * maxseg, o ? o + 6 : nullptr);
-    take(4 * maxseg, o ? o + 7 : nullptr);
-    take(4 * maxseg, o ? o + 8 : nullptr);
-    take(4 * maxseg, o ? o + 9 : nullptr);
-    take(4 * maxseg, o ? o + 10 : nullptr);
-    take(sizeof(BMeas) * maxseg, o ? o + 11 : nullptr);
-    take(sizeof(BPre) * nsl, o ? o + 12 : nullptr);
-    take(4 * n1, o ? o + 13 : nullptr);
-  }
-  size_t scan_tmp = 0;
-  if (nlev) {
-    BSum* zs = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, scan_tmp, zs, zs, BSum(), nsl, BSumOp(), (hipStream_t)0);
-    BPre* zp = nullptr; size_t tp = 0;
-    (void)rocprim::inclusive_scan(nullptr, tp, zp, zp, nsl, BPreOp(), (hipStream_t)0);
-    if (tp > scan_tmp) scan_tmp = tp;
-  }
-  take(scan_tmp + 256, SO ? SO + (size_t)BIG_SPEC_MAX * SPEC_SLOTS : nullptr);
-  take(sizeof(BPart) * 2 * (M / BIG_PB + 2), SO ? SO + (size_t)BIG_SPEC_MAX * SPEC_SLOTS + 1 : nullptr);
-  take(scan_tmp + 256, SO ? SO + (size_t)BIG_SPEC_MAX * SPEC_SLOTS + 2 : nullptr);      // the third stream's scan temporary
-  take(scan_tmp + 256, SO ? SO + (size_t)BIG_SPEC_MAX * SPEC_SLOTS + 3 : nullptr);      // the fourth's
-  if (nlev_out) *nlev_out = nlev;
-  return off;
-}
+struct SpecRegions {
+  Region<BPiece> pieces; Region<BPre> preout; Region<BSum> own, comp; Region<uint32_t> wlist; Region<double> snap;
+  Region<BSeg> segs; Region<uint32_t> axis, node, nleft, cnt; Region<BMeas> exact; Region<BPre> prein; Region<uint32_t> seg_of;
+};
+struct BuildArena {
+  Region<uint32_t> perm, seg_of; Region<double> cx, cy, cz;
+  Region<uint32_t> spare_f, nleft; Region<unsigned long long> LR, AB;
+  Region<uint32_t> posL, posR;
+  Region<BSeg> segA, segB; Region<BMeas> meas;
+  Region<uint32_t> kind, axis; Region<double> splitval; Region<uint32_t> irank;
+  Region<void> tmp; Region<uint32_t> small;
+  Region<KdNode> nodes; Region<double> node_r; Region<LeafEntry> leaf_tab;
+  Region<BLevel> lvl;                              // per-level counters
+  Region<BPiece> pieces;                           // pieces of big nodes: 3 axes x 2 per block
+  Region<BPre> prein, preout;                      // plain prefix in / out
+  Region<BSum> own, comp;                          // piece summaries, folded runs
+  Region<uint32_t> wlist;                          // slots of the walked pieces, in run order
+  Region<BMeas> dbg_meas;                          // debug (TDTK_BIG_DEBUG & 8): the chain's results
+  Region<char> scan_state;                         // state of the one-launch scans (sort.hip's, k_part_scan's)
+  // subtrees finished by one workgroup each (k_fin_*): staging of their records, their own kind / rank arrays, tables
+  Region<KdNode> fin_nodes; Region<double> fin_r; Region<LeafEntry> fin_leaf;
+  Region<uint32_t> fin_kind, fin_irank;
+  Region<BSeg> fin_roots; Region<FinTab> fin_tab; Region<FinOff> fin_off;
+  Region<uint32_t> fin_tot;                        // the levels' totals
+  Region<uint32_t> fin_nlev, fin_maxleaf;          // the subtrees' depths, their largest buckets
+  size_t scan_tmp = 0;                             // bytes rocPRIM's scans of the base layout ask for
+  size_t base_bytes = 0;                           // the arena of a build without background streams ends here
+  // behind it, with background streams: the speculated levels, then the second stream's scan temporary, the block
+  // partials, the third and the fourth stream's scan temporaries
+  SpecRegions spec[BIG_SPEC_LEVELS];
+  Region<void> tmp2; Region<BPart> part; Region<void> tmp3, tmp4;
+  size_t total = 0;
+  GuardList guards{};                              // lab: where the guards are
+};
 
-static size_t build_layout(size_t M, size_t* O, size_t* scan_tmp_out)
+static void carve_build_arena(BuildArena& A, size_t M, bool dbg_meas, bool with_spec, int spec_levels)
 {
   size_t scan_tmp = 0;
+  const size_t nsl = 6 * (M / BIG_CH + 2);
   {
     uint32_t* z = nullptr;
     (void)rocprim::exclusive_scan(nullptr, scan_tmp, z, z, 0u, M + 1, rocprim::plus<uint32_t>(), (hipStream_t)0);
@@ -2362,7 +1799,6 @@ static size_t build_layout(size_t M, size_t* O, size_t* scan_tmp_out)
     size_t t8 = 0;
     (void)rocprim::exclusive_scan(nullptr, t8, z8, z8, 0ull, M + 1, rocprim::plus<unsigned long long>(), (hipStream_t)0);
     if (t8 > scan_tmp) scan_tmp = t8;
-    const size_t nsl = 6 * (M / BIG_CH + 2);
     BPre* zp = nullptr; size_t tp = 0;
     (void)rocprim::inclusive_scan(nullptr, tp, zp, zp, nsl, BPreOp(), (hipStream_t)0);
     if (tp > scan_tmp) scan_tmp = tp;
@@ -2371,33 +1807,773 @@ static size_t build_layout(size_t M, size_t* O, size_t* scan_tmp_out)
     if (ts > scan_tmp) scan_tmp = ts;
   }
   const size_t n1 = M + 1;
-  size_t off = 0;
-  int k = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; arena_guard(off); if (O) O[k] = o; k++; return o; };
-  take(4 * n1); take(4 * n1); take(8 * n1); take(8 * n1); take(8 * n1);      // perm segof cx cy cz
-  take(4 * n1); take(4 * n1); take(8 * n1); take(8 * n1);                    // f F LR AB
-  take(4 * n1); take(4 * n1);                                                // posL posR
-  take(sizeof(BSeg) * n1); take(sizeof(BSeg) * n1); take(sizeof(BMeas) * n1);
-  take(4 * n1); take(4 * n1); take(8 * n1); take(4 * n1);                    // kind axis split irank
-  take(scan_tmp + 256); take(256);                                          // tmp small
-  take(sizeof(KdNode) * n1); take(sizeof(double) * n1); take(sizeof(LeafEntry) * n1);   // nodes node_r leaf_tab
-  take(sizeof(BLevel) * (BUILD_MAX_LEVELS + 2));                            // 23 per-level counters
-  const size_t nsl = 6 * (M / BIG_CH + 2);                                  // pieces of big nodes: 3 axes x 2 per block
-  take(sizeof(BPiece) * nsl);                                               // 24
-  take(sizeof(BPre) * nsl); take(sizeof(BPre) * nsl);                       // 25 26 plain prefix in / out
-  take(sizeof(BSum) * nsl); take(sizeof(BSum) * nsl);                       // 27 28 piece summaries, folded runs
-  take(4 * (nsl + 1));                                                      // 29 slots of the walked pieces, in run order
-  take(lab_env("TDTK_BIG_DEBUG") && (atoi(lab_env("TDTK_BIG_DEBUG")) & 8) ? sizeof(BMeas) * n1 : 256);   // 30 debug: the chain's results
-  take(std::max(scan_pair27_state_bytes(n1), part_state_bytes(n1)));        // 31 state of the one-launch scans (sort.hip's, k_part_scan's)
-  // subtrees finished by one workgroup each (k_fin_*): staging of their records, their own kind / rank arrays, tables
-  take(sizeof(KdNode) * n1); take(sizeof(double) * n1); take(sizeof(LeafEntry) * n1);   // 32 33 34
+  ArenaCarver c;
+  c.take(A.perm, 4 * n1); c.take(A.seg_of, 4 * n1); c.take(A.cx, 8 * n1); c.take(A.cy, 8 * n1); c.take(A.cz, 8 * n1);
+  c.take(A.spare_f, 4 * n1); c.take(A.nleft, 4 * n1); c.take(A.LR, 8 * n1); c.take(A.AB, 8 * n1);
+  c.take(A.posL, 4 * n1); c.take(A.posR, 4 * n1);
+  c.take(A.segA, sizeof(BSeg) * n1); c.take(A.segB, sizeof(BSeg) * n1); c.take(A.meas, sizeof(BMeas) * n1);
+  c.take(A.kind, 4 * n1); c.take(A.axis, 4 * n1); c.take(A.splitval, 8 * n1); c.take(A.irank, 4 * n1);
+  c.take(A.tmp, scan_tmp + 256); c.take(A.small, 256);
+  c.take(A.nodes, sizeof(KdNode) * n1); c.take(A.node_r, sizeof(double) * n1); c.take(A.leaf_tab, sizeof(LeafEntry) * n1);
+  c.take(A.lvl, sizeof(BLevel) * (BUILD_MAX_LEVELS + 2));
+  c.take(A.pieces, sizeof(BPiece) * nsl);
+  c.take(A.prein, sizeof(BPre) * nsl); c.take(A.preout, sizeof(BPre) * nsl);
+  c.take(A.own, sizeof(BSum) * nsl); c.take(A.comp, sizeof(BSum) * nsl);
+  c.take(A.wlist, 4 * (nsl + 1));
+  c.take(A.dbg_meas, dbg_meas ? sizeof(BMeas) * n1 : 256);
+  c.take(A.scan_state, std::max(scan_pair27_state_bytes(n1), part_state_bytes(n1)));
+  c.take(A.fin_nodes, sizeof(KdNode) * n1); c.take(A.fin_r, sizeof(double) * n1); c.take(A.fin_leaf, sizeof(LeafEntry) * n1);
   const size_t fcap = fin_max_subtrees(M);
-  take(4 * (n1 + fcap)); take(4 * (n1 + fcap));                                        // 35 36 kind, irank
-  take(sizeof(BSeg) * fcap); take(sizeof(FinTab) * fcap); take(sizeof(FinOff) * fcap);   // 37 38 39
-  take(4 * 2 * (FIN_LV + 2));                                                          // 40 the levels' totals
-  take(4 * fcap); take(4 * fcap);                                                      // 41 42 the subtrees' depths, their largest buckets
-  if (scan_tmp_out) *scan_tmp_out = scan_tmp;
-  return off;
+  c.take(A.fin_kind, 4 * (n1 + fcap)); c.take(A.fin_irank, 4 * (n1 + fcap));
+  c.take(A.fin_roots, sizeof(BSeg) * fcap); c.take(A.fin_tab, sizeof(FinTab) * fcap); c.take(A.fin_off, sizeof(FinOff) * fcap);
+  c.take(A.fin_tot, 4 * 2 * (FIN_LV + 2));
+  c.take(A.fin_nlev, 4 * fcap); c.take(A.fin_maxleaf, 4 * fcap);
+  A.scan_tmp = scan_tmp;
+  A.base_bytes = A.total = c.off;
+  if (with_spec) {
+    c.off = (c.off + 255) & ~(size_t)255;
+    const size_t nsl1 = nsl / 3 + 3;
+    for (int l = 0; l < spec_levels; l++) {
+      SpecRegions& S = A.spec[l];
+      size_t maxseg = (l < 40) ? ((size_t)1 << l) : n1;
+      if (maxseg > n1) maxseg = n1;
+      c.take(S.pieces, sizeof(BPiece) * nsl); c.take(S.preout, sizeof(BPre) * nsl);
+      c.take(S.own, sizeof(BSum) * nsl1); c.take(S.comp, sizeof(BSum) * nsl1);
+      c.take(S.wlist, 4 * (nsl1 + 1)); c.take(S.snap, 8 * 3 * n1);
+      c.take(S.segs, sizeof(BSeg) * maxseg);
+      c.take(S.axis, 4 * maxseg); c.take(S.node, 4 * maxseg); c.take(S.nleft, 4 * maxseg); c.take(S.cnt, 4 * maxseg);
+      c.take(S.exact, sizeof(BMeas) * maxseg); c.take(S.prein, sizeof(BPre) * nsl); c.take(S.seg_of, 4 * n1);
+    }
+    size_t side_tmp = 0;
+    if (spec_levels) {
+      BSum* zs = nullptr;
+      (void)rocprim::exclusive_scan(nullptr, side_tmp, zs, zs, BSum(), nsl, BSumOp(), (hipStream_t)0);
+      BPre* zp = nullptr; size_t tp = 0;
+      (void)rocprim::inclusive_scan(nullptr, tp, zp, zp, nsl, BPreOp(), (hipStream_t)0);
+      if (tp > side_tmp) side_tmp = tp;
+    }
+    c.take(A.tmp2, side_tmp + 256);
+    c.take(A.part, sizeof(BPart) * 2 * (M / BIG_PB + 2));
+    c.take(A.tmp3, side_tmp + 256);
+    c.take(A.tmp4, side_tmp + 256);
+    A.total = c.off;
+  }
+  A.guards = c.guards;
+}
+
+// ---- the plan: everything about a build that depends only on its size, its bucket, whether it has background streams,
+// `no_finish` and the environment.  make_build_plan is the only reader of the environment in this file, and both the
+// sizing (device_build_arena_bytes) and the build go through it: they cannot disagree.  The switches are read per plan.
+struct BuildPlan {
+  uint32_t big_min = 0, big_level_min = 0;   // the piecewise path's node threshold (every k_big_* kernel gets it) and level threshold
+  bool chain_only = false, use_big = false;
+  bool measure_per_axis_always = false;
+  int big_dbg_all = 0;      // TDTK_BIG_DEBUG: 1: never trust a folded run, 2: walk every piece, 4: garbage in the arena, 8: compare with the chain
+  bool spec = false;        // speculative splits
+  int spec_levels = 0, spec_fault = 0;
+  uint32_t chain_from = 0;
+  bool chain_look = false;
+  bool own_scan = false, part2 = false, merge = false;
+  uint32_t fin_cap = 0, fin_level = 0xFFFFFFFFu;
+  bool fin_half = false, fin_wave = false;
+  uint32_t fw_debug = 0;
+  uint32_t first_batch = 1;
+  bool lvl_trace = false, fin_trace = false, spec_dump = false, guard_selftest = false;
+  BuildArena A;
+};
+
+static BuildPlan make_build_plan(size_t M, int bucket, bool has_side, int no_finish)
+{
+  const auto on = [](const char* e) { return !(e && e[0] == '0'); };     // on unless set to 0
+  const auto is1 = [](const char* e) { return e && e[0] == '1'; };
+  BuildPlan P;
+  const bool small_rule = on(lab_env("TDTK_BUILD_BIGMIN"));
+  P.big_level_min = build_big_level_min(M, small_rule, on(lab_env("TDTK_BUILD_BIGGROW")));
+  P.big_min = build_big_min(M, small_rule, P.big_level_min);
+  P.chain_only = is1(lab_env("TDTK_BUILD_CHAIN"));
+  P.use_big = !P.chain_only && M >= P.big_min;
+  // TDTK_MEASURE=axis: round 2's wave per (node, axis) for the nodes below the piecewise path (k_measure); default: a wave
+  // per node (k_measure_node).  With TDTK_BUILD_CHAIN=1 (no piecewise path: chains of any length) the long-chain kernel.
+  { const char* e = lab_env("TDTK_MEASURE"); P.measure_per_axis_always = (e && e[0] == 'a') || P.chain_only; }
+  { const char* e = lab_env("TDTK_BIG_DEBUG"); P.big_dbg_all = e ? atoi(e) : 0; }
+  // speculative splits: TDTK_BUILD_SPEC=0 builds in order; TDTK_BUILD_SPEC_FAULT=1 (tests) cuts every big node elsewhere than
+  // the exact sum would, so that the final check fails and the in-order path takes over
+  const bool spec_env = on(getenv("TDTK_BUILD_SPEC"));
+  P.spec_fault = is1(lab_env("TDTK_BUILD_SPEC_FAULT")) ? 1 : 0;
+  P.spec = spec_env && has_side && P.use_big && !P.big_dbg_all;
+  if (spec_env && M >= P.big_min)
+    for (uint32_t level = 0; level < BUILD_MAX_LEVELS && (M >> level) >= P.big_level_min && P.spec_levels < BIG_SPEC_LEVELS; level++) P.spec_levels++;
+  // the partition's scan in one launch while the positions fit its 27-bit counters (TDTK_OWN_SCAN=0: rocPRIM's two)
+  P.own_scan = on(lab_env("TDTK_OWN_SCAN")) && M + 1 < ((size_t)1 << 27);
+  // the partition pass in two passes over the points while the one-launch scan's conditions hold (TDTK_BUILD_PART=0, lab: round 3's five)
+  P.part2 = on(lab_env("TDTK_BUILD_PART")) && P.own_scan;
+  // a speculated level's chains of small nodes ride in the launch of its partial sums (k_level_front)
+  P.merge = on(lab_env("TDTK_BUILD_MERGE"));
+  // diagnostics (TDTK_BUILD_TRACE=1): an event at the start of every level on the build's stream; the elapsed times are
+  // printed when the build is done -- what a level costs when no profiler is serialising the launches
+  { const char* e = lab_env("TDTK_BUILD_TRACE"); P.lvl_trace = e && (e[0] == '1' || e[0] == '2'); P.fin_trace = e && e[0] == '2'; }
+  P.spec_dump = kLab && lab_env("TDTK_SPEC_DUMP");
+  // (TDTK_GUARD_SELFTEST=1: one word behind the sixth region is overwritten on purpose -- the build must fail)
+  P.guard_selftest = lab_env("TDTK_GUARD_SELFTEST") != nullptr;
+  P.first_batch = 1;
+  for (size_t c = (size_t)(bucket > 0 ? bucket : 1); c < M; c <<= 1) P.first_batch++;
+  P.first_batch += 2;   // mean splits do not halve: a 1M-point cloud is 18-19 levels deep, not 17, and a level past the end of the
+                        // tree costs less than the host's look (it moves nothing)
+  // The level from which every node is finished by one workgroup (k_fin_subtrees): the first at which a balanced node
+  // holds at most FIN_HANDOFF points.  TDTK_BUILD_FINISH=0 (lab): level by level to the end.
+  P.fin_cap = fin_max_subtrees(M);
+  {
+    uint32_t L = 0;
+    // (round 6: a cloud of two million points and more goes on by levels until a balanced node fits a wave's finisher --
+    //  two or three more levels of launches against most of the workgroup finisher's time; TDTK_BUILD_HANDOFF, lab)
+    const char* e = lab_env("TDTK_BUILD_HANDOFF");
+    const uint32_t handoff_env = e ? (uint32_t)atoi(e) : 0u;
+    const uint32_t handoff = handoff_env ? handoff_env : (M >= FIN_HANDOFF_WAVE_FROM ? FIN_HANDOFF_WAVE : FIN_HANDOFF);
+    while ((M >> L) > handoff) L++;
+    if (on(lab_env("TDTK_BUILD_FINISH")) && no_finish == 0 && bucket >= 6 && L < 31 && (1u << L) <= P.fin_cap && !P.big_dbg_all) P.fin_level = L;
+  }
+  if (P.fin_level != 0xFFFFFFFFu) P.first_batch = P.fin_level;
+  // subtrees of at most FIN_LDS_HALF points two workgroups to a compute unit, then (if the level has any) the larger ones
+  // ... and in front of both, the subtrees of at most FW_CAP points, a wave each
+  P.fin_half = on(lab_env("TDTK_BUILD_FINHALF"));
+  P.fin_wave = on(lab_env("TDTK_BUILD_FINWAVE"));
+  { const char* e = lab_env("TDTK_FW_DEBUG"); P.fw_debug = e ? (uint32_t)atoi(e) : 0u; }
+  // From chain_from on the exact sums of a speculated level are plain chains in the background (k_chain_exact) -- 4.2 ns
+  // per point of the level's largest node, which must end before the build does.  A balanced cloud's do; a cloud with a
+  // third of its points in one tight cluster has a 1.3M-point node on levels 5 .. 10 of 4M points, and its chains (5.6 ms)
+  // were what the build waited for.  So a build of two million points and more -- where a look costs a few per cent of a
+  // level -- looks at the largest node before the first such level (and before every further one while it is too large):
+  // beyond M / 17 points the level takes the piecewise path.
+  // chain_from: the first level whose balanced node's chain (4.2 ns a point) is a small share of what a build of this
+  // size takes -- 20 000 + M / 50 points, the sixth level at the latest: level 0 for a 15K-point scan, 1 at 40K, 2 at 81K,
+  // 4 at 300K, 5 from 1M on (measured: 4 at 1M is 8 % slower, 3 at 300K 4 %).  On small clouds this is not about bandwidth
+  // but about the HOST: a level's piecewise path is nine launches on the side streams, and enqueuing them (3-4 us
+  // apiece) was what a level of a 15K .. 40K-point build took (15K: 0.50 -> 0.41 ms, lab library).
+  if (const char* e = lab_env("TDTK_BUILD_CHAINFROM")) P.chain_from = (uint32_t)atoi(e);
+  else {
+    const size_t thresh = 20000u + M / 50u;
+    while (P.chain_from < 5u && (M >> P.chain_from) > thresh) P.chain_from++;
+  }
+  P.chain_look = P.spec && M >= 2000000u && P.fin_level != 0xFFFFFFFFu && P.chain_from < P.fin_level && P.chain_from < (uint32_t)P.spec_levels;
+  if (P.chain_look) P.first_batch = P.chain_from;
+  carve_build_arena(P.A, M, (P.big_dbg_all & 8) != 0, has_side, P.spec_levels);
+  return P;
+}
+
+size_t device_build_arena_bytes(size_t M, bool with_background_chain)
+{
+  return make_build_plan(M, 0, with_background_chain, 0).A.total;
+}
+
+// ---- a build's run: what its stages hand to each other ---------------------------------------------------------------
+struct BuildRun {
+  const BuildPlan& P;
+  const double* d_xyz; size_t M_; uint32_t M; int bucket; char* arena; hipStream_t s; const BuildSide* side; int no_finish;
+  // the regions of the arena the level loop works in
+  uint32_t *perm, *seg_of; double *cx, *cy, *cz; uint32_t *nleft, *posL, *posR; unsigned long long *LR, *AB;
+  BSeg *segs, *next;                          // the nodes of this level and of the next one: they trade places per level
+  BMeas* meas; uint32_t *kind, *axis, *irank; double* splitval; void* tmp; uint32_t* small;
+  KdNode* nodes; double* node_r; LeafEntry* leaf_tab; BLevel* lvl;
+  uint32_t nblocks;
+  // speculation
+  bool spec = false;                          // on, and the side streams may hold work of this build
+  BSpecAll SP;
+  uint32_t h_spec_err = 0;
+  bool spec_suspect = false;                  // the failure may be the speculation's doing (device_build_tree's way out)
+  // the level loop
+  uint32_t level = 0, known = 1, known_at = 0, batch = 1;
+  uint32_t fin_level; bool have_max = false, fin_retry = false;
+  uint32_t fin_nodes = 0, fin_maxn = 0;       // nodes of the level about to be handed over, the largest of them (k_fin_maxn)
+  bool chain_ok = true, chain_look;
+  bool tail_enqueued = false;
+  bool redo_by_levels = false;                // a subtree deeper than the finishers' tables
+  // The host's looks at the device land in pinned memory when the caller has some (a copy into pageable memory is a
+  // synchronisation of its own): h_small = small[0 .. 7] (root reference, largest bucket, error word, check word, the
+  // hand-over level's largest node and node count), hl = the level counters.
+  std::vector<unsigned char> h_pageable;
+  uint32_t* h_small = nullptr; BLevel* hl = nullptr;
+  std::vector<hipEvent_t> lvl_ev;             // TDTK_BUILD_TRACE
+  // the result
+  KdPoint* pts = nullptr; KdNode* f_nodes = nullptr; double* f_r = nullptr; LeafEntry* f_leaf = nullptr;
+  uint32_t node_count = 0, leaf_count = 0, depth = 0;
+  DevBuildResult res{};
+
+  BuildRun(const BuildPlan& P_, const double* d_xyz_, size_t M, int bucket_, void* arena_, hipStream_t s_, const BuildSide* side_, int no_finish_)
+      : P(P_), d_xyz(d_xyz_), M_(M), M((uint32_t)M), bucket(bucket_), arena(static_cast<char*>(arena_)), s(s_), side(side_), no_finish(no_finish_)
+  {
+    const BuildArena& A = P.A;
+    perm = A.perm.in(arena); seg_of = A.seg_of.in(arena); cx = A.cx.in(arena); cy = A.cy.in(arena); cz = A.cz.in(arena);
+    nleft = A.nleft.in(arena); posL = A.posL.in(arena); posR = A.posR.in(arena); LR = A.LR.in(arena); AB = A.AB.in(arena);
+    segs = A.segA.in(arena); next = A.segB.in(arena); meas = A.meas.in(arena);
+    kind = A.kind.in(arena); axis = A.axis.in(arena); irank = A.irank.in(arena); splitval = A.splitval.in(arena);
+    tmp = A.tmp.in(arena); small = A.small.in(arena);
+    nodes = A.nodes.in(arena); node_r = A.node_r.in(arena); leaf_tab = A.leaf_tab.in(arena); lvl = A.lvl.in(arena);
+    nblocks = cdiv(this->M, BIG_CH);
+    SP.n = 0;
+    batch = P.first_batch; fin_level = P.fin_level; chain_look = P.chain_look;
+  }
+};
+
+// the host waits for everything on the background streams: nothing of this build may still be running in the arena
+static void wait_side_streams(const BuildSide* side)
+{
+  (void)hipStreamSynchronize(side->s2);
+  if (side->s3) (void)hipStreamSynchronize(side->s3);
+  if (side->s4) (void)hipStreamSynchronize(side->s4);
+}
+
+static void trace_level_start(BuildRun& R)
+{
+  if (!R.P.lvl_trace) return;
+  hipEvent_t e;
+  if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, R.s); R.lvl_ev.push_back(e); }
+}
+static void trace_levels_print(BuildRun& R)
+{
+  if (!R.P.lvl_trace || R.lvl_ev.empty()) return;
+  std::vector<hipEvent_t>& lvl_ev = R.lvl_ev;
+  hipEvent_t e;
+  if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, R.s); (void)hipEventSynchronize(e); lvl_ev.push_back(e); }
+  fprintf(stderr, "BUILD_TRACE M=%u:", R.M);
+  for (size_t k = 0; k + 1 < lvl_ev.size(); k++) { float ms = 0; (void)hipEventElapsedTime(&ms, lvl_ev[k], lvl_ev[k + 1]); fprintf(stderr, " L%zu %.0f", k, ms * 1e3f); }
+  float tot = 0; (void)hipEventElapsedTime(&tot, lvl_ev.front(), lvl_ev.back());
+  fprintf(stderr, " | levels total %.0f us\n", tot * 1e3f);
+  for (hipEvent_t x : lvl_ev) (void)hipEventDestroy(x);
+  lvl_ev.clear();
+}
+static void trace_finisher_print(BuildRun& R)
+{
+  uint32_t ph[10];
+  if (hipMemcpy(ph, R.small + SM_FIN_PHASES, sizeof ph, hipMemcpyDeviceToHost) != hipSuccess) return;
+  fprintf(stderr, "FIN_TRACE subtree 0 (100 MHz ticks -> us):");
+  const char* nm[10] = {"", "measure (wave: measure+emit)", "decide (wave: scan)", "rank (wave: children+swap)", "emit+count (wave: write-back)", "mark+children", "scan", "swaplist", "swap+relabel", ""};
+  for (int k = 1; k < 9; k++) fprintf(stderr, " %s %.1f", nm[k], ph[k] / 100.0);
+  fprintf(stderr, "\n");
+}
+static void spec_dump(BuildRun& R)
+{
+  (void)hipStreamSynchronize(R.s);
+  fprintf(stderr, "SPEC_DUMP M=%u spec %d SP.n %d tail_enqueued %d fin_level %u level %u h_spec_err %u depth %u\n", R.M, (int)R.P.spec, (int)R.SP.n, (int)R.tail_enqueued,
+          R.fin_level, R.level, R.h_spec_err, R.depth);
+  for (int l = 0; l < (int)R.SP.n; l++) {
+    const BSpecLevel& L = R.SP.L[l];
+    uint32_t nd[4], nlf[4], cn[4], axs[4]; BMeas ex[4]; BSeg sg[4];
+    (void)hipMemcpy(nd, L.node, sizeof nd, hipMemcpyDeviceToHost); (void)hipMemcpy(nlf, L.nleft, sizeof nlf, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(cn, L.cnt, sizeof cn, hipMemcpyDeviceToHost); (void)hipMemcpy(axs, L.axis, sizeof axs, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(ex, L.exact, sizeof ex, hipMemcpyDeviceToHost); (void)hipMemcpy(sg, L.segs, sizeof sg, hipMemcpyDeviceToHost);
+    for (int k = 0; k < 4; k++)
+      fprintf(stderr, "  spec level %u entry %d: node %08x seg(start %u n %u) axis %u nleft %u cnt %u exact mean (%.17g %.17g %.17g)\n", L.level, k, nd[k],
+              sg[k].start, sg[k].n, axs[k], nlf[k], cn[k], ex[k].mean[0], ex[k].mean[1], ex[k].mean[2]);
+  }
+}
+
+static hipError_t build_setup(BuildRun& R)
+{
+  const BuildPlan& P = R.P;
+  const BuildArena& A = P.A;
+  const size_t n1 = (size_t)R.M + 1;
+  arena_guards_arm(R.arena, A.guards, R.s);
+  if (P.guard_selftest && A.guards.n > 5) (void)hipMemsetAsync(R.arena + A.guards.off[5] + 8, 0, 4, R.s);
+  BCHK((hipError_t)pool_malloc_raw((void**)&R.pts, sizeof(KdPoint) * (size_t)R.M));
+  R.spec = P.spec;
+  if (P.big_dbg_all & 4) BCHK(hipMemsetAsync(R.arena, 0xFF, A.base_bytes, R.s));
+  if (P.own_scan) BCHK(hipMemsetAsync(A.scan_state.in(R.arena), 0, std::max(scan_pair27_state_bytes(n1), part_state_bytes(n1)), R.s));
+  hipLaunchKernelGGL(k_init, dim3(cdiv(R.M, 256)), dim3(256), 0, R.s, R.d_xyz, R.M, R.perm, R.seg_of, R.cx, R.cy, R.cz, R.small, R.lvl, R.segs);
+  unsigned char* const hst = (R.side && R.side->h_pin) ? static_cast<unsigned char*>(R.side->h_pin) : (R.h_pageable.resize(65536), R.h_pageable.data());
+  R.h_small = reinterpret_cast<uint32_t*>(hst);
+  R.hl = reinterpret_cast<BLevel*>(hst + 64);
+  static_assert(64 + sizeof(BLevel) * (BUILD_MAX_LEVELS + 2) <= 65536, "the staging block holds every level's counters");
+  std::memset(hst, 0, 64);
+  return hipSuccess;
+}
+
+// the exact left-to-right sums of a level's big nodes, piecewise, on `st`: of the level as it stands (in order, into the
+// level's measurements) or of a speculated level's snapshot (on a background stream, the split axes only)
+struct SumBufs {
+  const BSeg* segs; const uint32_t* seg_of; const double *x, *y, *z;
+  BPiece* pieces; BPre *prein, *preout; BSum *own, *comp; uint32_t* wlist; BMeas* out;
+  const uint32_t* only_axis;
+};
+static hipError_t enqueue_exact_sums(const BuildRun& R, hipStream_t st, void* scan_tmp, const SumBufs& B, const BLevel* lv, size_t bound)
+{
+  const uint32_t nblocks = R.nblocks, big_min = R.P.big_min;
+  const int big_dbg = R.P.big_dbg_all & (3 | 16);
+  const size_t nsl = (size_t)nblocks * 2 * 3, nsl1 = (size_t)nblocks * 2;
+  hipLaunchKernelGGL(k_big_stats, dim3(cdiv(nblocks, 256 / WAVE)), dim3(256), 0, st, B.segs, B.seg_of, B.x, B.y, B.z, R.M,
+                     nblocks, B.pieces, B.prein, big_min, B.only_axis);
+  size_t stb = R.P.A.scan_tmp;
+  BCHK(rocprim::inclusive_scan(scan_tmp, stb, B.prein, B.preout, nsl, BPreOp(), st));
+  hipLaunchKernelGGL(k_big_emulate, dim3(cdiv(nsl1, 64)), dim3(64), 0, st, B.segs, B.x, B.y, B.z, nblocks,
+                     B.pieces, B.preout, B.own, big_dbg, B.only_axis);
+  stb = R.P.A.scan_tmp;
+  BSum ident;   // exclusive: comp[slot] = everything since the last reset BEFORE the slot = the run in front of it
+  ident.T0 = ident.T1 = ident.mn0 = ident.mn1 = ident.mx0 = ident.mx1 = 0; ident.eb = BIG_ANY; ident.reset = 0u; ident.cnt = 0u; ident.pad = 0u;
+  BCHK(rocprim::exclusive_scan(scan_tmp, stb, B.own, B.comp, ident, nsl1, BSumOp(), st));
+  hipLaunchKernelGGL(k_big_list, dim3(cdiv(nsl1, 256)), dim3(256), 0, st, B.own, B.comp, (uint32_t)nsl1, B.wlist);
+  hipLaunchKernelGGL(k_big_stitch, dim3(cdiv(bound * 3 * WAVE, 256)), dim3(256), 0, st, B.segs, lv, B.x, B.y, B.z,
+                     nblocks, B.pieces, B.preout, B.own, B.comp, B.wlist, B.out, big_dbg, big_min, B.only_axis);
+  return hipSuccess;
+}
+
+// what enqueue_level's steps agree on about the level
+struct LevelShape {
+  size_t bound;            // an upper bound of the level's node count: per-node kernels are launched over it
+  const BLevel* lv;
+  bool big_level, measure_per_axis, spec_this, front_merged;
+  bool nodes_done = false; // the level's decisions and records are written already (k_nodes_small_approx)
+};
+
+// a speculated level: cut at the plain sums; its exact sums on a background stream, from a snapshot of the coordinates
+static hipError_t enqueue_speculated_sums(BuildRun& R, LevelShape& C)
+{
+  const BuildPlan& P = R.P;
+  const BuildSide* side = R.side;
+  char* arena = R.arena; hipStream_t s = R.s;
+  const uint32_t M = R.M, big_min = P.big_min;
+  const size_t n1 = (size_t)M + 1, bound = C.bound;
+  BSpecLevel& L = R.SP.L[R.SP.n];
+  const SpecRegions& o = P.A.spec[R.SP.n];
+  L.pieces = o.pieces.in(arena); L.preout = o.preout.in(arena); L.own = o.own.in(arena);
+  L.comp = o.comp.in(arena); L.wlist = o.wlist.in(arena); L.snap = o.snap.in(arena);
+  L.segs = o.segs.in(arena); L.axis = o.axis.in(arena); L.node = o.node.in(arena);
+  L.nleft = o.nleft.in(arena); L.cnt = o.cnt.in(arena); L.exact = o.exact.in(arena);
+  L.level = R.level; L.pad = 0;
+  R.SP.n++;
+  L.prein = o.prein.in(arena); L.seg_of = o.seg_of.in(arena);
+  BPart* part = P.A.part.in(arena);
+  double *sx = L.snap, *sy = L.snap + n1, *sz = L.snap + 2 * n1;
+  if (C.front_merged) {
+    const uint32_t nbp = cdiv(M, BIG_PB);
+    hipLaunchKernelGGL(k_level_front, dim3(nbp + cdiv(bound * 3 * WAVE, 256)), dim3(256), 0, s, R.segs, C.lv, R.seg_of, R.cx, R.cy, R.cz, M,
+                       part, L.snap, L.seg_of, (uint32_t)n1, nbp, R.meas, big_min);
+  } else {
+    hipLaunchKernelGGL(k_big_partials, dim3(cdiv(M, BIG_PB)), dim3(256), 0, s, R.segs, R.seg_of, R.cx, R.cy, R.cz, M, part, big_min);
+  }
+  if (P.merge && bound <= 16) {
+    // at most sixteen nodes: their plain sums, the decisions and the records in one workgroup
+    hipLaunchKernelGGL(k_nodes_small_approx, dim3(1), dim3(1024), 0, s, R.segs, R.lvl + R.level, (uint32_t)bound, R.meas, (uint32_t)R.bucket,
+                       R.kind, R.axis, R.splitval, R.nleft, R.irank, R.nodes, R.node_r, R.leaf_tab, R.small + SM_ROOT_REF, R.small + SM_MAX_LEAF, part, L, P.spec_fault, big_min);
+    C.nodes_done = true;
+  } else {
+    hipLaunchKernelGGL(k_big_approx, dim3(cdiv(bound * WAVE, 256)), dim3(256), 0, s, R.segs, C.lv, part, R.meas, L, P.spec_fault, big_min);
+  }
+  if (!C.front_merged) hipLaunchKernelGGL(k_spec_snapshot, dim3(cdiv(M, 256)), dim3(256), 0, s, R.seg_of, R.cx, R.cy, R.cz, M, (uint32_t)n1, L.snap, L.seg_of);
+  // the exact chain of this level, all of it, on the snapshot.  The chains of different levels do not depend on each
+  // other: the root's (1.3 ms of one wave) runs on one background stream, every other level's on the second -- in a
+  // single stream the levels' chains queue up behind the root's and together outlast the build
+  // (round 6: ... and the second stream was then the build's critical path at 1M points -- the chains of levels 1 and 2,
+  // 0.6 and 0.4 ms, and five more levels' 0.12 ms each in a row outlast levels + finisher by 0.8 ms: the levels below
+  // the root alternate between two streams)
+  const bool use3 = side->s3 && (R.SP.n - 1) != 0;
+  const bool use4 = use3 && side->s4 && ((R.SP.n - 1) & 1) == 0;
+  hipStream_t sb = use4 ? side->s4 : (use3 ? side->s3 : side->s2);
+  void* tmpb = use4 ? P.A.tmp4.in(arena) : (use3 ? P.A.tmp3.in(arena) : P.A.tmp2.in(arena));
+  BCHK(hipEventRecord(side->e1, s));
+  BCHK(hipStreamWaitEvent(sb, side->e1, 0));
+  // from the sixth level on (a balanced node's chain: M / 32 adds of 4.2 ns, a seventh of what the build takes) the
+  // exact sums are plain chains (TDTK_BUILD_CHAINFROM, lab: another level; 99: never)
+  if (R.level >= P.chain_from && R.chain_ok) {
+    hipLaunchKernelGGL(k_chain_exact, dim3(cdiv(bound * 3 * WAVE, 256)), dim3(256), 0, sb, L.segs, C.lv, sx, sy, sz, L.exact, L.axis, big_min);
+    return hipSuccess;
+  }
+  const SumBufs B = {L.segs, L.seg_of, sx, sy, sz, L.pieces, L.prein, L.preout, L.own, L.comp, L.wlist, L.exact, (const uint32_t*)L.axis};
+  return enqueue_exact_sums(R, sb, tmpb, B, C.lv, bound);
+}
+
+// the level's decisions and records from its measurements
+static hipError_t enqueue_decide(BuildRun& R, const LevelShape& C)
+{
+  hipStream_t s = R.s;
+  const size_t bound = C.bound;
+  size_t st = R.P.A.scan_tmp;
+  if (C.nodes_done) {}
+  else if (bound + 1 <= 1024) {
+    hipLaunchKernelGGL(k_nodes_small, dim3(1), dim3(1024), 0, s, R.segs, R.lvl + R.level, (uint32_t)bound, R.meas, (uint32_t)R.bucket,
+                       R.kind, R.axis, R.splitval, R.nleft, R.irank, R.nodes, R.node_r, R.leaf_tab, R.small + SM_ROOT_REF, R.small + SM_MAX_LEAF);
+  } else {
+    hipLaunchKernelGGL(k_decide, dim3(cdiv(bound + 1, 256)), dim3(256), 0, s, R.segs, C.lv, (uint32_t)bound, R.meas,
+                       (uint32_t)R.bucket, R.kind, R.axis, R.splitval, R.nleft);
+    BCHK(rocprim::exclusive_scan(R.tmp, st, R.kind, R.irank, 0u, bound + 1, rocprim::plus<uint32_t>(), s));
+    hipLaunchKernelGGL(k_emit, dim3(cdiv(bound, 256)), dim3(256), 0, s, R.segs, R.lvl + R.level, R.meas, R.kind, R.axis, R.splitval,
+                       R.irank, R.nodes, R.node_r, R.leaf_tab, R.small + SM_ROOT_REF, R.small + SM_MAX_LEAF);
+  }
+  return hipSuccess;
+}
+
+// the partition pass (with no internal node at this level it moves nothing): two passes over the points while the
+// one-launch scan's conditions hold (TDTK_BUILD_PART=0, lab: round 3's five)
+static hipError_t enqueue_partition(BuildRun& R, const LevelShape& C)
+{
+  const BuildPlan& P = R.P;
+  hipStream_t s = R.s;
+  const uint32_t M = R.M, level = R.level;
+  const size_t n1 = (size_t)M + 1, bound = C.bound;
+  char* const scan_state = P.A.scan_state.in(R.arena);
+  uint32_t* const err = R.small + SM_ERR;
+  if (P.part2 && level < 255u) {
+    const uint32_t ntiles = cdiv(M, PS_TILE), nbw = cdiv(M, 256u * PW_ROWS);
+    uint32_t* counter = reinterpret_cast<uint32_t*>(scan_state);
+    unsigned long long* status = reinterpret_cast<unsigned long long*>(scan_state + 64);
+    hipLaunchKernelGGL(k_part_scan, dim3(ntiles), dim3(PS_THREADS), 0, s, R.seg_of, R.kind, R.segs, R.axis, R.splitval, R.cx, R.cy, R.cz, M, R.nleft, R.posL,
+                       status, counter, level + 1u, ntiles, err);
+    if (C.spec_this)
+      hipLaunchKernelGGL(k_part_swap_keep, dim3(nbw + cdiv(bound, 256)), dim3(256), 0, s, R.posL, R.segs, R.kind, R.irank, R.nleft, M, R.seg_of,
+                         R.perm, R.cx, R.cy, R.cz, nbw, C.lv, R.next, err, R.SP.L[R.SP.n - 1]);
+    else
+      hipLaunchKernelGGL(k_part_swap, dim3(nbw + cdiv(bound, 256)), dim3(256), 0, s, R.posL, R.segs, R.kind, R.irank, R.nleft, M, R.seg_of,
+                         R.perm, R.cx, R.cy, R.cz, nbw, C.lv, R.next, err);
+    return hipSuccess;
+  }
+  hipLaunchKernelGGL(k_count, dim3(cdiv(M, 256 * CNT_ITERS)), dim3(256), 0, s, R.seg_of, R.kind, R.axis, R.splitval, R.cx, R.cy,
+                     R.cz, M, R.nleft);
+  {
+    const uint32_t nbm = cdiv(n1, 256);
+    if (C.spec_this)
+      hipLaunchKernelGGL(k_misplaced_children_keep, dim3(nbm + cdiv(bound, 256)), dim3(256), 0, s, R.seg_of, R.kind, R.segs, R.axis,
+                         R.splitval, R.nleft, R.cx, R.cy, R.cz, M, R.LR, nbm, C.lv, R.irank, R.next, err, R.SP.L[R.SP.n - 1]);
+    else
+      hipLaunchKernelGGL(k_misplaced_children, dim3(nbm + cdiv(bound, 256)), dim3(256), 0, s, R.seg_of, R.kind, R.segs, R.axis,
+                         R.splitval, R.nleft, R.cx, R.cy, R.cz, M, R.LR, nbm, C.lv, R.irank, R.next, err);
+  }
+  if (P.own_scan && level < 255u) {
+    BCHK(launch_scan_pair27(R.LR, R.AB, n1, scan_state, level + 1u, err, s));    // one launch (sort.hip)
+  } else {
+    size_t st = P.A.scan_tmp;
+    BCHK(rocprim::exclusive_scan(R.tmp, st, R.LR, R.AB, 0ull, n1, rocprim::plus<unsigned long long>(), s));
+  }
+  hipLaunchKernelGGL(k_swaplist, dim3(cdiv(M, 256)), dim3(256), 0, s, R.seg_of, R.segs, R.LR, R.AB, M, R.posL, R.posR);
+  {
+    const uint32_t nbs = cdiv((size_t)M / 2 + 1, 256);
+    hipLaunchKernelGGL(k_swap_relabel, dim3(nbs + cdiv(M, 256)), dim3(256), 0, s, R.posL, R.posR, R.AB + M, R.perm, R.cx, R.cy, R.cz, nbs,
+                       R.segs, R.kind, R.irank, R.nleft, M, R.seg_of);
+  }
+  return hipSuccess;
+}
+
+// one level: measure its nodes, decide and write their records, partition the points
+static hipError_t enqueue_level(BuildRun& R)
+{
+  const BuildPlan& P = R.P;
+  hipStream_t s = R.s;
+  const uint32_t M = R.M, level = R.level, big_min = P.big_min;
+  LevelShape C;
+  size_t bound = (size_t)R.known << ((level - R.known_at) < 31 ? (level - R.known_at) : 31);
+  if (bound > M) bound = M;
+  // the nodes of a level are the children of the level above's internal nodes: disjoint runs of more than
+  // `bucket` points each, two children per run (at 1M points and buckets of 20 the doubling bound reaches the
+  // point count at level 16, sixty times the nodes there are)
+  const size_t cap = 2 * (R.M_ / ((size_t)(R.bucket > 0 ? R.bucket : 0) + 1));
+  if (level > 0 && bound > cap) bound = cap;
+  if (bound < 1) bound = 1;
+  C.bound = bound;
+  C.lv = R.lvl + level;
+  trace_level_start(R);
+  // the piecewise path runs while a balanced node is at least half its threshold (below that level the chain in
+  // k_measure takes every node, whatever its size: an empty pass of the piecewise kernels costs 75 us)
+  C.big_level = P.use_big && ((R.M_ >> level) >= P.big_level_min);
+  // a wave per node while the nodes of a balanced tree hold at most 128 points (three chains in one wave issue 24
+  // cycles per point where three waves need 10: level 7 of a 1M-point tree 253 us against 46, level 12 equal,
+  // level 16 74 against 139)
+  C.measure_per_axis = P.measure_per_axis_always || (R.M_ >> level) > 128;
+  C.spec_this = C.big_level && P.spec && R.SP.n < P.spec_levels && R.SP.n < BIG_SPEC_MAX;
+  // a speculated level's chains of small nodes ride in the launch of its partial sums (k_level_front)
+  C.front_merged = C.spec_this && C.measure_per_axis && P.merge;
+  if (C.front_merged) {}
+  else if (C.measure_per_axis)
+    hipLaunchKernelGGL(k_measure, dim3(cdiv(bound * 3 * WAVE, 256)), dim3(256), 0, s, R.segs, C.lv, R.cx, R.cy, R.cz, R.meas,
+                       C.big_level ? big_min : 0xFFFFFFFFu);
+  else
+    hipLaunchKernelGGL(k_measure_node, dim3(cdiv(bound * WAVE, 256)), dim3(256), 0, s, R.segs, C.lv, R.cx, R.cy, R.cz, R.meas,
+                       C.big_level ? big_min : 0xFFFFFFFFu);
+  if (C.spec_this) {
+    BCHK(enqueue_speculated_sums(R, C));
+  } else if (C.big_level) {
+    const BuildArena& A = P.A;
+    char* arena = R.arena;
+    const SumBufs B = {R.segs, R.seg_of, R.cx, R.cy, R.cz, A.pieces.in(arena), A.prein.in(arena), A.preout.in(arena),
+                       A.own.in(arena), A.comp.in(arena), A.wlist.in(arena), R.meas, nullptr};
+    BCHK(enqueue_exact_sums(R, s, R.tmp, B, C.lv, bound));
+    if (P.big_dbg_all & 8) {
+      BMeas* meas2 = A.dbg_meas.in(arena);
+      hipLaunchKernelGGL(k_measure, dim3(cdiv(bound * 3 * WAVE, 256)), dim3(256), 0, s, R.segs, C.lv, R.cx, R.cy, R.cz, meas2, 0xFFFFFFFFu);
+      hipLaunchKernelGGL(k_big_dbg_compare, dim3(cdiv(bound, 256)), dim3(256), 0, s, R.segs, C.lv, R.meas, meas2, level, big_min);
+    }
+  }
+  BCHK(enqueue_decide(R, C));
+  BCHK(enqueue_partition(R, C));
+  BSeg* t = R.segs; R.segs = R.next; R.next = t;
+  return hipSuccess;
+}
+
+// the exact sums have to be there now: the build's stream waits for the background streams, every big node's cut is
+// checked against them and its record given the exact value
+static hipError_t check_speculation(BuildRun& R)
+{
+  const BuildSide* side = R.side;
+  hipStream_t s = R.s;
+  BCHK(hipEventRecord(side->e2, side->s2));
+  BCHK(hipStreamWaitEvent(s, side->e2, 0));
+  if (side->s3) { BCHK(hipEventRecord(side->e3, side->s3)); BCHK(hipStreamWaitEvent(s, side->e3, 0)); }
+  if (side->s4) { BCHK(hipEventRecord(side->e4, side->s4)); BCHK(hipStreamWaitEvent(s, side->e4, 0)); }
+  hipLaunchKernelGGL(k_spec_count, dim3(cdiv(R.M, 1024)), dim3(256), 0, s, R.SP, R.lvl, R.cx, R.cy, R.cz, R.M);
+  hipLaunchKernelGGL(k_spec_patch, dim3(4), dim3(256), 0, s, R.SP, R.lvl, R.nodes, R.small + SM_SPEC_ERR);
+  return hipSuccess;
+}
+
+// At the hand-over level: does the level's largest node fit a workgroup's LDS?  (An unbalanced cloud -- a real scan --
+// takes a level or two more.)  Moves fin_level on, or gives the finishers up, when it does not.
+static hipError_t size_up_hand_over(BuildRun& R)
+{
+  const uint32_t fin_cap = R.P.fin_cap;
+  if (!R.have_max) {
+    hipLaunchKernelGGL(k_fin_maxn, dim3(1), dim3(256), 0, R.s, R.segs, R.lvl + R.level, R.small + SM_FIN_MAXN);
+    BCHK(hipMemcpyAsync(R.h_small, R.small, 4 * SM_LOOK_WORDS, hipMemcpyDeviceToHost, R.s));
+    BCHK(hipStreamSynchronize(R.s));
+  }
+  R.have_max = false;
+  const uint32_t h_max[2] = {R.h_small[SM_FIN_MAXN], R.h_small[SM_FIN_NODES]};
+  R.fin_nodes = h_max[1]; R.fin_maxn = h_max[0];
+  if (h_max[0] > FIN_LDS && h_max[1] * 2u <= fin_cap && R.fin_level + 1u < 31u) {
+    R.fin_level++;              // one more level by its own launches, then look again
+    R.known = h_max[1]; R.known_at = R.level;
+    R.batch = 1;
+  } else if (h_max[0] > FIN_LDS || h_max[1] > fin_cap) {
+    // too many nodes for the tables, or a node too large with no room for a wider level: on by levels -- and a look at
+    // every batch's end whether the level has thinned out (round 6: a cloud with a third of its points in one tight
+    // cluster is in that state for nine levels, until the sparse rest has ended in buckets; it used to stay by levels
+    // to the last bucket, eight levels more)
+    R.fin_level = 0xFFFFFFFFu;
+    R.fin_retry = R.no_finish == 0;
+    R.known = h_max[1]; R.known_at = R.level;
+    R.batch = 2;
+  }
+  return hipSuccess;
+}
+
+// the finishers over the `tmax` subtrees rooted at the hand-over level, by size
+static void enqueue_finishers(BuildRun& R, uint32_t tmax, BSeg* roots, FinTab* ftab)
+{
+  const BuildPlan& P = R.P;
+  const BuildArena& A = P.A;
+  char* arena = R.arena; hipStream_t s = R.s;
+  FinArgs fa;
+  fa.roots = roots; fa.lvH = R.lvl + R.fin_level; fa.cx = R.cx; fa.cy = R.cy; fa.cz = R.cz; fa.perm = R.perm;
+  fa.segA = A.segA.in(arena); fa.segB = A.segB.in(arena); fa.meas = R.meas;
+  fa.kind = A.fin_kind.in(arena); fa.axis = R.axis; fa.splitval = R.splitval; fa.irank = A.fin_irank.in(arena); fa.nleft = R.nleft;
+  fa.nodes_st = A.fin_nodes.in(arena); fa.r_st = A.fin_r.in(arena); fa.leaf_st = A.fin_leaf.in(arena);
+  fa.tab = ftab; fa.bucket = (uint32_t)R.bucket; fa.small = R.small;
+  fa.sub_nlev = A.fin_nlev.in(arena); fa.sub_maxleaf = A.fin_maxleaf.in(arena);
+  fa.n_lo = 0u; fa.skip_big = 1u;
+  fa.dbg_levels = P.fw_debug;
+  // (by size only when the level has more subtrees than the chip has room for at once: below that the launches would
+  //  run one after the other where one launch runs them side by side -- the dat/ scan 0.97 -> 1.13 ms)
+  const bool staged = tmax > 1024u;
+  if (P.fin_wave && staged) { hipLaunchKernelGGL(k_fin_wave, dim3(cdiv(tmax, FW_WAVES)), dim3(WAVE * FW_WAVES), 0, s, fa); fa.n_lo = FW_CAP; }
+  if (P.fin_half && staged && R.fin_maxn > fa.n_lo) { hipLaunchKernelGGL(k_fin_subtrees_half, dim3(tmax), dim3(FIN_T), 0, s, fa); fa.n_lo = FIN_LDS_HALF; }
+  fa.skip_big = 0u;
+  if (R.fin_maxn > fa.n_lo) hipLaunchKernelGGL(k_fin_subtrees, dim3(tmax), dim3(FIN_T), 0, s, fa);
+}
+
+// Hand the level over: its nodes become the roots of subtrees.  As many workgroups as the level HAS nodes (counted by
+// size_up_hand_over; the tables hold FIN_MAX_SUBTREES): 2^level of them -- right for a balanced tree -- is a million by the
+// time a lopsided cloud (one dense cluster that stays above FIN_LDS for sixteen levels) is handed over, and the
+// copy of that many root records ran over the arena (found by tools/fuzz_parity.py --seed 4401, round 4).
+static hipError_t hand_over(BuildRun& R)
+{
+  const BuildPlan& P = R.P;
+  const BuildArena& A = P.A;
+  char* arena = R.arena; hipStream_t s = R.s;
+  uint32_t* const small = R.small;
+  BLevel* lvH = R.lvl + R.fin_level;
+  const uint32_t tmax = R.fin_nodes ? R.fin_nodes : 1u;
+  BSeg* roots = A.fin_roots.in(arena);
+  FinTab* ftab = A.fin_tab.in(arena);
+  FinOff* foff = A.fin_off.in(arena);
+  BCHK(hipMemcpyAsync(roots, R.segs, sizeof(BSeg) * tmax, hipMemcpyDeviceToDevice, s));
+  if (P.fin_trace) { const uint32_t magic = 0x7157u; BCHK(hipMemcpyAsync(small + SM_FIN_TRACE, &magic, 4, hipMemcpyHostToDevice, s)); }
+  trace_level_start(R);
+  enqueue_finishers(R, tmax, roots, ftab);
+  uint32_t* ftot = A.fin_tot.in(arena);
+  hipLaunchKernelGGL(k_fin_offsets, dim3(FIN_LV + 1u), dim3(FO_T), 0, s, ftab, foff, lvH, ftot, (const uint32_t*)A.fin_nlev.in(arena),
+                     (const uint32_t*)A.fin_maxleaf.in(arena), small + SM_MAX_LEAF);
+  hipLaunchKernelGGL(k_fin_place, dim3(tmax), dim3(256), 0, s, ftab, foff, ftot, roots, lvH, (const KdNode*)A.fin_nodes.in(arena),
+                     (const double*)A.fin_r.in(arena), (const LeafEntry*)A.fin_leaf.in(arena), R.nodes, R.node_r, R.leaf_tab, small + SM_ROOT_REF);
+  R.level = R.fin_level + FIN_LV + 2u;
+  // what follows the levels does not wait for the host's look: the check of the speculated cuts and the point array
+  // are enqueued now, their results come back with the level counters
+  // (the point array first: it does not need the exact sums, and at a million points the build is waiting for the root's)
+  hipLaunchKernelGGL(k_points, dim3(cdiv(R.M, 256)), dim3(256), 0, s, R.perm, R.cx, R.cy, R.cz, R.M, R.pts);
+  if (R.spec && R.SP.n) BCHK(check_speculation(R));
+  R.tail_enqueued = true;
+  BCHK(hipMemcpyAsync(R.hl, R.lvl, sizeof(BLevel) * (R.level + 1), hipMemcpyDeviceToHost, s));
+  BCHK(hipMemcpyAsync(R.h_small, small, 4 * SM_LOOK_WORDS, hipMemcpyDeviceToHost, s));
+  BCHK(hipStreamSynchronize(s));
+  if (R.spec && R.SP.n) R.h_spec_err = R.h_small[SM_SPEC_ERR];
+  if (P.fin_trace) trace_finisher_print(R);
+  if (R.h_small[SM_ERR] & ERR_DEEP_SUBTREE) { R.redo_by_levels = true; return hipSuccess; }   // level by level, then (device_build_tree)
+  if (R.h_small[SM_ERR]) {
+    R.res.degenerate = true;
+    R.spec_suspect = true;
+    return hipErrorInvalidValue;
+  }
+  return hipSuccess;
+}
+
+// One look per batch: the level counters so far and the root reference / largest bucket / error word together -- and,
+// when the next level is the one handed to the finisher, its largest node.  Decides how the loop goes on.
+static hipError_t look(BuildRun& R, bool* done)
+{
+  const BuildPlan& P = R.P;
+  hipStream_t s = R.s;
+  const uint32_t level = R.level;
+  if (level == R.fin_level || R.fin_retry) { hipLaunchKernelGGL(k_fin_maxn, dim3(1), dim3(256), 0, s, R.segs, R.lvl + level, R.small + SM_FIN_MAXN); R.have_max = true; }
+  else if (R.chain_look) hipLaunchKernelGGL(k_fin_maxn, dim3(1), dim3(256), 0, s, R.segs, R.lvl + level, R.small + SM_FIN_MAXN);
+  BCHK(hipMemcpyAsync(R.hl, R.lvl, sizeof(BLevel) * (level + 1), hipMemcpyDeviceToHost, s));
+  BCHK(hipMemcpyAsync(R.h_small, R.small, 4 * SM_LOOK_WORDS, hipMemcpyDeviceToHost, s));
+  BCHK(hipStreamSynchronize(s));
+  const uint32_t* h_small = R.h_small;
+  const BLevel nx = R.hl[level];
+  if (h_small[SM_ERR] || (nx.nseg && level >= BUILD_MAX_LEVELS)) {
+    // an empty child / non-finite coordinates -- or, on a speculated level, a cut so far off the exact one that a
+    // child came out empty: only then is the in-order build asked what the input really is
+    if (h_small[SM_ERR] & ERR_SCAN_TIMEOUT) return hipErrorLaunchTimeOut;
+    R.res.degenerate = true;
+    R.spec_suspect = true;
+    return hipErrorInvalidValue;
+  }
+  if (nx.nseg == 0) { *done = true; return hipSuccess; }
+  R.known = nx.nseg; R.known_at = level;
+  R.batch = 2;
+  if (R.chain_look) {
+    R.chain_ok = h_small[SM_FIN_MAXN] <= R.M_ / 17u;
+    if (R.chain_ok || level >= (uint32_t)P.spec_levels || level >= R.fin_level) R.chain_look = false;
+    R.batch = R.chain_look ? 1u : ((R.fin_level != 0xFFFFFFFFu && level < R.fin_level) ? R.fin_level - level : 2u);
+  }
+  if (R.fin_retry) {
+    if (h_small[SM_FIN_MAXN] <= FIN_LDS && h_small[SM_FIN_NODES] <= P.fin_cap && level + FIN_LV + 3u < BUILD_MAX_LEVELS) { R.fin_level = level; R.fin_retry = false; }   // hand over now (run_levels)
+    else R.have_max = false;
+  }
+  return hipSuccess;
+}
+
+// Levels are enqueued in batches; how many nodes a level has, and where its node / bucket records start, is
+// known on the device only (lvl[]).  The host looks once after a first batch as deep as a balanced tree gets
+// down to bucket-sized nodes, then every two levels; per-node kernels are launched over an upper bound of the
+// level's node count (what the last look saw, doubled per level since) and return past the real count.
+static hipError_t run_levels(BuildRun& R)
+{
+  for (;;) {
+    if (R.level == R.fin_level) BCHK(size_up_hand_over(R));
+    if (R.level == R.fin_level) return hand_over(R);
+    for (uint32_t b = 0; b < R.batch && R.level < BUILD_MAX_LEVELS; b++, R.level++) BCHK(enqueue_level(R));
+    bool done = false;
+    BCHK(look(R, &done));
+    if (done) return hipSuccess;
+  }
+}
+
+// the records move out of the scratch into allocations of their exact size
+static hipError_t copy_out_records(BuildRun& R)
+{
+  hipStream_t s = R.s;
+  const size_t node_count = R.node_count, leaf_count = R.leaf_count;
+  if (node_count) {
+    BCHK((hipError_t)pool_malloc_raw((void**)&R.f_nodes, sizeof(KdNode) * node_count));
+    BCHK((hipError_t)pool_malloc_raw((void**)&R.f_r, sizeof(double) * node_count));
+    BCHK(hipMemcpyAsync(R.f_nodes, R.nodes, sizeof(KdNode) * node_count, hipMemcpyDeviceToDevice, s));
+    BCHK(hipMemcpyAsync(R.f_r, R.node_r, sizeof(double) * node_count, hipMemcpyDeviceToDevice, s));
+  }
+  if (R.res.table_mode) {
+    BCHK((hipError_t)pool_malloc_raw((void**)&R.f_leaf, sizeof(LeafEntry) * leaf_count));
+    BCHK(hipMemcpyAsync(R.f_leaf, R.leaf_tab, sizeof(LeafEntry) * leaf_count, hipMemcpyDeviceToDevice, s));
+  }
+  return hipSuccess;
+}
+
+// behind the levels: the tree's totals, what the finishers' path has not enqueued yet, the records' way out
+static hipError_t finish_tree(BuildRun& R)
+{
+  hipStream_t s = R.s;
+  DevBuildResult& res = R.res;
+  const uint32_t M = R.M;
+  trace_levels_print(R);
+  // the first level without nodes: its counters are the totals, its index the depth of the tree
+  R.depth = 0;
+  while (R.depth < R.level && R.hl[R.depth].nseg) R.depth++;
+  R.node_count = R.hl[R.depth].node_base; R.leaf_count = R.hl[R.depth].leaf_base;
+  res.max_leaf = R.h_small[SM_MAX_LEAF];
+  res.cb = bits_for(res.max_leaf);
+  res.table_mode = (bits_for(M) + res.cb) > 30;
+  if (R.spec && R.SP.n && !R.tail_enqueued) {
+    BCHK(check_speculation(R));
+    BCHK(hipMemcpyAsync(&R.h_spec_err, R.small + SM_SPEC_ERR, 4, hipMemcpyDeviceToHost, s));
+  }
+  if (!R.tail_enqueued) hipLaunchKernelGGL(k_points, dim3(cdiv(M, 256)), dim3(256), 0, s, R.perm, R.cx, R.cy, R.cz, M, R.pts);
+  if (!res.table_mode)
+    hipLaunchKernelGGL(k_pack_refs, dim3(cdiv(R.node_count ? R.node_count : 1, 256)), dim3(256), 0, s, R.nodes, R.node_count,
+                       R.leaf_tab, (uint32_t)res.cb, R.small + SM_ROOT_REF);
+  // (the finisher's path has looked at everything already -- the check word, and a root that is a node keeps its reference
+  // through k_pack_refs: what is enqueued from here on is waited for by the caller's own synchronisation, tree_finish)
+  const bool no_last_look = R.tail_enqueued && !res.table_mode && !(R.h_small[SM_ROOT_REF] & REF_LEAF);
+  if (no_last_look) res.root_ref = R.h_small[SM_ROOT_REF];
+  else BCHK(hipMemcpyAsync(&res.root_ref, R.small + SM_ROOT_REF, 4, hipMemcpyDeviceToHost, s));
+  BCHK(copy_out_records(R));
+  if (!no_last_look) BCHK(hipStreamSynchronize(s));
+  BCHK(hipGetLastError());
+  if (R.P.spec_dump) spec_dump(R);
+  if (R.h_spec_err) { R.spec_suspect = true; return hipErrorNotReady; }     // a cut the exact sum would have made elsewhere: in order, then
+  return hipSuccess;
+}
+
+// lab: the guards behind the arena's regions must be as build_setup left them
+static hipError_t check_guards(BuildRun& R)
+{
+  const GuardList& G = R.P.A.guards;
+  if (!G.n) return hipSuccess;
+  if (R.spec) wait_side_streams(R.side);
+  const uint32_t bad = arena_guards_check(R.arena, G, R.small + SM_GUARD_BAD, R.s);
+  if (!bad) return hipSuccess;
+  fprintf(stderr, "tree build: arena guard %u of %u overwritten (M = %u): a region was written past its end\n", bad - 1u, G.n, R.M);
+  return hipErrorAssert;
+}
+
+// Builds on `s` inside the caller's scratch `arena_` (>= device_build_arena_bytes(M), reused from build to build:
+// no hipMalloc / hipFree of hundreds of MB per tree, and no device-wide sync from hipFree while another thread's
+// kernels run).  On success the caller owns res.{nodes,node_r,pts,leaf_tab}, from the handle pool (pool.cpp) at their sizes.
+DevBuildResult device_build_tree(const double* d_xyz, size_t M_, int bucket, void* arena_, hipStream_t s, const BuildSide* side,
+                                 int no_finish)
+{
+  const BuildPlan P = make_build_plan(M_, bucket, side && side->s2, no_finish);
+  BuildRun R(P, d_xyz, M_, bucket, arena_, s, side, no_finish);
+  hipError_t err = build_setup(R);
+  if (err == hipSuccess) err = run_levels(R);
+  if (err == hipSuccess && !R.redo_by_levels) err = finish_tree(R);
+  if (err == hipSuccess && !R.redo_by_levels) err = check_guards(R);
+  if (err == hipSuccess && !R.redo_by_levels) {
+    DevBuildResult& res = R.res;
+    res.nodes = R.f_nodes; res.node_r = R.f_r; res.leaf_tab = R.f_leaf; res.pts = R.pts;
+    res.n_internal = R.node_count; res.n_leaves = R.leaf_count; res.max_depth = R.depth;
+    return res;
+  }
+  // every other way out: nothing of this build may still be running in the arena, and nothing of it is kept
+  if (R.spec) wait_side_streams(side);
+  if (R.f_nodes) pool_free(R.f_nodes);
+  if (R.f_r) pool_free(R.f_r);
+  if (R.f_leaf) pool_free(R.f_leaf);
+  if (R.pts) pool_free(R.pts);
+  for (hipEvent_t x : R.lvl_ev) (void)hipEventDestroy(x);
+  if (R.redo_by_levels) return device_build_tree(d_xyz, M_, bucket, arena_, s, side, 1);   // a subtree deeper than the tables
+  if (R.spec && R.spec_suspect) {
+    // a failed check, or a degenerate split on a tree cut at the plain sums: the in-order build decides what the input
+    // really is.  (Anything else -- no memory, a failed launch -- is returned as it is: building twice would not help.)
+    (void)hipStreamSynchronize(s);
+    (void)hipGetLastError();
+    DevBuildResult again = device_build_tree(d_xyz, M_, bucket, arena_, s, nullptr, no_finish);
+    again.respeculated = again.err == hipSuccess;     // tdtk_build_respeculated counts cuts that really were off, not bad inputs
+    return again;
+  }
+  R.res.err = err;
+  return R.res;
 }
 
 }  // namespace tdtk
