@@ -286,6 +286,9 @@ static int icp_match_impl(const tdtk_tree* model, const double model_dalignxf[16
   }
   bool loop_done = false, resume_with_acc = false;
   double acc[ACC_TOTAL], shift[3];
+  // certificates live from one pass of THIS loop to the next (scan_pass); TDTK_CERT_SKIP=0: none (read per match, tests flip it)
+  c->cert_live = false;
+  const bool cert_ok = [] { const char* e = getenv("TDTK_CERT_SKIP"); return !(e && e[0] == '0'); }();
 #ifdef TDTK_LAB
   // lab: the small-scan loop that runs without the host (see icp_device_loop): -a 1, closest points, every point a candidate
   if (icp_loop_ahead() > 0 && algo == TDTK_ALGO_QUAT && pmode == 0 && want == 0u && rnd <= 1 && !hashing && !c->counting &&
@@ -317,7 +320,8 @@ static int icp_match_impl(const tdtk_tree* model, const double model_dalignxf[16
     // the others a point of THIS tree, whose distance bounds the nearest neighbour's however the scan has moved since)
     if (!resume_with_acc) {
       rc = scan_pass(c, model, model_dalignxf, data, pmode, prm->max_dist_match2, want, nullptr,
-                     have_pending ? pend : nullptr, true, acc, shift, iter > 0 && warm_ok, skip);
+                     have_pending ? pend : nullptr, true, acc, shift, iter > 0 && warm_ok, skip,
+                     cert_ok && iter > 0 && rnd <= 1);
       if (rc) return rc;
       have_pending = false;
     }

@@ -59,7 +59,7 @@ struct DevBuf {
 };
 
 enum { WS_KPOS, WS_D2, WS_PART, WS_OUT, WS_OVF_M2, WS_OVF_REF, WS_IDX, WS_QX, WS_QY, WS_QZ, WS_DX,
-       WS_DY, WS_DZ, WS_ORDER, WS_CELL, WS_HIST, WS_TMPA, WS_TMPB, WS_CNT, WS_BOX, WS_ARENA, WS_COST, WS_MOVES, WS_BOUNDS, WS_COUNT };
+       WS_DY, WS_DZ, WS_ORDER, WS_CELL, WS_HIST, WS_TMPA, WS_TMPB, WS_CNT, WS_BOX, WS_ARENA, WS_COST, WS_MOVES, WS_BOUNDS, WS_CERT, WS_COUNT };
 
 // an auxiliary stream with the buffers one whole-scan pass needs: batches of links over small scans run several
 // passes side by side (one pass of an 80K-point scan occupies a fraction of the machine and is latency-bound)
@@ -150,6 +150,9 @@ struct Ctx {
   // slabs of equal cost for the next pass of an ICP loop (launch_slab_bounds): valid for the loop's next scan_pass only
   const uint32_t* next_bounds = nullptr;
   size_t next_bounds_n = 0;
+  // WS_CERT holds the certificates (SearchArgs::cert) the last scan_pass of the running tdtk_icp_match loop wrote for exactly
+  // the queries and the tree of its next pass: set by a pass that wrote them, cleared by every other pass and where a loop starts
+  bool cert_live = false;
   // a context dies with its host thread (worker threads of a prefetch pool come and go): give everything back
   ~Ctx();
 };
@@ -205,7 +208,7 @@ double search_margin(const tdtk_tree* t, double maxd2);
 void pass_shift(const tdtk_tree* t, const double* A16, double out[3]);
 int scan_pass(Ctx* c, const tdtk_tree* model, const double* A16, tdtk_scan* data, int pmode, double maxd2,
               unsigned want, const double* lum_D, const double* pending, bool do_search, double* acc_out,
-              double shift_out[3], bool warm = false, const unsigned char* skip = nullptr);
+              double shift_out[3], bool warm = false, const unsigned char* skip = nullptr, bool cert_ok = false);
 int scan_idx_to_host(Ctx* c, const tdtk_tree* model, tdtk_scan* data, int32_t* idx_out);
 // api_scan.cpp
 int queue_scan_moves(Ctx* c, const std::vector<tdtk_scan*>& moved);

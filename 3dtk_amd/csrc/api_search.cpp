@@ -326,6 +326,24 @@ static double search_tie(const tdtk_tree* t, double maxd2)
   return search_margin(t, maxd2);
 }
 
+// The margin of a walk that leaves a certificate: m = clamp(kappa * move, lo * d, hi * d) (SearchArgs::cert_*; DESIGN section 4
+// has the table the values were chosen from).  Any m >= 0 is exact; TDTK_CERT_KAPPA / _LO / _HI, read once per process, exist
+// for repeating that table.
+static void cert_policy(float* kappa, float* lo, float* hi)
+{
+  struct Policy { float kappa, lo, hi; };
+  static const Policy pol = [] {
+    auto env = [](const char* name, float dflt) {
+      const char* e = getenv(name);
+      if (!e || !e[0]) return dflt;
+      const float v = (float)atof(e);
+      return (v >= 0.f && v <= 1024.f) ? v : dflt;
+    };
+    return Policy{env("TDTK_CERT_KAPPA", 4.0f), env("TDTK_CERT_LO", 1.0f / 64.0f), env("TDTK_CERT_HI", 0.25f)};
+  }();
+  *kappa = pol.kappa; *lo = pol.lo; *hi = pol.hi;
+}
+
 // the accumulation point of a pass: the tree's box centre moved by A
 void pass_shift(const tdtk_tree* t, const double* A16, double out[3])
 {
@@ -334,7 +352,7 @@ void pass_shift(const tdtk_tree* t, const double* A16, double out[3])
 
 int scan_pass(Ctx* c, const tdtk_tree* model, const double* A16, tdtk_scan* data, int pmode, double maxd2,
               unsigned want, const double* lum_D, const double* pending, bool do_search, double* acc_out,
-              double shift_out[3], bool warm, const unsigned char* skip)
+              double shift_out[3], bool warm, const unsigned char* skip, bool cert_ok)
 {
   hipStream_t s = c->stream;
   const size_t N = data->N;
@@ -406,6 +424,21 @@ int scan_pass(Ctx* c, const tdtk_tree* model, const double* A16, tdtk_scan* data
       for (int k = 0; k < 3; k++) sa.shift[k] = sh[k];
       sa.partials = c->ws[WS_PART].as<double>();
     }
+    // Certificates (kernels.hip, "a certificate per query"): only between consecutive passes of one tdtk_icp_match loop (cert_ok:
+    // the loop says so; TDTK_CERT_SKIP=0: never) that both run the instantiation that keeps them.  The first such pass ignores what
+    // the array holds and writes it, the following ones use it; any other pass of this context ends the chain.
+    bool certs = false;
+    if (cert_ok && fused && pmode == 0 && !skip) {
+      sa.T = model->dev;
+      certs = search_cert_capable(sa);
+    }
+    if (certs) {
+      if ((rc = c->ws[WS_CERT].ensure(N * sizeof(float)))) return rc;
+      sa.cert = c->ws[WS_CERT].as<float>();
+      sa.cert_use = c->cert_live ? 1 : 0;
+      cert_policy(&sa.cert_kappa, &sa.cert_lo, &sa.cert_hi);
+    }
+    c->cert_live = certs;
     rc = run_search(c, model, sa, pmode == 1 ? 1 : 0, false, s, true);
     if (rc) return rc;
     if (fused) {
@@ -695,6 +728,23 @@ int tdtk_visit_counters(int device, uint64_t out[8])
   for (int k = 0; k < 3; k++) out[k] = h[k];
   out[4] = h[4]; out[5] = h[5];
   out[7] = h[7];
+  return TDTK_OK;
+}
+
+// the instrumented persistent-lane launches since tdtk_visit_counting(device, on): queries answered by their certificate with
+// the hit kept (out[0]) and without a hit (out[1]), queries handed to a lane (out[2]), second searches behind a slab (out[3])
+int tdtk_skip_counters(int device, uint64_t out[4])
+{
+  if (!out) { set_error("NULL argument"); return TDTK_EINVAL; }
+  Ctx* c;
+  int rc = get_ctx(device, &c);
+  if (rc) return rc;
+  for (int k = 0; k < 4; k++) out[k] = 0;
+  if (!c->d_counters.p) return TDTK_OK;
+  HIPCHK(hipDeviceSynchronize());
+  unsigned long long h[16];
+  HIPCHK(hipMemcpy(h, c->d_counters.p, sizeof h, hipMemcpyDeviceToHost));
+  out[0] = h[10]; out[1] = h[11]; out[2] = h[12]; out[3] = h[7];
   return TDTK_OK;
 }
 

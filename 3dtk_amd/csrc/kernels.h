@@ -120,6 +120,15 @@ struct SearchArgs {
   // -R (rnd > 1, searchTree.cc:118): one byte per query in sorted order, non-zero = "not drawn this pass": the point still moves
   // (has_pending) but is no candidate -- kpos = -1, no search.  nullptr: every query is a candidate.
   const unsigned char* skip;
+  // Certificates (kernels.hip, "a certificate per query"; the persistent-lane single pass that defers the quick check and adds up
+  // its own sums only): one float per query in sorted order.  Non-null: every wave first sweeps its slab -- applies `pending`
+  // there --, every walk prunes against a FIXED radius (previous hit's distance + a margin m) and leaves behind a lower bound L
+  // on the distance from the query to every tree point but its hit.  cert_use != 0: the array holds the L of the previous pass of
+  // the same loop, and a query whose hit provably stays nearest (or which provably stays without one) is not walked at all.
+  // m = clamp(cert_kappa * move, cert_lo * d, cert_hi * d), d the distance the walk starts from.  nullptr: none of it.
+  float* cert;
+  int cert_use;
+  float cert_kappa, cert_lo, cert_hi;
 #ifdef TDTK_LAB
   // the small-batch kernels inside the host-free ICP loop (non-null; see IcpLoopDev): this is launch `loop_iter`; the rows of
   // pair sums of the launch in front (loop_rows of them; this launch writes `partials`, the other buffer of the pair) and the
@@ -193,6 +202,7 @@ size_t search_max_lanes(size_t n);     // most lanes any search kernel launches 
 bool search_uses_queue(size_t n);      // does it get the work-queue kernel (needs q_ctr / q_ctr_next)?
 bool search_can_fuse(size_t n);
 bool search_fuse_after_last_pays(size_t n);   // FUSE 3 by default for a batch of this size?
+bool search_cert_capable(const SearchArgs& a);   // can this pass keep certificates (SearchArgs::cert)?  a.T set
 int search_fuse_kind(size_t n);   // 0 no, 1 persistent-lane FUSE modes (on request), 2 chunk epilogue of the small-batch kernels        // does a batch of n queries get the kernel that can fuse the base sums?
 uint32_t search_fused_rows(size_t n, int side_by_side = 1);  // rows of partials the fused kernel writes
 #ifdef TDTK_LAB

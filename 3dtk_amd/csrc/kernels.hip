@@ -146,6 +146,9 @@ struct LaneStack {
   }
 };
 
+// the longest slab (queries per wave) of a pass that keeps certificates: one piece that order_piece can order (search_refill_body)
+constexpr int CERT_MAX_SLAB = 256;
+
 // descend() for the persistent-lane kernel: the axis comes with the record (KdHot::axis) and the child references keep
 // their axis bit -- whoever turns a reference into an address or a leaf value masks it anyway (24-bit multiply, REF_VAL)
 template <class STK>
@@ -485,6 +488,9 @@ __device__ __forceinline__ int q16_index(const double v, const double lo, const 
   return (int)u - 32768;                     // u >= 0: truncation is floor
 }
 
+// an fp32 value at or below a non-negative fp64 one: the conversion rounds to nearest (2^-24 relative), the factor takes 1e-6
+__device__ __forceinline__ float f32_below(const double v) { return (float)v * 0.999999f; }
+
 // ---- bucket_scan_q16 (round 5): the same filter on a 16-bit shadow -- eight 16-byte loads per bucket instead of fifteen.
 // Every slot's coordinates sit on ONE grid over the tree's root box (TreeDev::q16: 65536 cells per axis, cell = largest
 // extent / 65535, int16 = index - 32768, two slots per 12 bytes { (x0,y0), (x1,y1), (z0,z1) }), the query is put on the same
@@ -499,10 +505,15 @@ __device__ __forceinline__ int q16_index(const double v, const double lo, const 
 //                                                             =>  t_j > t_k: somebody else is strictly closer.
 // Survivors are tested in fp64, in bucket order, with the strict '<' (kdTreeImpl.h:351-357 restricted to who can win).
 // No proof available (radius beyond the grid, thresholds not finite): every slot of the bucket is a survivor.
+template <bool CERT = false>
 __device__ __forceinline__ void bucket_scan_q16(const char* __restrict__ t_q16, const char* __restrict__ pb, const int start, const int count,
                                                 const uint32_t o0, const BoxF32& bx, const uint32_t qxy, const uint32_t qzz, const bool q_in,
-                                                const double qx, const double qy, const double qz, double& best, int& bk, const double tie, bool& thin)
+                                                const double qx, const double qy, const double qz, double& best, int& bk, const double tie, bool& thin,
+                                                const bool fixw = false, float* const slot = nullptr)
 {
+  // fixw (a walk that leaves a certificate): `best` is the FIXED prune radius and stays; the acceptance threshold (fp64), the
+  // runner-up's d2 (rounded down) and the margin m live in the lane's LDS slot { thr, ru, m }.  (B) then asks for the margin too:
+  // sqrt(s_j) > sqrt(s_k) + 2 sqrt(3) + m cells  =>  t_j > t_k + m, and every survivor that is not the hit goes into the runner-up.
   typedef short v2s __attribute__((ext_vector_type(2)));
   const uint32_t go = (uint32_t)start * 6u;      // 6 bytes per slot; start is a multiple of 4: 8-byte aligned
   uint4 W[8];
@@ -539,7 +550,8 @@ __device__ __forceinline__ void bucket_scan_q16(const char* __restrict__ t_q16, 
     float thr = bx.pthr16;
     if (q_in && smin < 1000000000) {
       // (B): t_k <= sqrt(s_k) + 1.7321, t_j >= sqrt(s_j) - 1.7321
-      const float rub = __builtin_amdgcn_sqrtf(sminf) * 1.000001f + 3.47f;
+      float rub = __builtin_amdgcn_sqrtf(sminf) * 1.000001f + 3.47f;
+      if (CERT && fixw) rub += slot[3] * bx.qs * 1.000001f;          // the margin in cells, rounded up (qs is)
       thr = fminf(thr, rub * rub * 1.000001f);               // fminf skips a NaN operand: either proof alone is valid
     }
     if (thr < 2.0e9f) {
@@ -549,15 +561,40 @@ __device__ __forceinline__ void bucket_scan_q16(const char* __restrict__ t_q16, 
     } else surv = 0xFFFFFu;                                  // no proof available: every slot is tested exactly
     surv &= cmask20;
   }
-  while (surv) {                          // in bucket order: lowest set bit first
-    const uint32_t j = (uint32_t)__builtin_ctz(surv);
-    surv &= surv - 1u;
-    const uint32_t oj = o0 + (j << 5);
-    const double2 pxy = gload<double2>(pb, oj);
-    const double pz = gload<double>(pb, oj + 16);
-    const double dx = pxy.x - qx, dy = pxy.y - qy, dz = pz - qz;
-    const double dj = dx * dx + dy * dy + dz * dz;
-    if (dj < best) { thin = thin || (best - dj <= tie); best = dj; bk = (int)(oj >> 5); }
+  if constexpr (!CERT) {                  // (an instantiation that keeps no certificates: the loop as it always was)
+    while (surv) {                        // in bucket order: lowest set bit first
+      const uint32_t j = (uint32_t)__builtin_ctz(surv);
+      surv &= surv - 1u;
+      const uint32_t oj = o0 + (j << 5);
+      const double2 pxy = gload<double2>(pb, oj);
+      const double pz = gload<double>(pb, oj + 16);
+      const double dx = pxy.x - qx, dy = pxy.y - qy, dz = pz - qz;
+      const double dj = dx * dx + dy * dy + dz * dz;
+      if (dj < best) { thin = thin || (best - dj <= tie); best = dj; bk = (int)(oj >> 5); }
+    }
+  } else {
+    if (!surv) return;
+    double cd = best;                     // the reference's closest_d2
+    float ru = __builtin_inff();
+    if (fixw) { cd = *reinterpret_cast<const double*>(slot); ru = slot[2]; }
+    while (surv) {
+      const uint32_t j = (uint32_t)__builtin_ctz(surv);
+      surv &= surv - 1u;
+      const uint32_t oj = o0 + (j << 5);
+      const double2 pxy = gload<double2>(pb, oj);
+      const double pz = gload<double>(pb, oj + 16);
+      const double dx = pxy.x - qx, dy = pxy.y - qy, dz = pz - qz;
+      const double dj = dx * dx + dy * dy + dz * dz;
+      // (selects, no branches -- nested ones cost this instantiation scalar registers it does not have: the loser of the
+      // comparison, the tested point or the hit it displaces, goes into the runner-up; the threshold a walk starts from is
+      // nobody's distance.  Without fixw -- a launch of this instantiation without the array -- the runner-up is dropped.)
+      const bool take = dj < cd;
+      thin = thin || (take && cd - dj <= tie);
+      ru = (!take || bk >= 0) ? fminf(ru, f32_below(take ? cd : dj)) : ru;
+      cd = take ? dj : cd; bk = take ? (int)(oj >> 5) : bk;
+    }
+    if (fixw) { *reinterpret_cast<double*>(slot) = cd; slot[2] = ru; }
+    else best = cd;
   }
 }
 
@@ -1384,8 +1421,16 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   typedef typename std::conditional<(ORD_MAX > 256), unsigned short, unsigned char>::type ord_t;
   __shared__ ord_t lds_order[ORDER ? BLOCK / WAVE : 1][ORDER ? ORD_MAX : 4];
   ord_t* const my_order = lds_order[ORDER ? threadIdx.x / WAVE : 0];
+  // (CERT: the instantiation that can keep a certificate per query -- further down)
+  constexpr bool CERT = DEFER && BUCKET_Q16 && !LAZY && !FAT && !PIPE && TOP == 0 && PROBE == 0 && FUSE == 3 && !DYN && !SHARE && ORDER;
+  // (the sweep covers a slab in ORD_MAX / WAVE rounds, one bit of walkbits each, and a slab with certificates is ONE ordered piece:
+  // search_cert_capable admits slabs of up to CERT_MAX_SLAB queries)
+  static_assert(!CERT || (ORD_MAX >= CERT_MAX_SLAB && ORD_MAX / WAVE <= 32), "a slab with certificates is one ordered piece");
   bool ordered = false;
   size_t piece0 = 0;
+  // (bit r: the query at offset 64 r + lane of the piece is handed out -- all of them, unless the certificate sweep below has
+  // answered some without a walk; n_listed: how many the order lists)
+  uint32_t walkbits = 0xFFFFFFFFu, n_listed = 0;
   auto order_piece = [&](size_t p0, size_t p1) {
     ordered = false;
     piece0 = p0;
@@ -1399,8 +1444,9 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
 #pragma unroll
     for (int r = 0; r < ORD_MAX / WAVE; r++) {
       const uint32_t o = (uint32_t)r * WAVE + lane;
-      cvv[r] = (o < cntp) ? (unsigned)a.cost[p0 + o] : 0u;
-      if (o < cntp) { mn = min(mn, cvv[r]); mx = max(mx, cvv[r]); }
+      const bool w = o < cntp && (!CERT || ((walkbits >> r) & 1u) != 0u);
+      cvv[r] = w ? (unsigned)a.cost[p0 + o] : 0u;
+      if (w) { mn = min(mn, cvv[r]); mx = max(mx, cvv[r]); }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -1411,7 +1457,8 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
 #pragma unroll
     for (int r = 0; r < ORD_MAX / WAVE; r++) {
       const uint32_t o = (uint32_t)r * WAVE + lane;
-      cls[r] = (o < cntp) ? (int)min(((cvv[r] - mn) * 8u) / span, 7u) : -1;
+      const bool w = o < cntp && (!CERT || ((walkbits >> r) & 1u) != 0u);
+      cls[r] = w ? (int)min(((cvv[r] - mn) * 8u) / span, 7u) : -1;
     }
     uint32_t base = 0;
     for (int k = 7; k >= 0; k--) {
@@ -1426,6 +1473,88 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
     ordered = true;
+    n_listed = base;
+  };
+  // ---- a certificate per query: queries whose hit provably stays nearest are not walked ----
+  // SearchArgs::cert (one float per query; the launch sets it only for the instantiation that defers the quick check and adds up
+  // its own sums, one ordered piece per slab).  A walk of such a pass prunes far children and bucket slots against a radius that
+  // does NOT shrink, W = (d + m)^2 -- d the distance it starts from (the previous hit's, or sqrt(maxd2)), m a margin -- while
+  // acceptance keeps the reference's closest_d2 (the lane's LDS slot).  What it visits is a superset of the reference's walk in
+  // the reference's order, so the acceptances are the reference's (the argument of the deferred quick check, `thin` included);
+  // and when it retires, every tree point other than its hit is accounted for: cut off behind a plane at myd^2 >= W, rejected by
+  // the bucket filter's (A) at d >= sqrt(W) or by (B) at more than m beyond a point of that bucket (which is no nearer than the
+  // hit), or tested in fp64 and folded into the runner-up.  L = min(sqrt(W), d_hit + m, sqrt(runner-up)), rounded down, is a
+  // lower bound on the distance to all of them (with no hit: to every point, d_hit = sqrt(maxd2)); 0 for a thin acceptance.
+  // The sweep: before the wave hands out anything it passes over its slab, consecutive lanes, consecutive queries: applies
+  // `pending` (the hand-out then does not), maps the old and the new position into the tree's frame, delta = how far the query
+  // moved (rounded up).  A query with a hit at d2 < maxd2 and sqrt(d2) < L - delta keeps its hit -- every other point is
+  // still further away, whatever the order of the walk --; one without a hit and sqrt(maxd2) <= L - delta stays without.
+  // Either keeps kpos and its cost byte, stores L - delta and is left out of the hand-out order (walkbits).  Everybody else gets
+  // its margin m = clamp(kappa delta, lo d, hi d) stored in the same array, to be read where a lane takes the query.
+  // Roundings: every fp32 step rounds away from the skip by a factor 1e-6 (>= 8 ulp); eabs = 1e-9 (|q| +
+  // absmax + R) stands for the fp64 roundings of dev_xf3 and of the distance formula (2^-50 of the same magnitudes).
+  const bool certw = CERT && a.cert != nullptr;         // (used up to the first hand-out; a lane on a walk carries NBK_FIXW)
+  __shared__ uint4 lds_cert[CERT ? BLOCK : 1];          // per lane: { closest_d2 (fp64), runner-up d2, m }
+  float* const my_slot = reinterpret_cast<float*>(&lds_cert[CERT ? threadIdx.x : 0]);
+  unsigned c_skh = 0, c_skn = 0, c_walk = 0;            // instrumented: skipped with a hit / without one, handed out
+  auto cert_sweep = [&](size_t p0, size_t p1) {
+    // (scalar registers are what this kernel is short of: each group of arguments is read behind an opaque pointer where it is
+    // used -- the two matrices one after the other, the thresholds behind them -- and the slab is indexed in 32 bits)
+    walkbits = 0u;
+    const uint32_t q0 = (uint32_t)p0, cntp = (uint32_t)(p1 - p0);
+    for (uint32_t r = 0; r < (uint32_t)(ORD_MAX / WAVE); r++) {
+      const uint32_t o = r * WAVE + lane;
+      if (o >= cntp) continue;
+      const uint32_t q = q0 + o, q8 = q << 3, q4 = q << 2;
+      const SearchArgs* ap = &a;
+      asm volatile("" : "+s"(ap));
+      const int kp = gload<int>(reinterpret_cast<const char*>(a_kpos), q4);
+      const float Lq = ap->cert_use ? gload<float>(reinterpret_cast<const char*>(ap->cert), q4) : 0.f;
+      const double ox = gload<double>(reinterpret_cast<const char*>(ap->x), q8), oy = gload<double>(reinterpret_cast<const char*>(ap->y), q8),
+                   oz = gload<double>(reinterpret_cast<const char*>(ap->z), q8);
+      double tx = ox, ty = oy, tz = oz;
+      if (ap->has_pending) {  // Scan::transformReduced fused in (scan.cc:851-875), as at a hand-out
+        dev_xf3_inplace(ap->pending, tx, ty, tz);
+        gstore<double>(reinterpret_cast<char*>(ap->x), q8, tx); gstore<double>(reinterpret_cast<char*>(ap->y), q8, ty);
+        gstore<double>(reinterpret_cast<char*>(ap->z), q8, tz);
+        if (ap->nx) {
+          double px = ap->nx[q], py = ap->ny[q], pz = ap->nz[q];
+          dev_xf3normal(ap->pending, px, py, pz);
+          ap->nx[q] = px; ap->ny[q] = py; ap->nz[q] = pz;
+        }
+      }
+      const SearchArgs* ap2 = &a;
+      asm volatile("" : "+s"(ap2), "+v"(tx));
+      double ax = ox, ay = oy, az = oz, bxq = tx, byq = ty, bzq = tz;     // old and new position in the tree's frame
+      if (ap2->has_inv) { dev_xf3(ap2->inv, ox, oy, oz, ax, ay, az); dev_xf3(ap2->inv, tx, ty, tz, bxq, byq, bzq); }
+      const double ex = bxq - ax, ey = byq - ay, ez = bzq - az;
+      const float mv = __builtin_amdgcn_sqrtf((float)(ex * ex + ey * ey + ez * ez) * 1.000001f) * 1.000001f;
+      const float qm = fmaxf(fmaxf(fabsf((float)bxq), fabsf((float)byq)), fabsf((float)bzq));
+      const SearchArgs* ap3 = &a;
+      asm volatile("" : "+s"(ap3), "+v"(bxq));
+      const double maxd2 = ap3->maxd2;
+      const float R = __builtin_amdgcn_sqrtf((float)maxd2) * 1.000001f;
+      const float eabs = 1.0e-9f * (ap3->T.absmax + R + qm) + 1.0e-30f;
+      const float delta = mv + eabs;
+      float dh = R;
+      bool hit = false;
+      if (kp >= 0) {
+        const uint32_t po = (uint32_t)kp << 5;
+        const double2 pxy = gload<double2>(reinterpret_cast<const char*>(pts), po);
+        const double pzz = gload<double>(reinterpret_cast<const char*>(pts), po + 16);
+        const double dx = pxy.x - bxq, dy = pxy.y - byq, dz = pzz - bzq;
+        const double d = dx * dx + dy * dy + dz * dz;        // as the bucket scan computes it
+        if (d < maxd2) { hit = true; dh = __builtin_amdgcn_sqrtf((float)d * 1.000001f) * 1.000001f; }
+      }
+      const float rhs = Lq - delta * 1.000001f - eabs;      // (NaN anywhere: no comparison passes, the query walks)
+      const bool skip = (kp >= 0) ? (hit && dh < rhs) : (dh <= rhs);
+      const float mrg = fminf(fmaxf(ap3->cert_kappa * delta, ap3->cert_lo * dh), ap3->cert_hi * dh);
+      if (!skip) walkbits |= 1u << r;
+      gstore<float>(reinterpret_cast<char*>(ap3->cert), q4, skip ? rhs * 0.999999f : mrg);
+      if (COUNT && skip) { if (kp >= 0) ++c_skh; else ++c_skn; }
+    }
+    // (the moved points and the margins are read back by other lanes of this wave: workgroup scope, as for the sums pass)
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
   };
   size_t next_q, end_q;  // wave-uniform: the queries this wave may still hand to its lanes
   // SHARE (round 4): the waves of a workgroup hand out their slabs TOGETHER -- one cursor in LDS over the workgroup's
@@ -1498,7 +1627,10 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
       end_q = next_q + sub;
       if (next_q > slab_end) next_q = slab_end;
       if (end_q > slab_end) end_q = slab_end;
+      if (certw) cert_sweep(next_q, end_q);
       order_piece(next_q, end_q);
+      if (certw && ordered) end_q = next_q + n_listed;      // the walkers only
+      walkbits = 0xFFFFFFFFu;     // (a later piece -- there is none with certificates -- lists everybody: a constant from here on)
       if constexpr (SHARE) {
         // (one piece per wave -- the launcher sets phases = 1 --, so the workgroup's slabs are one stretch of the scan)
         wg0 = (size_t)(bid & 7u) * wpx * (size_t)a.qpw + (size_t)((bid >> 3) * (BLOCK / WAVE)) * sub;
@@ -1644,6 +1776,10 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   // field keeps 29 bits and is clamped to 255 where it is stored)
   constexpr uint32_t NBK_DEFER = 0x80000000u, NBK_THIN = 0x40000000u, NBK_UCHK = 0x20000000u, NBK_COST = 0x1FFFFFFFu;
   constexpr bool DEFER_UCHK = false;
+  // (NBK_FIXW: the lane's walk prunes against a fixed radius and leaves a certificate -- every lane of a launch with
+  // SearchArgs::cert, none otherwise; a per-lane bit for the same reason as the others.  It takes the bit DEFER_UCHK would.)
+  constexpr uint32_t NBK_FIXW = NBK_UCHK;
+  static_assert(!(CERT && DEFER_UCHK), "one bit");
   unsigned c_int = 0, c_leaf = 0, c_pts = 0, c_redo = 0;
   unsigned c_t1 = 0, c_t2 = 0;   // lab, instrumented instantiations: trips of the wave through the node walk / the bucket scan
   unsigned nbk = 0;   // buckets this lane's query has visited (the next pass's ordering key)
@@ -1660,6 +1796,16 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
     // ---- retire finished queries, hand out new ones ----
     const bool idle = (cur == REF_DONE);
     if (idle && have) {
+      if (CERT && (nbk & NBK_FIXW) != 0u) {
+        // the certificate: L = min(sqrt(W), d_hit + m, sqrt(runner-up)), every step rounded down; none behind a thin acceptance
+        const float sw = __builtin_amdgcn_sqrtf(f32_below(best)) * 0.999999f;
+        const float dm = __builtin_amdgcn_sqrtf(f32_below(*reinterpret_cast<const double*>(my_slot))) * 0.999999f + my_slot[3];
+        const float sr = __builtin_amdgcn_sqrtf(my_slot[2]) * 0.999999f;
+        const float L = fminf(fminf(sw, dm), sr) * 0.999999f;
+        const SearchArgs* ap = &a;
+        asm volatile("" : "+s"(ap));      // (the array's address is read here, not kept in scalar registers across the walk)
+        gstore<float>(reinterpret_cast<char*>(ap->cert), (uint32_t)qi << 2, ((nbk & NBK_THIN) == 0u && sw >= 0.f && dm >= 0.f && sr >= 0.f && L > 0.f) ? L : 0.f);   // (a NaN: none)
+      }
       if (DEFER_OK && (nbk & (NBK_DEFER | NBK_THIN)) == (NBK_DEFER | NBK_THIN)) {
         // accepted a point within `tie` of its closest_d2 on a walk without quick checks: marked (kpos -2, the dearest cost) and
         // searched again behind the slab, as the reference does it (the pass behind this loop); nobody outside this launch sees
@@ -1758,10 +1904,16 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
         // the previous hit (warm start) is requested with the coordinates, not behind them: one round trip less
         // (global loads / stores at 32-bit byte offsets: a scan has < 2^27 points)
         const uint32_t m8 = (uint32_t)mine << 3;
+        const SearchArgs* hp = &a;
+        bool certh = false;
+        if constexpr (CERT) {
+          asm volatile("" : "+s"(hp));    // (read where a lane takes a query, like the matrices: not hoisted, not kept live)
+          certh = hp->cert != nullptr;
+        }
         const int kp_prev = a.warm ? gload<int>(reinterpret_cast<const char*>(a_kpos), (uint32_t)mine << 2) : -1;
         double tx = gload<double>(reinterpret_cast<const char*>(a.x), m8), ty = gload<double>(reinterpret_cast<const char*>(a.y), m8),
                tz = gload<double>(reinterpret_cast<const char*>(a.z), m8);
-        if (a.has_pending) {  // Scan::transformReduced fused in (scan.cc:851-875)
+        if (a.has_pending && !certh) {  // Scan::transformReduced fused in (scan.cc:851-875); (certh: the sweep has moved the slab)
           dev_xf3_inplace(a.pending, tx, ty, tz);
           gstore<double>(reinterpret_cast<char*>(a.x), m8, tx); gstore<double>(reinterpret_cast<char*>(a.y), m8, ty);
           gstore<double>(reinterpret_cast<char*>(a.z), m8, tz);
@@ -1784,6 +1936,18 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
         // (every lane of a DEFER pass walks in the one mode; DEFER_UCHK: one without a previous hit -- or whose warm radius is
         // not below maxd2 -- makes the quick check where the wave visits a node together)
         if (DEFER_OK) nbk = (DEFER_UCHK && !(kp_prev >= 0 && best < a.maxd2)) ? (NBK_DEFER | NBK_UCHK) : NBK_DEFER;
+        if (COUNT) ++c_walk;
+        if (certh) {
+          // the fixed prune radius W = (sqrt(closest_d2) + m)^2 >= closest_d2, m from the sweep; `best` is W from here to the
+          // retire, the reference's closest_d2 lives in the lane's slot
+          float m = gload<float>(reinterpret_cast<const char*>(hp->cert), (uint32_t)mine << 2);
+          if (!(m >= 0.f)) m = 0.f;
+          nbk |= NBK_FIXW;
+          *reinterpret_cast<double*>(my_slot) = best; my_slot[2] = __builtin_inff(); my_slot[3] = m;
+          const double rw = (double)(__builtin_amdgcn_sqrtf((float)best) * 1.000001f + m);
+          const double W = rw * rw;
+          if (W >= best) best = W;            // (not finite, or below closest_d2 by a rounding: the radius stays closest_d2, fixed)
+        }
         bx.set_query(qx, qy, qz, T.absmax);
         q16_query();
         bx.set_radius(best);
@@ -1928,6 +2092,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
       if (COUNT) { ++c_leaf; c_pts += (unsigned)count; }
       if (COUNT && kLab) { const unsigned long long on = __ballot(true); if ((int)lane == __ffsll((long long)on) - 1) ++c_t2; }
       if (ORDER) nbk += 4u;
+      const bool fixw = CERT && (nbk & NBK_FIXW) != 0u;
       const char* pb = reinterpret_cast<const char*>(pts);
       const uint32_t o0 = (uint32_t)start << 5;              // byte offset of the bucket (< 4 GB)
       const uint32_t olast = o0 + ((uint32_t)(count - 1) << 5);
@@ -1935,7 +2100,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
       // three waves per SIMD; a tree without the filter this build uses -- degenerate box, no memory -- takes the fp64 loop)
       if (USE_Q16 && (PROBE == 0 || PROBE == 3) && (DEFER_OK || t_q16 != nullptr) && count <= 20) {
         bool thin = false;
-        bucket_scan_q16(t_q16, pb, start, count, o0, bx, q16xy, q16zz, q16in, qx, qy, qz, best, bk, a_tie, thin);
+        bucket_scan_q16<CERT>(t_q16, pb, start, count, o0, bx, q16xy, q16zz, q16in, qx, qy, qz, best, bk, a_tie, thin, fixw, my_slot);
         if (DEFER_OK && thin) nbk |= NBK_THIN;
       } else
       if (!USE_Q16 && (PROBE == 0 || PROBE == 3) && t_grp != nullptr && count <= 4 * GRP_TRIP) {
@@ -1943,6 +2108,11 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
       } else
       // PTS points per round trip, all their loads issued before the first use; the last group re-reads the final point
       // instead of running a scalar tail (a repeated point can never pass the strict '<' a second time)
+      {
+      // (CERT, fixw: closest_d2 and the runner-up in the lane's slot, as in bucket_scan_q16; every point of the bucket is tested)
+      double cd = best;
+      float ru = __builtin_inff();
+      if (fixw) { cd = *reinterpret_cast<const double*>(my_slot); ru = my_slot[2]; }
       for (uint32_t o = o0; o <= olast; o += 32u * PTS) {
         uint32_t oo[PTS];
         double px[PTS], py[PTS], pz[PTS];
@@ -1969,17 +2139,33 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
             asm volatile("" :: "v"(w));
           }
         }
+        if constexpr (!CERT) {
 #pragma unroll
-        for (int j = 0; j < PTS; j++)
-          if (dd[j] < best) { if (DEFER_OK && best - dd[j] <= a_tie) nbk |= NBK_THIN; best = dd[j]; bk = (int)(oo[j] >> 5); }
+          for (int j = 0; j < PTS; j++)
+            if (dd[j] < best) { if (DEFER_OK && best - dd[j] <= a_tie) nbk |= NBK_THIN; best = dd[j]; bk = (int)(oo[j] >> 5); }
+        } else {
+          // the loser goes into the runner-up (not the re-read of the last point, not the threshold the walk started from)
+#pragma unroll
+          for (int j = 0; j < PTS; j++) {
+            const bool take = dd[j] < cd, again = j > 0 && oo[j] == oo[j - 1];
+            if (take && cd - dd[j] <= a_tie) nbk |= NBK_THIN;
+            ru = (take ? bk >= 0 : !again) ? fminf(ru, f32_below(take ? cd : dd[j])) : ru;
+            if (take) { cd = dd[j]; bk = (int)(oo[j] >> 5); }
+          }
+        }
       }
-      bx.set_radius(best);
+      if constexpr (CERT) {
+        if (fixw) { *reinterpret_cast<double*>(my_slot) = cd; my_slot[2] = ru; }
+        else best = cd;
+      }
+      }
+      if (!fixw) bx.set_radius(best);
       cur = REF_DONE;
       while (st.sp > 0) {
         --st.sp;
         uint32_t r; double m2;
         st.top(r, m2);
-        if (m2 < best) { cur = r; break; }
+        if (fixw || m2 < best) { cur = r; break; }      // (fixw: pushed against the same radius)
       }
     }
   }
@@ -2038,6 +2224,14 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
     if (DEFER_OK) {   // queries searched a second time, with every check (a thin acceptance on the walk that defers them)
       const unsigned long long s_redo = wave_sum_u(c_redo);
       if (lane == 0 && s_redo) atomicAdd(&a.counters[7], s_redo);
+    }
+    {                 // tdtk_skip_counters: answered by their certificate (with a hit, without one), handed out to a lane
+      const unsigned long long s_skh = wave_sum_u(c_skh), s_skn = wave_sum_u(c_skn), s_walk = wave_sum_u(c_walk);
+      if (lane == 0) {
+        if (s_skh) atomicAdd(&a.counters[10], s_skh);
+        if (s_skn) atomicAdd(&a.counters[11], s_skn);
+        if (s_walk) atomicAdd(&a.counters[12], s_walk);
+      }
     }
     if (kLab) {       // wave trips: (lane-visits of a phase) / (64 x its trips) = the share of lane-slots that phase keeps busy
       const unsigned long long s_t1 = wave_sum_u(c_t1), s_t2 = wave_sum_u(c_t2);
@@ -2853,9 +3047,24 @@ uint32_t search_fused_rows(size_t n, int side_by_side)
   int q;
   return refill_grid_b(n, 128, &q, side_by_side);
 }
+// Can a pass with these arguments keep certificates (SearchArgs::cert)?  Exactly the launches of SinglePass<.., FUSE 3, DEFER>
+// whose slab is one ordered piece: persistent lanes, sums by the waves themselves, a repeated pass over a tree with split halves
+// and the 16-bit shadow, cost bytes of the previous pass, every query a candidate, nobody asking for the d2 array.  The host asks
+// before it hands the array over (api_search.cpp: a certificate is valid from one such pass to the next only); the launch asks
+// again and drops the array otherwise.
+bool search_cert_capable(const SearchArgs& a)
+{
+  if (kLab || !BUCKET_Q16 || pick_variant(a.n) != 20 || a.fuse != 3) return false;
+  if (!(a.warm && a.tie > 0.0 && a.T.split != nullptr && a.T.q16 != nullptr)) return false;
+  if (!(a.use_cost && a.cost != nullptr) || a.skip != nullptr || a.d2 != nullptr || a.side_by_side > 1) return false;
+  int qpw;
+  (void)refill_grid_b(a.n, 128, &qpw, a.side_by_side);
+  return qpw <= CERT_MAX_SLAB;     // (= SinglePass's ORD_MAX: the body asserts it)
+}
 template <bool COUNT, int FUSE>
 static void launch_refill128(SearchArgs& a, hipStream_t s)
 {
+  if (a.cert && !(FUSE == 3 && search_cert_capable(a))) a.cert = nullptr;
 #ifdef TDTK_LAB
   if (lab_refill_own_grid<COUNT, FUSE>(a, s)) return;
 #endif

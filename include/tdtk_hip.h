@@ -573,9 +573,15 @@ int tdtk_last_timings(double out[4]);
  * worth: DESIGN.md section 4, "the quick check deferred").
  * on == 2: while counting, every search also starts cold (no warm start, no deferred quick check): the counters then hold
  * the walk of the reference's _FindClosest (kdTreeImpl.h:345-383) over the same queries -- SURVEY 8(d)'s n_int / n_pts,
- * "properties of (tree, query, maxdist2), independent of implementation"; the results, and so a loop's path, are unchanged. */
+ * "properties of (tree, query, maxdist2), independent of implementation"; the results, and so a loop's path, are unchanged.
+ * With on == 1 the counters are the launches' OWN walk, which does depend on the implementation: from the third pass of a
+ * tdtk_icp_match loop on, queries answered by their certificate (tdtk_skip_counters) are counted in out[3] but visit nothing. */
 int tdtk_visit_counting(int device, int on);
 int tdtk_visit_counters(int device, uint64_t out[8]);
+/* the instrumented passes of tdtk_icp_match since tdtk_visit_counting(device, on): queries of repeated passes answered by their
+ * certificate -- the previous hit provably stays nearest (out[0]), or there provably is still none (out[1]): DESIGN.md section 4,
+ * "a certificate per query" --, queries handed to a lane and walked (out[2]), second searches (out[3] = tdtk_visit_counters' out[7]) */
+int tdtk_skip_counters(int device, uint64_t out[4]);
 /* measured roofline denominators: kind 0 = HBM stream copy over `bytes` (read + written per pass), kind 1 =
  * repeated reads of an L2-resident buffer (bytes <= 16 MB); best of `reps` passes in GB/s */
 int tdtk_measure_bandwidth(int device, int kind, size_t bytes, int reps, double* gbs);
