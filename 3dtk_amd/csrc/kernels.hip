@@ -237,6 +237,7 @@ __device__ __forceinline__ void gstore(char* base, const uint32_t off, const V v
 #define TDTK_PIN_S32(x) asm volatile("" : "+s"(x))
 #define TDTK_PIN_SF(x) asm volatile("" : "+s"(x))
 #define TDTK_PIN_VF(x) asm volatile("" : "+v"(x))
+#define TDTK_PIN_V32(x) asm volatile("" : "+v"(x))
 
 // ---- the box test at fp32 rate, without changing a single decision ---------------------------------------------
 // The reference prunes a node iff  a >= 0 && a*a >= closest_d2,  a = max_i(|q_i - c_i| - h_i)  in fp64
@@ -1331,12 +1332,15 @@ __global__ void __launch_bounds__(BLOCK) k_search_g8_multi(const SearchArgs* __r
 // contended counter costs ~0.6 us and they serialise per counter (1M queries, 64-query draws: 0.93 ms against 0.27 ms
 // static; 256-query draws: 0.58 ms), and (b) the premise is wrong at this size -- a chip full of resident waves
 // (7168) leaves 1M queries only ~140 per wave, i.e. MORE drains per query than the static 224..256-query slabs.
-// diagnostics (TDTK_WAVE_TRACE=<launch index>): start / end time (100 MHz) and XCD of every wave of one launch
+// diagnostics (TDTK_WAVE_TRACE=<launch index>[,<launch index>...]): the 100 MHz clock of every wave of those launches at entry
+// and at the end of each phase, and its XCD.  Words per wave (WT_*): entry, second-search pass left, XCD / HW_ID, end of the
+// certificate sweep, end of order_piece, first hand-out done, main loop left, sums done (tools/cert_phases.py makes the table).
 #define WTRACE_MAX 32768u
+enum { WT_ENTRY = 0, WT_REDO = 1, WT_HWID = 2, WT_SWEEP = 3, WT_ORDER = 4, WT_FIRST = 5, WT_LOOP = 6, WT_SUMS = 7, WT_WORDS = 8 };
 #ifdef TDTK_LAB
-__device__ unsigned long long g_wtrace[3 * WTRACE_MAX];
+__device__ unsigned long long g_wtrace[WT_WORDS * WTRACE_MAX];
 #else
-__device__ unsigned long long g_wtrace[3];     // (never touched: a.trace is a lab switch)
+__device__ unsigned long long g_wtrace[WT_WORDS];     // (never touched: a.trace is a lab switch)
 #endif
 
 // the body of k_search_refill for workgroup `bid` of the `nb` that search one batch of queries (the kernel proper and
@@ -1358,6 +1362,28 @@ struct RefillCfg {
   static constexpr bool DYN = false, FAT = false, SHARE = false, PIPE = false;
   static constexpr int PTS = 4, PROBE = 0, TOP = 0;
 };
+// The argument block where a group of its fields is used: behind an opaque pointer -- nothing is hoisted out of the walk or kept
+// live across it -- of the CONSTANT address space, so that every field is an s_load.  (Laundered as a generic pointer the block
+// could be anywhere for all the compiler knows, and every field was a per-lane flat load: two counters, a full drain behind
+// each group, and one vector-memory instruction per value that is the same in all 64 lanes.)  The block is the kernel's
+// arguments, or an entry of the several-links table in device memory: global memory that nobody writes during the launch.
+typedef const SearchArgs __attribute__((address_space(4))) * args_kp;
+typedef const Mat4 __attribute__((address_space(4))) * mat_kp;
+__device__ __forceinline__ args_kp args_here(const SearchArgs& a)
+{
+  args_kp p = (args_kp)&a;
+  asm volatile("" : "+s"(p));
+  return p;
+}
+// the three rows a transform uses, into scalar registers
+__device__ __forceinline__ Mat4 mat_here(const mat_kp m)
+{
+  Mat4 A;
+#pragma unroll
+  for (int k = 0; k < 16; k++) A.m[k] = ((k & 3) == 3) ? 0.0 : m->m[k];
+  return A;
+}
+
 template <class CFG>
 __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const uint32_t bid, const uint32_t nb)
 {
@@ -1384,8 +1410,15 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   // whole kernel, and the compiler spilled it
   if (kLab && a.trace && lane == 0) {
     const uint32_t wid0 = bid * (BLOCK / WAVE) + threadIdx.x / WAVE;
-    if (wid0 < WTRACE_MAX) g_wtrace[3 * wid0] = wall_clock64();
+    if (wid0 < WTRACE_MAX) { g_wtrace[WT_WORDS * wid0 + WT_FIRST] = 0ull; g_wtrace[WT_WORDS * wid0 + WT_ENTRY] = wall_clock64(); }
   }
+  // (the end of a phase: nothing is carried for it -- the wave's index is worked out again where it is written)
+  auto wtrace_at = [&](const int word) {
+    if (kLab && a.trace && lane == 0) {
+      const uint32_t wid0 = bid * (BLOCK / WAVE) + threadIdx.x / WAVE;
+      if (wid0 < WTRACE_MAX) g_wtrace[WT_WORDS * wid0 + word] = wall_clock64();
+    }
+  };
   // lazy scan moves: the chain (at most LAZY_MAX matrices, the host sees to that) is staged in LDS once per workgroup
   __shared__ double lds_mv[LAZY ? LAZY_MAX * 16 : 1];
   if constexpr (LAZY) {
@@ -1431,7 +1464,8 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   // (bit r: the query at offset 64 r + lane of the piece is handed out -- all of them, unless the certificate sweep below has
   // answered some without a walk; n_listed: how many the order lists)
   uint32_t walkbits = 0xFFFFFFFFu, n_listed = 0;
-  auto order_piece = [&](size_t p0, size_t p1) {
+  // (pre: the piece's cost bytes where the certificate sweep has just read them, offset 64 r + lane in pre[r]; null: loaded here)
+  auto order_piece = [&](size_t p0, size_t p1, const unsigned* pre) {
     ordered = false;
     piece0 = p0;
     if (!ORDER || !a.use_cost || !a.cost || p1 <= p0 || p1 - p0 > (size_t)ORD_MAX) return;
@@ -1445,7 +1479,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
     for (int r = 0; r < ORD_MAX / WAVE; r++) {
       const uint32_t o = (uint32_t)r * WAVE + lane;
       const bool w = o < cntp && (!CERT || ((walkbits >> r) & 1u) != 0u);
-      cvv[r] = w ? (unsigned)a.cost[p0 + o] : 0u;
+      cvv[r] = w ? (pre ? pre[r] : (unsigned)a.cost[p0 + o]) : 0u;
       if (w) { mn = min(mn, cvv[r]); mx = max(mx, cvv[r]); }
     }
 #pragma unroll
@@ -1497,61 +1531,152 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   __shared__ uint4 lds_cert[CERT ? BLOCK : 1];          // per lane: { closest_d2 (fp64), runner-up d2, m }
   float* const my_slot = reinterpret_cast<float*>(&lds_cert[CERT ? threadIdx.x : 0]);
   unsigned c_skh = 0, c_skn = 0, c_walk = 0;            // instrumented: skipped with a hit / without one, handed out
+  // The sweep in two memory round trips for the whole slab: every load of every round (kpos, the certificate, the point, the cost
+  // byte) is issued before the first is used, then every hit's point, then the arithmetic and the stores with no wait between
+  // them, one fence at the end.  (One round at a time -- a slab of 168 queries is three -- each round was a chain of dependent
+  // trips of its own.)  The arguments come through SCALAR loads: the block is read behind an opaque pointer of the constant
+  // address space (args_here); behind an opaque generic pointer every field was a per-lane flat load, 39 of them per round.
+  // Scalar registers are what this kernel is short of, so the matrices are read where a round uses them -- `pending`, then
+  // `inv`, then the thresholds, out of the scalar cache -- and the slab is indexed in 32 bits.
+  // sw_cost: the cost bytes of the slab, which order_piece right behind the sweep then does not load again.
+  unsigned sw_cost[ORD_MAX / WAVE];
   auto cert_sweep = [&](size_t p0, size_t p1) {
-    // (scalar registers are what this kernel is short of: each group of arguments is read behind an opaque pointer where it is
-    // used -- the two matrices one after the other, the thresholds behind them -- and the slab is indexed in 32 bits)
+    constexpr int NR = ORD_MAX / WAVE;
     walkbits = 0u;
     const uint32_t q0 = (uint32_t)p0, cntp = (uint32_t)(p1 - p0);
-    for (uint32_t r = 0; r < (uint32_t)(ORD_MAX / WAVE); r++) {
-      const uint32_t o = r * WAVE + lane;
-      if (o >= cntp) continue;
-      const uint32_t q = q0 + o, q8 = q << 3, q4 = q << 2;
-      const SearchArgs* ap = &a;
-      asm volatile("" : "+s"(ap));
-      const int kp = gload<int>(reinterpret_cast<const char*>(a_kpos), q4);
-      const float Lq = ap->cert_use ? gload<float>(reinterpret_cast<const char*>(ap->cert), q4) : 0.f;
-      const double ox = gload<double>(reinterpret_cast<const char*>(ap->x), q8), oy = gload<double>(reinterpret_cast<const char*>(ap->y), q8),
-                   oz = gload<double>(reinterpret_cast<const char*>(ap->z), q8);
-      double tx = ox, ty = oy, tz = oz;
-      if (ap->has_pending) {  // Scan::transformReduced fused in (scan.cc:851-875), as at a hand-out
-        dev_xf3_inplace(ap->pending, tx, ty, tz);
-        gstore<double>(reinterpret_cast<char*>(ap->x), q8, tx); gstore<double>(reinterpret_cast<char*>(ap->y), q8, ty);
-        gstore<double>(reinterpret_cast<char*>(ap->z), q8, tz);
-        if (ap->nx) {
-          double px = ap->nx[q], py = ap->ny[q], pz = ap->nz[q];
-          dev_xf3normal(ap->pending, px, py, pz);
-          ap->nx[q] = px; ap->ny[q] = py; ap->nz[q] = pz;
+    int kp[NR];
+    float Lq[NR];
+    double ox[NR], oy[NR], oz[NR], hz[NR];
+    double2 hxy[NR];
+    // (an empty slab: nothing to read, nothing stored, so no fence either; sw_cost stays unset, which is safe only because
+    // order_piece returns on p1 <= p0 before it looks at `pre`.  cntp <= NR * WAVE: search_cert_capable admits no longer slab.)
+    if (cntp == 0u) return;
+    {
+      // (one basic block: a lane beyond the slab's end reads the slab's last query again and stores nothing -- under a per-lane
+      // branch each the compiler can no longer count which loads it waits for, and waits for all of them)
+      const args_kp ap = args_here(a);
+      const char* const gx = reinterpret_cast<const char*>(ap->x);
+      const char* const gy = reinterpret_cast<const char*>(ap->y);
+      const char* const gz = reinterpret_cast<const char*>(ap->z);
+      const char* const gc = reinterpret_cast<const char*>(ap->cert);
+      const bool use = ap->cert_use != 0;
+      const char* const gk = (ap->use_cost && a_cost) ? reinterpret_cast<const char*>(a_cost) : nullptr;   // (order_piece's own condition)
+      uint32_t qc[NR];
+#pragma unroll
+      for (int r = 0; r < NR; r++) {
+        qc[r] = q0 + min((uint32_t)r * WAVE + lane, cntp - 1u);
+        kp[r] = gload<int>(reinterpret_cast<const char*>(a_kpos), qc[r] << 2);
+      }
+#pragma unroll
+      for (int r = 0; r < NR; r++) {
+        Lq[r] = gload<float>(gc, qc[r] << 2);        // (what a pass that does not use the certificates finds here is not looked at)
+        ox[r] = gload<double>(gx, qc[r] << 3); oy[r] = gload<double>(gy, qc[r] << 3); oz[r] = gload<double>(gz, qc[r] << 3);
+      }
+#pragma unroll
+      for (int r = 0; r < NR; r++) sw_cost[r] = 0u;
+      if (gk) {
+#pragma unroll
+        for (int r = 0; r < NR; r++) sw_cost[r] = (unsigned)*(const unsigned char __attribute__((address_space(1)))*)(gk + qc[r]);
+      }
+      // (the indices of the hits are the first loads issued: waiting for them leaves the rest of the trip in flight)
+#pragma unroll
+      for (int r = 0; r < NR; r++) TDTK_PIN_V32(kp[r]);
+      // (a lane without a hit reads slot 0 and does not look at it: the loads of all rounds stay in one block as well)
+#pragma unroll
+      for (int r = 0; r < NR; r++) { hxy[r] = make_double2(0.0, 0.0); hz[r] = 0.0; }
+      if (ap->T.n_slots != 0u) {
+#pragma unroll
+        for (int r = 0; r < NR; r++) {
+          const uint32_t po = (kp[r] >= 0) ? (uint32_t)kp[r] << 5 : 0u;
+          hxy[r] = gload<double2>(reinterpret_cast<const char*>(pts), po);
+          hz[r] = gload<double>(reinterpret_cast<const char*>(pts), po + 16);
         }
       }
-      const SearchArgs* ap2 = &a;
-      asm volatile("" : "+s"(ap2), "+v"(tx));
-      double ax = ox, ay = oy, az = oz, bxq = tx, byq = ty, bzq = tz;     // old and new position in the tree's frame
-      if (ap2->has_inv) { dev_xf3(ap2->inv, ox, oy, oz, ax, ay, az); dev_xf3(ap2->inv, tx, ty, tz, bxq, byq, bzq); }
+#pragma unroll
+      for (int r = 0; r < NR; r++) {
+        TDTK_PIN_BATCH3(ox[r], oy[r], oz[r]);
+        TDTK_PIN_BATCH3(hxy[r].x, hxy[r].y, hz[r]);
+        TDTK_PIN_VF(Lq[r]);
+        TDTK_PIN_V32(sw_cost[r]);
+        if (!use) Lq[r] = 0.f;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < NR; r++) {
+      const uint32_t o = (uint32_t)r * WAVE + lane;
+      if ((uint32_t)r * WAVE >= cntp) continue;           // (wave-uniform: the slab has no such round)
+      const bool in = o < cntp;
+      const uint32_t q = q0 + o, q8 = q << 3, q4 = q << 2;
+      double tx = ox[r], ty = oy[r], tz = oz[r];
+      const args_kp ap = args_here(a);
+      if (ap->has_pending) {  // Scan::transformReduced fused in (scan.cc:851-875), as at a hand-out
+        const Mat4 P = mat_here(&ap->pending);
+        dev_xf3_inplace(P, tx, ty, tz);
+        if (in) {
+          gstore<double>(reinterpret_cast<char*>(ap->x), q8, tx); gstore<double>(reinterpret_cast<char*>(ap->y), q8, ty);
+          gstore<double>(reinterpret_cast<char*>(ap->z), q8, tz);
+        }
+      }
+      const args_kp ap2 = args_here(a);
+      TDTK_PIN_V64(tx);
+      double ax = ox[r], ay = oy[r], az = oz[r], bxq = tx, byq = ty, bzq = tz;     // old and new position in the tree's frame
+      if (ap2->has_inv) {
+        const Mat4 I = mat_here(&ap2->inv);
+        dev_xf3(I, ox[r], oy[r], oz[r], ax, ay, az); dev_xf3(I, tx, ty, tz, bxq, byq, bzq);
+      }
       const double ex = bxq - ax, ey = byq - ay, ez = bzq - az;
       const float mv = __builtin_amdgcn_sqrtf((float)(ex * ex + ey * ey + ez * ez) * 1.000001f) * 1.000001f;
       const float qm = fmaxf(fmaxf(fabsf((float)bxq), fabsf((float)byq)), fabsf((float)bzq));
-      const SearchArgs* ap3 = &a;
-      asm volatile("" : "+s"(ap3), "+v"(bxq));
+      const args_kp ap3 = args_here(a);
+      TDTK_PIN_V64(bxq);
       const double maxd2 = ap3->maxd2;
       const float R = __builtin_amdgcn_sqrtf((float)maxd2) * 1.000001f;
       const float eabs = 1.0e-9f * (ap3->T.absmax + R + qm) + 1.0e-30f;
       const float delta = mv + eabs;
       float dh = R;
       bool hit = false;
-      if (kp >= 0) {
-        const uint32_t po = (uint32_t)kp << 5;
-        const double2 pxy = gload<double2>(reinterpret_cast<const char*>(pts), po);
-        const double pzz = gload<double>(reinterpret_cast<const char*>(pts), po + 16);
-        const double dx = pxy.x - bxq, dy = pxy.y - byq, dz = pzz - bzq;
+      if (kp[r] >= 0) {
+        const double dx = hxy[r].x - bxq, dy = hxy[r].y - byq, dz = hz[r] - bzq;
         const double d = dx * dx + dy * dy + dz * dz;        // as the bucket scan computes it
         if (d < maxd2) { hit = true; dh = __builtin_amdgcn_sqrtf((float)d * 1.000001f) * 1.000001f; }
       }
-      const float rhs = Lq - delta * 1.000001f - eabs;      // (NaN anywhere: no comparison passes, the query walks)
-      const bool skip = (kp >= 0) ? (hit && dh < rhs) : (dh <= rhs);
+      const float rhs = Lq[r] - delta * 1.000001f - eabs;   // (NaN anywhere: no comparison passes, the query walks)
+      const bool skip = (kp[r] >= 0) ? (hit && dh < rhs) : (dh <= rhs);
       const float mrg = fminf(fmaxf(ap3->cert_kappa * delta, ap3->cert_lo * dh), ap3->cert_hi * dh);
-      if (!skip) walkbits |= 1u << r;
-      gstore<float>(reinterpret_cast<char*>(ap3->cert), q4, skip ? rhs * 0.999999f : mrg);
-      if (COUNT && skip) { if (kp >= 0) ++c_skh; else ++c_skn; }
+      if (in) {
+        if (!skip) walkbits |= 1u << r;
+        gstore<float>(reinterpret_cast<char*>(ap3->cert), q4, skip ? rhs * 0.999999f : mrg);
+        if (COUNT && skip) { if (kp[r] >= 0) ++c_skh; else ++c_skn; }
+      }
+    }
+    {
+      // the normals of a scan that carries them, moved the same way: one trip for the slab's loads, then the stores
+      const args_kp ap = args_here(a);
+      if (ap->has_pending && ap->nx) {
+        double* const gnx = ap->nx; double* const gny = ap->ny; double* const gnz = ap->nz;
+        const Mat4 P = mat_here(&ap->pending);
+        double ux[NR], uy[NR], uz[NR];
+#pragma unroll
+        for (int r = 0; r < NR; r++) {
+          const uint32_t o = (uint32_t)r * WAVE + lane, q8 = (q0 + o) << 3;
+          ux[r] = uy[r] = uz[r] = 0.0;
+          if (o < cntp) {
+            ux[r] = gload<double>(reinterpret_cast<const char*>(gnx), q8); uy[r] = gload<double>(reinterpret_cast<const char*>(gny), q8);
+            uz[r] = gload<double>(reinterpret_cast<const char*>(gnz), q8);
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < NR; r++) TDTK_PIN_BATCH3(ux[r], uy[r], uz[r]);
+#pragma unroll
+        for (int r = 0; r < NR; r++) {
+          const uint32_t o = (uint32_t)r * WAVE + lane, q8 = (q0 + o) << 3;
+          dev_xf3normal(P, ux[r], uy[r], uz[r]);
+          if (o < cntp) {
+            gstore<double>(reinterpret_cast<char*>(gnx), q8, ux[r]); gstore<double>(reinterpret_cast<char*>(gny), q8, uy[r]);
+            gstore<double>(reinterpret_cast<char*>(gnz), q8, uz[r]);
+          }
+        }
+      }
     }
     // (the moved points and the margins are read back by other lanes of this wave: workgroup scope, as for the sums pass)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -1627,8 +1752,9 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
       end_q = next_q + sub;
       if (next_q > slab_end) next_q = slab_end;
       if (end_q > slab_end) end_q = slab_end;
-      if (certw) cert_sweep(next_q, end_q);
-      order_piece(next_q, end_q);
+      if (certw) { cert_sweep(next_q, end_q); wtrace_at(WT_SWEEP); order_piece(next_q, end_q, sw_cost); }
+      else { wtrace_at(WT_SWEEP); order_piece(next_q, end_q, nullptr); }
+      wtrace_at(WT_ORDER);
       if (certw && ordered) end_q = next_q + n_listed;      // the walkers only
       walkbits = 0xFFFFFFFFu;     // (a later piece -- there is none with certificates -- lists everybody: a constant from here on)
       if constexpr (SHARE) {
@@ -1734,8 +1860,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   const char* const t_q16 = USE_Q16 ? reinterpret_cast<const char*>(T.q16) : nullptr;
   auto q16_query = [&]() {
     if (USE_Q16 && (DEFER_OK || t_q16)) {
-      const SearchArgs* ap = &a;
-      asm volatile("" : "+s"(ap));      // (read where a lane takes a query, like the matrices: not hoisted, not kept live)
+      const args_kp ap = args_here(a);  // (read where a lane takes a query, like the matrices: not hoisted, not kept live)
       bool out = false;
       const double sc = ap->T.q_scale;
       const uint32_t ix = (uint32_t)q16_index(qx, ap->T.q_lo[0], sc, out) & 0xFFFFu, iy = (uint32_t)q16_index(qy, ap->T.q_lo[1], sc, out) & 0xFFFFu,
@@ -1770,6 +1895,10 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   const char* const splitb = DEFER_OK ? reinterpret_cast<const char*>(T.split) : nullptr;
   const uint32_t split_off = DEFER_OK ? (uint32_t)(splitb - hotb) : 0u;
   const double a_tie = DEFER_OK ? a.tie : 0.0;
+  // (one word per wave: "a lane of this wave has marked a query for the second search" -- set where it retires, read once behind
+  // the loop; the address comes from the thread index, so nothing lives across the walk for it)
+  __shared__ uint32_t lds_thin[DEFER_OK ? BLOCK / WAVE : 1];
+  if (DEFER_OK && lane == 0) lds_thin[threadIdx.x / WAVE] = 0u;
   // (the two per-lane flags ride in the top bits of nbk, the query's cost counter: as lane masks of their own they were two more
   // SGPR pairs in a kernel that has none to spare -- spilled into VGPR lanes, +5 % on every launch)
   // (NBK_UCHK, with DEFER_UCHK only: a lane without a previous hit, which makes the quick check in wave-uniform visits; the cost
@@ -1802,8 +1931,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
         const float dm = __builtin_amdgcn_sqrtf(f32_below(*reinterpret_cast<const double*>(my_slot))) * 0.999999f + my_slot[3];
         const float sr = __builtin_amdgcn_sqrtf(my_slot[2]) * 0.999999f;
         const float L = fminf(fminf(sw, dm), sr) * 0.999999f;
-        const SearchArgs* ap = &a;
-        asm volatile("" : "+s"(ap));      // (the array's address is read here, not kept in scalar registers across the walk)
+        const args_kp ap = args_here(a);  // (the array's address is read here, not kept in scalar registers across the walk)
         gstore<float>(reinterpret_cast<char*>(ap->cert), (uint32_t)qi << 2, ((nbk & NBK_THIN) == 0u && sw >= 0.f && dm >= 0.f && sr >= 0.f && L > 0.f) ? L : 0.f);   // (a NaN: none)
       }
       if (DEFER_OK && (nbk & (NBK_DEFER | NBK_THIN)) == (NBK_DEFER | NBK_THIN)) {
@@ -1811,6 +1939,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
         // searched again behind the slab, as the reference does it (the pass behind this loop); nobody outside this launch sees
         // the mark
         bk = -2; nbk = 255u;
+        lds_thin[threadIdx.x / WAVE] = 1u;
       }
       gstore<int>(reinterpret_cast<char*>(a_kpos), (uint32_t)qi << 2, bk);
       if (ORDER && a_cost) a_cost[qi] = (unsigned char)min(nbk & NBK_COST, 255u);   // nbk: node visits + 4 per bucket
@@ -1865,7 +1994,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
       end_q = next_q + sub;
       if (next_q > slab_end) next_q = slab_end;
       if (end_q > slab_end) end_q = slab_end;
-      order_piece(next_q, end_q);
+      order_piece(next_q, end_q, nullptr);
     }
     uint32_t sh_base = 0;
     bool sh_draw = false;
@@ -1904,12 +2033,9 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
         // the previous hit (warm start) is requested with the coordinates, not behind them: one round trip less
         // (global loads / stores at 32-bit byte offsets: a scan has < 2^27 points)
         const uint32_t m8 = (uint32_t)mine << 3;
-        const SearchArgs* hp = &a;
-        bool certh = false;
-        if constexpr (CERT) {
-          asm volatile("" : "+s"(hp));    // (read where a lane takes a query, like the matrices: not hoisted, not kept live)
-          certh = hp->cert != nullptr;
-        }
+        const char* h_cert = nullptr;     // (read where a lane takes a query, like the matrices: not hoisted, not kept live)
+        if constexpr (CERT) h_cert = reinterpret_cast<const char*>(args_here(a)->cert);
+        const bool certh = h_cert != nullptr;
         const int kp_prev = a.warm ? gload<int>(reinterpret_cast<const char*>(a_kpos), (uint32_t)mine << 2) : -1;
         double tx = gload<double>(reinterpret_cast<const char*>(a.x), m8), ty = gload<double>(reinterpret_cast<const char*>(a.y), m8),
                tz = gload<double>(reinterpret_cast<const char*>(a.z), m8);
@@ -1940,7 +2066,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
         if (certh) {
           // the fixed prune radius W = (sqrt(closest_d2) + m)^2 >= closest_d2, m from the sweep; `best` is W from here to the
           // retire, the reference's closest_d2 lives in the lane's slot
-          float m = gload<float>(reinterpret_cast<const char*>(hp->cert), (uint32_t)mine << 2);
+          float m = gload<float>(h_cert, (uint32_t)mine << 2);
           if (!(m >= 0.f)) m = 0.f;
           nbk |= NBK_FIXW;
           *reinterpret_cast<double*>(my_slot) = best; my_slot[2] = __builtin_inff(); my_slot[3] = m;
@@ -1954,6 +2080,14 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
         }
       }
       next_q += (size_t)__popcll(idlem);
+      if (kLab && a.trace) {
+        // the first hand-out of the wave, once its lanes have their queries and their starting radii (the word is zero until then)
+        TDTK_PIN_V64(best);
+        if (lane == 0) {
+          const uint32_t wid0 = bid * (BLOCK / WAVE) + threadIdx.x / WAVE;
+          if (wid0 < WTRACE_MAX && g_wtrace[WT_WORDS * wid0 + WT_FIRST] == 0ull) g_wtrace[WT_WORDS * wid0 + WT_FIRST] = wall_clock64();
+        }
+      }
     }
     if (__ballot(cur != REF_DONE) == 0) {
       if constexpr (SHARE) { if (exhausted) break; continue; }
@@ -2169,6 +2303,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
       }
     }
   }
+  wtrace_at(WT_LOOP);
   if constexpr (DEFER_OK) {
     // ---- thin acceptances, searched again behind the slab ----
     // The wave passes over its own slab once more, consecutive lanes, consecutive queries; a query marked -2 above is read back
@@ -2177,10 +2312,14 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
     // were written by other lanes of this wave: a fence of workgroup scope makes them visible (as for the sums pass below, which
     // -- like everybody behind this launch -- only ever sees >= 0 or -1).
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    const SearchArgs* ap = &a;
-    asm volatile("" : "+s"(ap));      // (the arguments are read here, not kept in scalar registers across the search)
+    const args_kp ap = args_here(a);  // (the arguments are read here, not kept in scalar registers across the search)
     const bool balanced = kLab && ap->bounds != nullptr;     // this wave's slab is [reg0, slab_end), in one piece
-    const uint32_t slab = balanced ? (uint32_t)(slab_end - reg0) : (uint32_t)ap->qpw, sub32 = balanced ? 0x7FFFFFFFu : (uint32_t)sub;
+    uint32_t slab = balanced ? (uint32_t)(slab_end - reg0) : (uint32_t)ap->qpw;
+    const uint32_t sub32 = balanced ? 0x7FFFFFFFu : (uint32_t)sub;
+    // (no scan for marks nobody made: a lane that marked a query also set its wave's word in LDS -- where the wave alone
+    // searches its slab; the marks of a slab that other waves have searched too are found by the scan, as before)
+    if (!SHARE && !DYN && !(kLab && ap->pool_slab) &&
+        __builtin_amdgcn_readfirstlane((int)lds_thin[threadIdx.x / WAVE]) == 0) slab = 0u;
     for (uint32_t j0 = 0; j0 < slab; j0 += WAVE) {
       uint32_t j = j0 + lane, ph = 0;
       const bool in = j < slab;
@@ -2193,7 +2332,7 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
       const double tx = gload<double>(reinterpret_cast<const char*>(ap->x), q8), ty = gload<double>(reinterpret_cast<const char*>(ap->y), q8),
                    tz = gload<double>(reinterpret_cast<const char*>(ap->z), q8);
       double rx = tx, ry = ty, rz = tz;
-      if (ap->has_inv) dev_xf3(ap->inv, tx, ty, tz, rx, ry, rz);  // searchTree.cc:122
+      if (ap->has_inv) { const Mat4 I = mat_here(&ap->inv); dev_xf3(I, tx, ty, tz, rx, ry, rz); }  // searchTree.cc:122
       double rbest = ap->maxd2;
       int rbk = -1;
       unsigned r_int = 0, r_leaf = 0, r_pts = 0;
@@ -2208,9 +2347,9 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
   if (kLab && a.trace && lane == 0) {
     const uint32_t wid = bid * (BLOCK / WAVE) + threadIdx.x / WAVE;
     if (wid < WTRACE_MAX) {
-      g_wtrace[3 * wid + 1] = wall_clock64();
+      g_wtrace[WT_WORDS * wid + WT_REDO] = wall_clock64();
       // XCC_ID in bits 0-2, HW_REG_HW_ID (register 4: wave, simd, cu, sh, se ...) above it
-      g_wtrace[3 * wid + 2] = (unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u) |
+      g_wtrace[WT_WORDS * wid + WT_HWID] = (unsigned long long)(__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u) |
                               ((unsigned long long)(unsigned)__builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 4) << 8);
     }
   }
@@ -2310,6 +2449,8 @@ __device__ __forceinline__ void search_refill_body(const SearchArgs& a, const ui
       }
     }
   }
+  if (kLab && FUSE) TDTK_PIN_V64(acc[0]);     // (lab: the clock below is read behind the sums)
+  wtrace_at(WT_SUMS);
   if (FUSE) {
     // wave64 reduction, then across the workgroup's waves through LDS: one row of ACC_TOTAL per workgroup
     constexpr int NW = BLOCK / WAVE;
@@ -3054,7 +3195,9 @@ uint32_t search_fused_rows(size_t n, int side_by_side)
 // again and drops the array otherwise.
 bool search_cert_capable(const SearchArgs& a)
 {
-  if (kLab || !BUCKET_Q16 || pick_variant(a.n) != 20 || a.fuse != 3) return false;
+  // (the lab library runs its passes without certificates -- its tests compare variants of the walk -- unless a wave trace is
+  // asked for: the trace is of the product's passes)
+  if ((kLab && !lab_env("TDTK_WAVE_TRACE")) || !BUCKET_Q16 || pick_variant(a.n) != 20 || a.fuse != 3) return false;
   if (!(a.warm && a.tie > 0.0 && a.T.split != nullptr && a.T.q16 != nullptr)) return false;
   if (!(a.use_cost && a.cost != nullptr) || a.skip != nullptr || a.d2 != nullptr || a.side_by_side > 1) return false;
   int qpw;
@@ -3077,10 +3220,20 @@ static void launch_refill128(SearchArgs& a, hipStream_t s)
   // cost coherence.  Non-temporal loads / stores for the query and result streams were measured too: no change in
   // misses or time.  (gpurun_out/r2n..r2r, tools/nt_probe.sh)
   // Neither do they pay beside other passes (84 link passes on 3 streams: 13.6 -> 13.2 ms without).
+  int trace_idx = -1;
   {
     static std::atomic<int> launches{0};
-    static const int want = [] { const char* e = lab_env("TDTK_WAVE_TRACE"); return e ? atoi(e) : -1; }();
-    a.trace = (want >= 0 && launches.fetch_add(1) == want) ? 1 : 0;
+    // (a comma-separated list of launch indices: each of them is traced and printed behind its launch)
+    static const std::vector<int> want = [] {
+      std::vector<int> w;
+      for (const char* e = lab_env("TDTK_WAVE_TRACE"); e && *e; ) { w.push_back(atoi(e)); e = strchr(e, ','); if (e) ++e; }
+      return w;
+    }();
+    a.trace = 0;
+    if (!want.empty()) {
+      trace_idx = launches.fetch_add(1);
+      a.trace = std::find(want.begin(), want.end(), trace_idx) != want.end() ? 1 : 0;
+    }
   }
   a.pool_slab = 0; a.region = 0;
   const int pool_pct = (FUSE == 3) ? 0 : refill_pool_pct(a.n, a.side_by_side);
@@ -3126,10 +3279,16 @@ static void launch_refill128(SearchArgs& a, hipStream_t s)
   if (kLab && a.trace) {
     (void)hipStreamSynchronize(s);
     const uint32_t nw = std::min<uint32_t>(nb * 2u, WTRACE_MAX);
-    std::vector<unsigned long long> h(3 * (size_t)nw);
-    if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_wtrace), h.size() * sizeof(unsigned long long)) == hipSuccess)
-      for (uint32_t w = 0; w < nw; w++)
-        fprintf(stderr, "WTRACE %u %u %llu %llu %llu\n", w / 2u, w % 2u, h[3 * w + 2], h[3 * w], h[3 * w + 1]);
+    std::vector<unsigned long long> h(WT_WORDS * (size_t)nw);
+    if (hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_wtrace), h.size() * sizeof(unsigned long long)) == hipSuccess) {
+      // (workgroup, wave, XCD / HW_ID, entry, second-search pass left -- as ever --, then the ends of the other phases)
+      fprintf(stderr, "WTRACE_LAUNCH %d n %zu cert %d cert_use %d warm %d qpw %d\n", trace_idx, a.n, a.cert ? 1 : 0, a.cert ? a.cert_use : 0, a.warm, a.qpw);
+      for (uint32_t w = 0; w < nw; w++) {
+        const unsigned long long* t = &h[WT_WORDS * (size_t)w];
+        fprintf(stderr, "WTRACE %u %u %llu %llu %llu %llu %llu %llu %llu %llu\n", w / 2u, w % 2u, t[WT_HWID], t[WT_ENTRY], t[WT_REDO], t[WT_SWEEP],
+                t[WT_ORDER], t[WT_FIRST], t[WT_LOOP], t[WT_SUMS]);
+      }
+    }
   }
 }
 

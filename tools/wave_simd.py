@@ -2,7 +2,7 @@
 how many waves of the launch each SIMD / CU hosted, and when the waves of the fuller ones end"""
 import re, sys, collections
 import numpy as np
-pat = re.compile(r"^WTRACE (\d+) (\d+) (\d+) (\d+) (\d+)$")
+pat = re.compile(r"^WTRACE (\d+) (\d+) (\d+) (\d+) (\d+)(?: \d+)*$")   # (the ends of the inner phases follow: tools/cert_phases.py)
 rows = [list(map(int, m.groups())) for m in (pat.match(l.strip()) for l in sys.stdin) if m]
 a = np.array(rows, dtype=np.int64)
 t0 = a[:, 3].min(); span = a[:, 4].max() - t0

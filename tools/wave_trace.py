@@ -2,7 +2,7 @@
 waves of one k_search launch end, per XCD"""
 import re, sys
 import numpy as np
-pat = re.compile(r"^WTRACE (\d+) (\d+) (\d+) (\d+) (\d+)$")
+pat = re.compile(r"^WTRACE (\d+) (\d+) (\d+) (\d+) (\d+)(?: \d+)*$")   # (the ends of the inner phases follow: tools/cert_phases.py)
 rows = [list(map(int, m.groups())) for m in (pat.match(l.strip()) for l in sys.stdin) if m]
 a = np.array(rows, dtype=np.int64)
 if len(a) == 0:
