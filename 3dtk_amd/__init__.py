@@ -23,7 +23,7 @@ from ._capi import (TdtkError, lib, build_extension, device_count, version, Pair
 from .slam6d import (KDtree, Scan, icp6Dminimizer, icp6D_QUAT, icp6D_SVD, icp6D_APX,  # noqa: F401
                      icp6D_ORTHO, icp6D_DUAL, icp6D_HELIX, icp6D_LUMEULER, icp6D_LUMQUAT, icp6D_QUAT_SCALE,
                      icp6D_NAPX, icp6D, Graph, lum6DEuler, lum6DQuat, ghelix6DQ2, gapx6D, QuatToMatrix4, Matrix4ToQuat, M4inv, MMult, M4identity,
-                     EulerToMatrix4, Matrix4ToEuler, host_tree_layout, calculateNormalsApxKNN, calculateNormalsKNN, calculateNormalsRange, calculateNormalsKNNRange, calculateNormalsAdaptiveKNN,
+                     EulerToMatrix4, Matrix4ToEuler, host_tree_layout, host_tree_levels, calculateNormalsApxKNN, calculateNormalsKNN, calculateNormalsRange, calculateNormalsKNNRange, calculateNormalsAdaptiveKNN,
                      calculateNormalsAdaptiveApxKNN, calculateNormalsIndexedKNN, flipNormals, flipNormalsUp, MetaScan, read_uos, read_pose,
                      openDirectory, closeDirectory, saveFrames, matchGraph6Dautomatic, calcReducedPoints,
                      computeGraph6Dautomatic, matchGraph6Dautomatic_clpairs, prepare_scans, loopSlam6D, elch6Deuler, elch6Dquat, elch6DunitQuat, elch6Dslerp,

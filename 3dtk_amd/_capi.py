@@ -21,6 +21,7 @@ WANT_APX, WANT_NAPX, WANT_LUM, WANT_GAPX, WANT_MOM2 = 1, 2, 4, 8, 16
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _u64p = C.POINTER(C.c_uint64)
+_u32p = C.POINTER(C.c_uint32)
 
 
 class TdtkError(RuntimeError):
@@ -60,7 +61,7 @@ class IcpResult(C.Structure):
 # every symbol include/tdtk_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "tdtk_last_error", "tdtk_device_count", "tdtk_pool_trim", "tdtk_build_respeculated", "tdtk_version", "tdtk_tree_create", "tdtk_tree_create_from_scan", "tdtk_tree_create_from_scans", "tdtk_scan_mark_original", "tdtk_scan_download_original", "tdtk_tree_destroy",
-    "tdtk_tree_get_info", "tdtk_tree_verify", "tdtk_find_closest", "tdtk_find_closest_dev", "tdtk_find_closest_along_dir",
+    "tdtk_tree_get_info", "tdtk_tree_verify", "tdtk_tree_build_path", "tdtk_find_closest", "tdtk_find_closest_dev", "tdtk_find_closest_along_dir",
     "tdtk_knn_search", "tdtk_fixed_range_search", "tdtk_normals_knn", "tdtk_normals_range",
     "tdtk_normals_adaptive_knn", "tdtk_normals_adaptive_apx_knn", "tdtk_knn_range_search", "tdtk_normals_knn_range",
     "tdtk_fixed_range_search_along_dir", "tdtk_fixed_range_search_between", "tdtk_aabb_search", "tdtk_segment_search_all",
@@ -75,7 +76,7 @@ EXPORTS = [
     "tdtk_graph_iteration", "tdtk_elch_graph_balancer", "tdtk_pair_sums_merge", "tdtk_graph_links",
     "tdtk_last_timings", "tdtk_kernel_timing", "tdtk_visit_counting", "tdtk_visit_counters", "tdtk_skip_counters", "tdtk_measure_bandwidth",
     "tdtk_icp_index_hashes", "tdtk_icp_last_hashes",
-    "tdtk_host_tree_layout", "tdtk_host_m4inv", "tdtk_host_mmult",
+    "tdtk_host_tree_layout", "tdtk_host_tree_levels", "tdtk_host_m4inv", "tdtk_host_mmult",
     "tdtk_host_euler_to_matrix4", "tdtk_host_matrix4_to_euler", "tdtk_host_quat_to_matrix4", "tdtk_host_matrix4_to_quat",
     "tdtk_io_read_uos", "tdtk_io_free", "tdtk_io_read_pose", "tdtk_io_write_frames",
 ]
@@ -148,6 +149,7 @@ def lib():
     L.tdtk_tree_destroy.restype = None
     L.tdtk_tree_get_info.argtypes = [C.c_void_p, C.POINTER(TreeInfo)]
     L.tdtk_tree_verify.argtypes = [C.c_void_p, _u64p]
+    L.tdtk_tree_build_path.argtypes = [C.c_void_p, _u32p]
     L.tdtk_find_closest.argtypes = [C.c_void_p, _dp, C.c_size_t, C.c_double, _ip, _dp]
     L.tdtk_find_closest_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p,
                                         C.c_void_p, C.c_int, C.c_void_p]
@@ -221,6 +223,7 @@ def lib():
     L.tdtk_icp_index_hashes.argtypes = [C.c_int]
     L.tdtk_icp_last_hashes.argtypes = [_u64p, C.c_int, C.POINTER(C.c_int)]
     L.tdtk_host_tree_layout.argtypes = [_dp, C.c_size_t, C.c_int, _ip, _u64p]
+    L.tdtk_host_tree_levels.argtypes = [_dp, C.c_size_t, C.c_int, C.c_int, _u32p, _u32p, C.POINTER(C.c_int)]
     L.tdtk_host_m4inv.argtypes = [_dp, _dp]
     L.tdtk_host_mmult.argtypes = [_dp, _dp, _dp]
     L.tdtk_host_mmult.restype = None

@@ -231,6 +231,7 @@ struct tdtk_tree {
   size_t Mp = 0;   // slots of d_pts: M, or 4 * groups once the buckets are padded to whole groups (tree_pad_buckets)
   double bbmin[3], bbmax[3], centre[3];
   tdtk_tree_info info{};
+  uint32_t build_path[12] = {0xFFFFFFFFu};   // tdtk_tree_build_path: what the device build decided (BuildPath); as it stands: no device build
   tdtk_tree() = default;
   tdtk_tree(const tdtk_tree&) = delete;
   tdtk_tree& operator=(const tdtk_tree&) = delete;

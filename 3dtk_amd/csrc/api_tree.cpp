@@ -62,6 +62,7 @@ int tree_from_device_points(Ctx* c, tdtk_tree* t, size_t M, int bucket_size, dou
   t->dev.cb = (uint32_t)r.cb;
   t->info.n_internal = r.n_internal; t->info.n_leaves = r.n_leaves;
   t->info.max_depth = r.max_depth; t->info.max_leaf_points = r.max_leaf;
+  std::memcpy(t->build_path, &r.path, sizeof t->build_path);
   t->info.build_ms = now_ms() - t1;
   c->last_build_ms = t->info.build_ms;
   return TDTK_OK;
@@ -321,6 +322,14 @@ int tdtk_tree_get_info(const tdtk_tree* t, tdtk_tree_info* info)
   return TDTK_OK;
 }
 
+// ---- diagnostics: which way through the hand-over decisions did the build of this tree take? -----
+int tdtk_tree_build_path(const tdtk_tree* t, uint32_t out[12])
+{
+  if (!t || !out) { set_error("NULL argument"); return TDTK_EINVAL; }
+  std::memcpy(out, t->build_path, sizeof t->build_path);
+  return TDTK_OK;
+}
+
 // ---- diagnostics: is the resident tree bit-identical to the host builder's? ----------------------
 int tdtk_tree_verify(const tdtk_tree* t, uint64_t mismatches[4])
 {
@@ -470,6 +479,44 @@ int tdtk_host_tree_layout(const double* xyz, size_t M, int bucket_size, int32_t*
   if (perm_out)
     for (size_t k = 0; k < M; k++) perm_out[k] = H.pts[k].orig;
   if (stats) { stats[0] = H.n_internal; stats[1] = H.n_leaves; stats[2] = H.max_depth; stats[3] = H.max_leaf_points; }
+  return TDTK_OK;
+}
+
+// The level profile of the host builder's tree: per depth how many nodes (internal and buckets) it has and how many points
+// the largest of them holds -- what the device build's looks see (k_fin_maxn) when its tree is the host builder's.
+// nseg / maxn hold `cap` entries (deeper levels are counted in *levels only).
+int tdtk_host_tree_levels(const double* xyz, size_t M, int bucket_size, int cap, uint32_t* nseg, uint32_t* maxn, int* levels)
+{
+  if (!nseg || !maxn || !levels || cap < 0) { set_error("NULL argument"); return TDTK_EINVAL; }
+  HostTree H;
+  std::string err;
+  if (!build_tree(xyz, M, bucket_size, H, err)) { set_error(err); return TDTK_EINVAL; }
+  const uint32_t cmask = (H.cb >= 32) ? 0xFFFFFFFFu : ((1u << H.cb) - 1u);
+  auto bucket_points = [&](uint32_t ref) -> uint32_t {
+    return H.table_mode ? (uint32_t)H.leaf_tab[ref & REF_VAL].count : ((ref & REF_VAL) & cmask);
+  };
+  const size_t n = H.nodes.size();
+  // subtree sizes bottom-up: in breadth-first order a node's children come behind it
+  std::vector<uint32_t> size(n), depth(n);
+  auto points_of = [&](uint32_t ref) -> uint32_t { return (ref & REF_LEAF) ? bucket_points(ref) : size[ref & REF_VAL]; };
+  for (size_t i = n; i-- > 0;) size[i] = points_of(H.nodes[i].c1) + points_of(H.nodes[i].c2);
+  std::fill(nseg, nseg + cap, 0u);
+  std::fill(maxn, maxn + cap, 0u);
+  uint32_t deepest = 0;
+  auto count = [&](uint32_t d, uint32_t points) {
+    deepest = std::max(deepest, d);
+    if (d < (uint32_t)cap) { nseg[d]++; maxn[d] = std::max(maxn[d], points); }
+  };
+  // depths top-down
+  count(0u, points_of(H.root_ref));
+  for (size_t i = 0; i < n; i++) {
+    if (i == 0) depth[0] = 0u;
+    for (uint32_t ref : {H.nodes[i].c1, H.nodes[i].c2}) {
+      count(depth[i] + 1u, points_of(ref));
+      if (!(ref & REF_LEAF)) depth[ref & REF_VAL] = depth[i] + 1u;
+    }
+  }
+  *levels = (int)deepest + 1;
   return TDTK_OK;
 }
 

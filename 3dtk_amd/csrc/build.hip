@@ -2011,6 +2011,7 @@ struct BuildRun {
     nblocks = cdiv(this->M, BIG_CH);
     SP.n = 0;
     batch = P.first_batch; fin_level = P.fin_level; chain_look = P.chain_look;
+    res.path.planned_level = P.fin_level; res.path.handed_level = 0xFFFFFFFFu; res.path.fin_cap = P.fin_cap;
   }
 };
 
@@ -2335,6 +2336,7 @@ static hipError_t size_up_hand_over(BuildRun& R)
   R.fin_nodes = h_max[1]; R.fin_maxn = h_max[0];
   if (h_max[0] > FIN_LDS && h_max[1] * 2u <= fin_cap && R.fin_level + 1u < 31u) {
     R.fin_level++;              // one more level by its own launches, then look again
+    R.res.path.more_levels++;
     R.known = h_max[1]; R.known_at = R.level;
     R.batch = 1;
   } else if (h_max[0] > FIN_LDS || h_max[1] > fin_cap) {
@@ -2344,6 +2346,7 @@ static hipError_t size_up_hand_over(BuildRun& R)
     // to the last bucket, eight levels more)
     R.fin_level = 0xFFFFFFFFu;
     R.fin_retry = R.no_finish == 0;
+    R.res.path.retried = R.fin_retry ? 1u : 0u;
     R.known = h_max[1]; R.known_at = R.level;
     R.batch = 2;
   }
@@ -2368,10 +2371,11 @@ static void enqueue_finishers(BuildRun& R, uint32_t tmax, BSeg* roots, FinTab* f
   // (by size only when the level has more subtrees than the chip has room for at once: below that the launches would
   //  run one after the other where one launch runs them side by side -- the dat/ scan 0.97 -> 1.13 ms)
   const bool staged = tmax > 1024u;
-  if (P.fin_wave && staged) { hipLaunchKernelGGL(k_fin_wave, dim3(cdiv(tmax, FW_WAVES)), dim3(WAVE * FW_WAVES), 0, s, fa); fa.n_lo = FW_CAP; }
-  if (P.fin_half && staged && R.fin_maxn > fa.n_lo) { hipLaunchKernelGGL(k_fin_subtrees_half, dim3(tmax), dim3(FIN_T), 0, s, fa); fa.n_lo = FIN_LDS_HALF; }
+  uint32_t& launched = R.res.path.finishers;
+  if (P.fin_wave && staged) { hipLaunchKernelGGL(k_fin_wave, dim3(cdiv(tmax, FW_WAVES)), dim3(WAVE * FW_WAVES), 0, s, fa); fa.n_lo = FW_CAP; launched |= 1u; }
+  if (P.fin_half && staged && R.fin_maxn > fa.n_lo) { hipLaunchKernelGGL(k_fin_subtrees_half, dim3(tmax), dim3(FIN_T), 0, s, fa); fa.n_lo = FIN_LDS_HALF; launched |= 2u; }
   fa.skip_big = 0u;
-  if (R.fin_maxn > fa.n_lo) hipLaunchKernelGGL(k_fin_subtrees, dim3(tmax), dim3(FIN_T), 0, s, fa);
+  if (R.fin_maxn > fa.n_lo) { hipLaunchKernelGGL(k_fin_subtrees, dim3(tmax), dim3(FIN_T), 0, s, fa); launched |= 4u; }
 }
 
 // Hand the level over: its nodes become the roots of subtrees.  As many workgroups as the level HAS nodes (counted by
@@ -2386,6 +2390,7 @@ static hipError_t hand_over(BuildRun& R)
   uint32_t* const small = R.small;
   BLevel* lvH = R.lvl + R.fin_level;
   const uint32_t tmax = R.fin_nodes ? R.fin_nodes : 1u;
+  R.res.path.handed_level = R.fin_level; R.res.path.fin_nodes = R.fin_nodes; R.res.path.fin_maxn = R.fin_maxn;
   BSeg* roots = A.fin_roots.in(arena);
   FinTab* ftab = A.fin_tab.in(arena);
   FinOff* foff = A.fin_off.in(arena);
@@ -2451,7 +2456,11 @@ static hipError_t look(BuildRun& R, bool* done)
   }
   if (R.fin_retry) {
     if (h_small[SM_FIN_MAXN] <= FIN_LDS && h_small[SM_FIN_NODES] <= P.fin_cap && level + FIN_LV + 3u < BUILD_MAX_LEVELS) { R.fin_level = level; R.fin_retry = false; }   // hand over now (run_levels)
-    else R.have_max = false;
+    else {
+      R.have_max = false;
+      if (h_small[SM_FIN_MAXN] > FIN_LDS) R.res.path.refused_size++;
+      if (h_small[SM_FIN_NODES] > P.fin_cap) R.res.path.refused_count++;
+    }
   }
   return hipSuccess;
 }
@@ -2562,7 +2571,13 @@ DevBuildResult device_build_tree(const double* d_xyz, size_t M_, int bucket, voi
   if (R.f_leaf) pool_free(R.f_leaf);
   if (R.pts) pool_free(R.pts);
   for (hipEvent_t x : R.lvl_ev) (void)hipEventDestroy(x);
-  if (R.redo_by_levels) return device_build_tree(d_xyz, M_, bucket, arena_, s, side, 1);   // a subtree deeper than the tables
+  if (R.redo_by_levels) {                                                                    // a subtree deeper than the tables
+    DevBuildResult again = device_build_tree(d_xyz, M_, bucket, arena_, s, side, 1);
+    BuildPath path = R.res.path;            // what the first attempt decided; the tree that is delivered was finished by levels
+    path.redone_by_levels = 1u; path.handed_level = again.path.handed_level; path.respeculated = again.path.respeculated;
+    again.path = path;
+    return again;
+  }
   if (R.spec && R.spec_suspect) {
     // a failed check, or a degenerate split on a tree cut at the plain sums: the in-order build decides what the input
     // really is.  (Anything else -- no memory, a failed launch -- is returned as it is: building twice would not help.)
@@ -2570,6 +2585,7 @@ DevBuildResult device_build_tree(const double* d_xyz, size_t M_, int bucket, voi
     (void)hipGetLastError();
     DevBuildResult again = device_build_tree(d_xyz, M_, bucket, arena_, s, nullptr, no_finish);
     again.respeculated = again.err == hipSuccess;     // tdtk_build_respeculated counts cuts that really were off, not bad inputs
+    again.path.respeculated = again.respeculated ? 1u : 0u;
     return again;
   }
   R.res.err = err;

@@ -246,6 +246,23 @@ hipError_t launch_scatter_idx(const int* kpos, const double* d2s, const int32_t*
                               const KdPoint* pts, size_t n, int32_t* idx_out, double* d2_out,
                               hipStream_t s);
 
+// What a device build decided about the hand-over to the subtree finishers (size_up_hand_over, look, hand_over,
+// enqueue_finishers in build.hip): bookkeeping of the host's decisions, twelve words, tdtk_tree_build_path's layout.
+struct BuildPath {
+  uint32_t planned_level;      // the level the plan hands over at; 0xFFFFFFFF: no finisher planned
+  uint32_t handed_level;       // the level the delivered tree was handed over at; 0xFFFFFFFF: finished by levels
+  uint32_t more_levels;        // times "one more level"
+  uint32_t retried;            // the finishers given up, on by levels with a look every second level
+  uint32_t refused_size;       // looks of the retry refused because the largest node exceeds FIN_LDS ...
+  uint32_t refused_count;      // ... because the level has more nodes than fin_cap (a look may count in both)
+  uint32_t fin_nodes, fin_maxn;   // at the hand-over: the level's nodes, the largest of them
+  uint32_t finishers;          // launches: bit 0 k_fin_wave, bit 1 k_fin_subtrees_half, bit 2 k_fin_subtrees
+  uint32_t redone_by_levels;   // a subtree deeper than the tables: every field but handed_level describes that first attempt
+  uint32_t respeculated;
+  uint32_t fin_cap;
+};
+static_assert(sizeof(BuildPath) == 12 * sizeof(uint32_t), "tdtk_tree_build_path hands out twelve words");
+
 struct DevBuildResult {
   hipError_t err;
   bool degenerate;
@@ -258,6 +275,7 @@ struct DevBuildResult {
   bool table_mode;
   uint32_t n_internal, n_leaves, max_depth, max_leaf;
   bool respeculated;   // the speculative build failed its check (or fell over) and the in-order build took its place
+  BuildPath path;
 };
 // level-synchronous construction of the reference's kd-tree on the device (build.hip)
 size_t device_build_arena_bytes(size_t M, bool with_background_chain = true);

@@ -149,6 +149,22 @@ def host_tree_layout(xyz, bucketSize=20):
     return perm, dict(internal=st[0], leaves=st[1], depth=st[2], max_leaf=st[3])
 
 
+def host_tree_levels(xyz, bucketSize=20, cap=4096):
+    """Host tree builder only (no device): per depth the number of nodes (internal and buckets) of the tree and the size
+    of the largest -- the level profile the device build's hand-over decisions depend on.  Returns (nseg, maxn), one entry
+    per level of the tree."""
+    xyz = f64(xyz).reshape(-1, 3)
+    nseg = np.zeros(cap, np.uint32)
+    maxn = np.zeros(cap, np.uint32)
+    levels = C.c_int(0)
+    u32p = C.POINTER(C.c_uint32)
+    check(lib().tdtk_host_tree_levels(dptr(xyz), len(xyz), int(bucketSize), int(cap), nseg.ctypes.data_as(u32p),
+                                      maxn.ctypes.data_as(u32p), C.byref(levels)))
+    if levels.value > cap:
+        return host_tree_levels(xyz, bucketSize, levels.value)
+    return nseg[:levels.value].copy(), maxn[:levels.value].copy()
+
+
 def _sums_dict(s):
     return dict(n_queries=int(s.n_queries), n=int(s.n), sum=s.sum,
                 centroid_m=np.array(s.centroid_m), centroid_d=np.array(s.centroid_d),
@@ -206,6 +222,20 @@ class KDtree:
         mm = (C.c_uint64 * 4)()
         check(lib().tdtk_tree_verify(self._h, mm))
         return [int(v) for v in mm]
+
+    BUILD_PATH_FIELDS = ("planned_level", "handed_level", "more_levels", "retried", "refused_size", "refused_count",
+                         "fin_nodes", "fin_maxn", "finishers", "redone_by_levels", "respeculated", "fin_cap")
+
+    def build_path(self):
+        """Which way the device build took through its hand-over to the subtree finishers (tdtk_tree_build_path);
+        planned_level / handed_level: None where the library reports none."""
+        w = (C.c_uint32 * 12)()
+        check(lib().tdtk_tree_build_path(self._h, w))
+        d = {k: int(v) for k, v in zip(self.BUILD_PATH_FIELDS, w)}
+        for k in ("planned_level", "handed_level"):
+            if d[k] == 0xFFFFFFFF:
+                d[k] = None
+        return d
 
     def FindClosest(self, p, maxdist2, threadNum=0):
         """kd.cc:78-87.  Returns the index of the closest point or None (reference: NULL)."""

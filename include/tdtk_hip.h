@@ -148,6 +148,17 @@ int tdtk_tree_get_info(const tdtk_tree* t, tdtk_tree_info* info);
 /* diagnostic: rebuild the tree with the host builder (kd_build.cpp; this is its only use -- trees are always built on
  * the device) and compare it with the resident one.  mismatches = {node records, node radii, points, structure}. */
 int tdtk_tree_verify(const tdtk_tree* t, uint64_t mismatches[4]);
+/* diagnostic: which way the device build of this tree took through its hand-over to the subtree finishers (host-side
+ * bookkeeping of build.hip's decisions; nothing forces a path).  out = { planned_level (the level the plan hands over at,
+ * 0xFFFFFFFF: none), handed_level (the level the delivered tree was handed over at, 0xFFFFFFFF: finished by levels),
+ * more_levels (times "one more level"), retried (0 / 1: finishers given up, on by levels with a look every second level),
+ * refused_size, refused_count (looks of the retry refused because the largest node exceeds a workgroup's capacity /
+ * because the level has more nodes than fin_cap; a look refused for both counts in both), fin_nodes, fin_maxn (the
+ * level's nodes and the largest of them at the hand-over), finishers (bit 0 the wave finisher, bit 1 the half-size,
+ * bit 2 the full-size workgroup finisher), redone_by_levels (the first attempt met a subtree deeper than the finishers'
+ * tables and the build was redone by levels: every field but handed_level describes that first attempt),
+ * respeculated, fin_cap (subtrees the tables hold) }.  A tree no device build made: all-ones in out[0], zeros elsewhere. */
+int tdtk_tree_build_path(const tdtk_tree* t, uint32_t out[12]);
 
 /* ---- batched KDtree::FindClosest (kd.cc:78-87; _FindClosest kdTreeImpl.h:345-383).
  * q [K][3] in the tree frame, host memory.  idx[k] = index into the xyz given to
@@ -614,6 +625,10 @@ int tdtk_io_write_frames(const char* path, const double* transMats, const int* t
  * MMult (globals.icc:762-785, 298-328) used for every query transform.                      */
 int tdtk_host_tree_layout(const double* xyz, size_t M, int bucket_size, int32_t* perm_out,
                           uint64_t stats[4]);
+/* tdtk_host_tree_levels: the level profile of the host builder's tree.  nseg[d] = nodes (internal and buckets) at depth
+ * d (the root: 0), maxn[d] = points of the largest of them, for d < cap; *levels = levels the tree has (may exceed cap). */
+int tdtk_host_tree_levels(const double* xyz, size_t M, int bucket_size, int cap, uint32_t* nseg, uint32_t* maxn,
+                          int* levels);
 int tdtk_host_m4inv(const double in[16], double out[16]);
 void tdtk_host_mmult(const double a[16], const double b[16], double out[16]);
 /* the pose conversions the pose updates use: EulerToMatrix4 / Matrix4ToEuler (globals.icc:501-576),

@@ -1092,7 +1092,9 @@ def test_device_tree_of_a_lopsided_cloud_is_handed_over_late(tdtk, orc, gpu, cas
     finisher sixteen levels later than a balanced tree's would be; round 4 launched 2^level workgroups and copied that many
     root records there -- a million, over the end of the build's arena: five wrong split values, 125 of 550 wrong neighbours
     and, inside a long process, a GPU memory fault.  Now: as many as the level has nodes.  Record for record the host
-    builder's tree, the oracle's neighbours, and a tree built right after it in the same context is sound too."""
+    builder's tree, the oracle's neighbours, and a tree built right after it in the same context is sound too.
+    The path of the two builds (KDtree.build_path()): planned at level 4 (20 000 / 30 000 points), "one more level" 16 /
+    14 times -- the level doubles from 16 nodes and stays under fin_cap = 1024 --, never the retry."""
     if case == "fixture":
         d = np.load(os.path.join(HERE, "golden", "fuzz_case_dynamic_range_20000.npz"))
         p, q, bucket, md2 = d["p"], d["q"], int(d["bucket"]), float(d["md2"])
@@ -1103,6 +1105,9 @@ def test_device_tree_of_a_lopsided_cloud_is_handed_over_late(tdtk, orc, gpu, cas
         bucket, md2 = 20, 1e18
     kd, T = tdtk.KDtree(p, bucket), orc.Tree(p, bucket)
     assert kd.verify() == [0, 0, 0, 0]
+    path = kd.build_path()
+    assert (path["more_levels"], path["retried"]) == ({"fixture": 16, "generated": 14}[case], 0)
+    assert path["handed_level"] == path["planned_level"] + path["more_levels"] and path["redone_by_levels"] == 0
     gi, gd = kd.FindClosestBatch(q, md2)
     oi, od = T.find_closest(q, md2)
     assert np.array_equal(gi, oi) and np.array_equal(gd, od)
