@@ -29,3 +29,4 @@ from .slam6d import (KDtree, Scan, icp6Dminimizer, icp6D_QUAT, icp6D_SVD, icp6D_
                      computeGraph6Dautomatic, matchGraph6Dautomatic_clpairs, prepare_scans, loopSlam6D, elch6Deuler, elch6Dquat, elch6DunitQuat, elch6Dslerp,
                      graph_balancer)
 from .collision import read_trajectory, handle_pointcloud, calculate_collidingdist, calculate_collidingdist2, segment_colliding  # noqa: F401
+from .peopleremover import walk_voxels, peopleremover, synthetic_room  # noqa: F401  (the function, not the module, is the name)

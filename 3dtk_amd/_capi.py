@@ -66,7 +66,7 @@ EXPORTS = [
     "tdtk_normals_adaptive_knn", "tdtk_normals_adaptive_apx_knn", "tdtk_knn_range_search", "tdtk_normals_knn_range",
     "tdtk_fixed_range_search_along_dir", "tdtk_fixed_range_search_between", "tdtk_aabb_search", "tdtk_segment_search_all",
     "tdtk_segment_search_nearest", "tdtk_collision_mark", "tdtk_collision_depth_closest", "tdtk_collision_depth_axis",
-    "tdtk_cluster_radius", "tdtk_cluster_grid_cap",
+    "tdtk_cluster_radius", "tdtk_cluster_grid_cap", "tdtk_voxel_walk", "tdtk_peopleremover", "tdtk_peopleremover_timings",
     "tdtk_get_pt_pairs", "tdtk_scan_create", "tdtk_scan_destroy", "tdtk_scan_size",
     "tdtk_scan_transform", "tdtk_scan_download", "tdtk_scan_pairs", "tdtk_align", "tdtk_icp_match", "tdtk_icp_match_rnd",
     "tdtk_lum_link", "tdtk_lum_links", "tdtk_links_pair_sums", "tdtk_lum_update_poses", "tdtk_lum_assemble_solve", "tdtk_point_point_error",
@@ -168,6 +168,10 @@ def lib():
     L.tdtk_cluster_radius.argtypes = [C.c_void_p, C.c_double, C.c_void_p, _dp, C.c_double, C.c_uint32, _ip, _u64p, C.c_void_p,
                                       C.c_void_p]
     L.tdtk_cluster_grid_cap.argtypes = [C.c_int]
+    L.tdtk_voxel_walk.argtypes = [C.c_int, _dp, _dp, C.c_size_t, C.c_double, _u64p, _ip, C.c_size_t, _u64p]
+    L.tdtk_peopleremover.argtypes = [C.c_int, _dp, _u64p, _dp, _dp, C.c_size_t, C.c_double, C.c_uint64, C.c_uint64, C.c_int,
+                                     C.POINTER(C.c_uint8), _ip, C.c_size_t, _u64p]
+    L.tdtk_peopleremover_timings.argtypes = [_dp]
     L.tdtk_normals_knn.argtypes = [_dp, C.c_size_t, C.c_int, _dp, C.c_int, C.c_int, _dp, _ip]
     L.tdtk_normals_range.argtypes = [_dp, C.c_size_t, C.c_double, _dp, C.c_int, C.c_int, _dp]
     L.tdtk_normals_knn_range.argtypes = [_dp, C.c_size_t, C.c_int, C.c_double, _dp, C.c_int, C.c_int, _dp, _ip, _ip]

@@ -285,6 +285,36 @@ int tdtk_cluster_radius(const tdtk_tree* t, double sqRad2, const uint8_t* subset
 /* The largest grid (workgroups) the link kernel of tdtk_cluster_radius may take, process-wide; 0 (the default): no cap of
  * its own.  A testing aid like tdtk_kernel_timing -- the labels do not depend on it.  Returns the previous setting. */
 int tdtk_cluster_grid_cap(int blocks);
+/* ---- the voxel grid of peopleremover (src/peopleremover/common.cc, peopleremover.cc).  A voxel is voxel_of_point
+ * (common.cc:48-54): py_div(p, voxel_size) per axis.  Voxel coordinates must fit 21 bits with a margin: every |x / voxel_size|
+ * of a point, origin or ray end has to stay below 2^20 - 4, otherwise TDTK_EUNSUP.  Non-finite coordinates and a voxel_size
+ * that is not finite and > 0 give TDTK_EINVAL.  Nothing is written to the result arrays of a refused call.
+ *
+ * walk_voxels (common.cc:112-306) for m rays starts[i] -> ends[i] (both [m][3], host memory): the ordered list of voxels the
+ * reference hands to its visitor, every call counted, repeats included, under a visitor that always continues.  CSR lists
+ * under tdtk_fixed_range_search's contract: offsets [m+1] and *total are always filled; cap < *total (or voxels == NULL with
+ * *total > 0) writes nothing else and returns TDTK_EINVAL: call again with cap >= *total.  voxels [cap][3].  A zero-length
+ * ray has an empty list.  More than 2^32 - 1 visits in one call: TDTK_EUNSUP.                                            */
+int tdtk_voxel_walk(int device, const double* starts, const double* ends, size_t m, double voxel_size, uint64_t* offsets,
+                    int32_t* voxels, size_t cap, uint64_t* total);
+/* peopleremover's main() between reading the scans and writing the partition (peopleremover.cc:176-545) with
+ * --maxrange-method none: occupancy (voxel -> set of scan ids), one ray from every scan's origin to every one of its points
+ * under `visitor` (common.cc:57-103; window [current - diff, current + diff]), the cluster filter when cluster_size > 1
+ * (26-connected components of the free voxels, fewer than cluster_size voxels: removed), the half-free voxels when subvoxel
+ * != 0 (distance 2), and the split.  xyz [n][3] the points of all scans in the global frame, scan s owning rows
+ * scan_offsets[s] .. scan_offsets[s+1] (S + 1 entries, from 0, not decreasing, n = scan_offsets[S] > 0); origins [S][3];
+ * ray_ends NULL, or [n][3] where each ray stops instead of at its point (shortened rays: the caller's maxranges).
+ * dynamic [n]: 1 where the reference writes the point to the dynamic file, else 0.  info [5]: occupied voxels, freed voxels,
+ * free voxels after clustering, half-free voxels -- the four numbers the reference prints -- and the voxel visits of all rays.
+ * free_voxels (nullable) [cap][3]: the free voxels after clustering in std::set order (x, then y, then z); cap < info[2]
+ * returns TDTK_EINVAL with dynamic and info written.  The reference's defaults: voxel_size 10, diff 0, cluster_size 5,
+ * subvoxel 1 (common.cc:432-435).  Not covered: --maxrange-method normals, --reduce, fuzz.                            */
+int tdtk_peopleremover(int device, const double* xyz, const uint64_t* scan_offsets, const double* origins,
+                       const double* ray_ends, size_t S, double voxel_size, uint64_t diff, uint64_t cluster_size, int subvoxel,
+                       uint8_t* dynamic, int32_t* free_voxels, size_t cap, uint64_t* info);
+/* HIP-event times of the calling thread's last tdtk_peopleremover, ms: occupancy build, walk, cluster + half-free +
+ * classification, and first upload to last download.                                                                 */
+int tdtk_peopleremover_timings(double* ms4);
 /* calculateNormalsKNN (normals.cc:442-516; calculateNormal :518-558): a KDtree(points, bucket) and, for every point, its
  * k nearest neighbours (itself included), their mean and covariance, the eigenvector of the smallest eigenvalue
  * (newmat EigenValues), oriented so that n . (p - rPos) >= 0, normalised.  normals_out [n][3] in point order (the

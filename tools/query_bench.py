@@ -35,6 +35,14 @@ a union-find over its lists on the host (numpy, the fixture generator's), (4) th
 over all points on ONE host thread, as segment_colliding's loop is serial (where oracle/_ref exists); --only-clusters runs
 nothing else.
 
+--only-peopleremover runs dynamic-object removal (tdtk_peopleremover) alone: a synthetic box room (600 units wide) scanned
+from 8 positions, 250 000 points each, with a cube that stands somewhere else in every scan (3dtk_amd.synthetic_room), at
+the reference's defaults (voxel 10, diff 0, cluster 5, subvoxel accuracy).  Warm, the minimum of --reps runs: the host call
+end to end, and from HIP events the occupancy build, the walk, cluster + half-free + classification, and upload to
+download; the voxel visits and visits per second of the walk; the walk again with every scan's points ordered by range
+(what divergent ray lengths inside a wave cost).  The reference's time for the same input comes from
+`python tests/golden/make_golden_peopleremover.py --time` on a machine that has the checkout (one host thread).
+
 Kernel times: run the same command under `rocprofv3 --kernel-trace --stats` (k_knn_reg, k_range_count / k_range_fill,
 k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest, k_knn_adaptive_reg / k_knn_adaptive_lds, k_ann_adaptive, k_knnr_reg / k_knnr_lds,
 k_collide_mark, k_collide_depth_axis)."""
@@ -347,6 +355,40 @@ def cluster_legs(tdtk, reps):
     return out
 
 
+def peopleremover_legs(tdtk, reps):
+    """tdtk_peopleremover on tests/golden/make_golden_peopleremover.py's BENCH workload"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("make_golden_peopleremover",
+                                                  os.path.join(ROOT, "tests", "golden", "make_golden_peopleremover.py"))
+    mg = importlib.util.module_from_spec(spec); spec.loader.exec_module(mg)
+    pr = importlib.import_module("3dtk_amd.peopleremover")
+    scans, org = tdtk.synthetic_room(mg.BENCH["n_scans"], mg.BENCH["points_per_scan"], seed=mg.BENCH["seed"])
+    out = {"peopleremover_scans": len(scans), "peopleremover_points": int(sum(len(s) for s in scans))}
+    stages = []
+
+    def run():
+        masks, counts = tdtk.peopleremover(scans, org)
+        stages.append(pr.last_timings())
+        return masks, counts
+    out["peopleremover_end_to_end"] = timed(run, reps)
+    masks, counts = run()
+    for k in ("build_ms", "walk_ms", "post_ms", "total_ms"):
+        out["peopleremover_" + k] = round(min(s[k] for s in stages[1:]), 3)           # (the first run is the warm-up)
+    out.update({"peopleremover_" + k: v for k, v in counts.items()})
+    out["peopleremover_dynamic_points"] = int(sum(int(m.sum()) for m in masks))
+    out["peopleremover_Mvisits_per_s"] = round(counts["visits"] / out["peopleremover_walk_ms"] / 1e3, 1)
+    # the same rays with every scan's points ordered by range: the lanes of a wave then walk rays of nearly equal length, so
+    # the difference to the walk above (random directions next to each other) is what divergence inside a wave costs
+    by_range = [s[np.argsort(np.linalg.norm(s - o, axis=1), kind="stable")] for s, o in zip(scans, org)]
+    stages.clear()
+    for _ in range(reps + 1):
+        _, c2 = tdtk.peopleremover(by_range, org)
+        stages.append(pr.last_timings())
+    assert c2 == counts
+    out["peopleremover_walk_ms_rays_by_range"] = round(min(s["walk_ms"] for s in stages[1:]), 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000000,10000000")
@@ -363,11 +405,16 @@ def main():
     ap.add_argument("--only-collision", action="store_true", help="those legs alone")
     ap.add_argument("--clusters", action="store_true", help="add the radius-clustering legs (1M points, two radii)")
     ap.add_argument("--only-clusters", action="store_true", help="those legs alone")
+    ap.add_argument("--only-peopleremover", action="store_true", help="dynamic-object removal on a synthetic room, alone")
     args = ap.parse_args()
     tdtk = importlib.import_module("3dtk_amd")
     if tdtk.device_count() < 1:
         raise SystemExit("no HIP device: the measurements need the MI355X")
     out = {"workload": "kdtree_queries", "reps": args.reps}
+    if args.only_peopleremover:
+        out.update(peopleremover_legs(tdtk, args.reps))
+        print(json.dumps(out))
+        return
     rng = np.random.default_rng(2024)
     rpos = [0.0, 0.0, 0.0]
     if args.segments or args.only_segments:
