@@ -116,7 +116,7 @@ struct Ctx {
   // (both are filled by copies enqueued on `stream` and read only behind a synchronisation of that stream that was made after
   //  the copy was enqueued: one of the build's looks at the device for the box, tree_finish's own hipStreamSynchronize for the
   //  groups -- device_build_tree may return with its last kernels still running, see build.hip "no_last_look")
-  static constexpr int PIN_BOX = 128;      // 6 doubles: the root bounding box (tree_from_device_points)
+  static constexpr int PIN_BOX = 128;      // 7 doubles: the root bounding box and the non-finite flag (tree_from_device_points)
   static constexpr int PIN_GROUPS = 140;   // 1 uint32: groups of the padded layout (tree_pad_buckets -> tree_finish)
   void* h_build = nullptr;  // 64 KB, pinned: the tree build's looks at the device (BuildSide::h_pin)
   void* h_stage = nullptr;  // pinned staging for descriptor tables of batched launches (grows on demand)

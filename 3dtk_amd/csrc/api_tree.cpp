@@ -21,10 +21,18 @@ int tree_from_device_points(Ctx* c, tdtk_tree* t, size_t M, int bucket_size, dou
   int rc;
   if ((rc = c->ws[WS_BOX].ensure(bbox_temp_bytes() + 8 * sizeof(double)))) return rc;
   double* d_box = c->ws[WS_BOX].as<double>();
-  // root bounding box (binning of unsorted query batches, accumulation shift): min / max on the device
-  // (read back behind the build: the build's own looks at the device are the next synchronisation points)
-  HIPCHK(launch_bbox(c->ws[WS_TMPA].as<double>(), M, d_box + 8, d_box, c->stream));
-  HIPCHK(hipMemcpyAsync(c->h_pin + Ctx::PIN_BOX, d_box, 6 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  // root bounding box (binning of unsorted query batches, accumulation shift): min / max on the device, and behind them
+  // whether a coordinate is a NaN or an infinity.  The build refuses such a cloud only where a split leaves a side empty
+  // (children_of, build.hip): a cloud that never splits (M <= bucket) or a single +inf (the mean is +inf, every other point
+  // goes left) would get a tree, and a list of the k-nearest walks over it could mix NaN and finite distances, which their
+  // "first nr slots" extraction excludes.  So the answer is read here, in front of the build, as kd_build.cpp does
+  HIPCHK(launch_bbox(c->ws[WS_TMPA].as<double>(), M, d_box + 8, d_box, c->stream, d_box + 6));
+  HIPCHK(hipMemcpyAsync(c->h_pin + Ctx::PIN_BOX, d_box, 7 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (c->h_pin[Ctx::PIN_BOX + 6] != 0.0) {
+    set_error("degenerate split (non-finite coordinates?)");
+    return TDTK_EINVAL;
+  }
   const double t1 = now_ms();
   t->info.upload_ms = t1 - t0;
   const bool alone = g_ctx_live.load() <= 2;
@@ -55,7 +63,7 @@ int tree_from_device_points(Ctx* c, tdtk_tree* t, size_t M, int bucket_size, dou
                            : std::string("device tree build: ") + hipGetErrorString(r.err));
     return r.degenerate ? TDTK_EINVAL : TDTK_EDEVICE;
   }
-  for (int a = 0; a < 3; a++) { t->bbmin[a] = c->h_pin[Ctx::PIN_BOX + a]; t->bbmax[a] = c->h_pin[Ctx::PIN_BOX + 3 + a]; }   // (the copy was enqueued in front of the build, and every path through device_build_tree synchronises c->stream at least once behind it: a look at the level loop's counters, or its last one)
+  for (int a = 0; a < 3; a++) { t->bbmin[a] = c->h_pin[Ctx::PIN_BOX + a]; t->bbmax[a] = c->h_pin[Ctx::PIN_BOX + 3 + a]; }
   t->d_nodes = r.nodes; t->d_r = r.node_r; t->d_pts = r.pts;
   t->d_leaf = r.leaf_tab;   // non-null only in table mode
   t->dev.root_ref = r.root_ref;

@@ -342,7 +342,8 @@ struct OctRoot {
   int depth;     // halvings until size <= voxelSize (>= 1)
 };
 size_t bbox_temp_bytes();
-hipError_t launch_bbox(const double* d_xyz, size_t n, double* d_partial, double* d_box, hipStream_t s);
+hipError_t launch_bbox(const double* d_xyz, size_t n, double* d_partial, double* d_box, hipStream_t s,
+                       double* d_nonfinite = nullptr);
 size_t oct_sort_temp_bytes(size_t n);
 hipError_t launch_oct_keys_sorted(const double* d_xyz, size_t n, const OctRoot& R, uint64_t* keys_a,
                                   uint64_t* keys_b, void* tmp, size_t tmp_bytes, hipStream_t s);

@@ -44,19 +44,25 @@ __device__ __forceinline__ double wave_max(double v)
   return v;
 }
 
-// partial[b][6] = lo xyz, hi xyz of the block's grid-stride slice
+// partial[b][6] = lo xyz, hi xyz of the block's grid-stride slice.  FLAG: *nonfinite (zeroed by the caller) becomes 1.0 when
+// a coordinate is a NaN or an infinity -- the comparisons below drop a NaN unless it is the first point's, so the box alone
+// does not show it.  Every lane that sees one stores the same value: a plain store, no reduction
+template <bool FLAG>
 __global__ __launch_bounds__(256) void k_bbox_partial(const double* __restrict__ xyz, size_t n,
-                                                      double* __restrict__ partial)
+                                                      double* __restrict__ partial, double* __restrict__ nonfinite)
 {
   __shared__ double sh[4][6];
   double lo[3] = {xyz[0], xyz[1], xyz[2]}, hi[3] = {xyz[0], xyz[1], xyz[2]};
   const size_t stride = (size_t)gridDim.x * blockDim.x;
+  bool bad = false;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
     for (int a = 0; a < 3; a++) {
       const double v = xyz[3 * i + a];
       lo[a] = (v < lo[a]) ? v : lo[a];
       hi[a] = (v > hi[a]) ? v : hi[a];
+      if (FLAG) bad |= !(fabs(v) <= 1.7976931348623157e308);
     }
+  if (FLAG && bad) *nonfinite = 1.0;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   for (int a = 0; a < 3; a++) {
     const double mn = wave_min(lo[a]), mx = wave_max(hi[a]);
@@ -89,12 +95,19 @@ __global__ __launch_bounds__(64) void k_bbox_final(const double* __restrict__ pa
 
 size_t bbox_temp_bytes() { return (size_t)BBOX_BLOCKS * 6 * sizeof(double); }
 
-// box[0..2] = min, box[3..5] = max of xyz[n][3] (device memory); n >= 1
-hipError_t launch_bbox(const double* d_xyz, size_t n, double* d_partial, double* d_box, hipStream_t s)
+// box[0..2] = min, box[3..5] = max of xyz[n][3] (device memory); n >= 1.  d_nonfinite (nullable): one double, 1.0 when a
+// coordinate is a NaN or an infinity, else 0.0
+hipError_t launch_bbox(const double* d_xyz, size_t n, double* d_partial, double* d_box, hipStream_t s, double* d_nonfinite)
 {
   size_t nb = (n + 255) / 256;
   if (nb > (size_t)BBOX_BLOCKS) nb = BBOX_BLOCKS;
-  hipLaunchKernelGGL(k_bbox_partial, dim3((uint32_t)nb), dim3(256), 0, s, d_xyz, n, d_partial);
+  if (d_nonfinite) {
+    const hipError_t e = hipMemsetAsync(d_nonfinite, 0, sizeof(double), s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_bbox_partial<true>, dim3((uint32_t)nb), dim3(256), 0, s, d_xyz, n, d_partial, d_nonfinite);
+  } else {
+    hipLaunchKernelGGL(k_bbox_partial<false>, dim3((uint32_t)nb), dim3(256), 0, s, d_xyz, n, d_partial, (double*)nullptr);
+  }
   hipLaunchKernelGGL(k_bbox_final, dim3(1), dim3(64), 0, s, d_partial, (int)nb, d_box);
   return hipGetLastError();
 }

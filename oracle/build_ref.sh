@@ -49,3 +49,13 @@ g++ $F $INC -c "$HERE/ref_driver.cc" -o "$OUT/obj/ref_driver.o"
 g++ $F $INC -I"$ANN/include" -c "$HERE/ref_ann_driver.cc" -o "$OUT/obj/ref_ann_driver.o"
 g++ -shared -fopenmp -o "$OUT/libref3dtk.so" "$OUT"/obj/*.o
 echo "built $OUT/libref3dtk.so"
+# libref_kd.so: the reference's kd.cc (KDtree, pointer flavour: kNearestRangeSearch) behind ref_kd_driver.cc.  A library of
+# its own with objects of its own (obj_kd/, outside the glob above): closed under --no-undefined, it shares nothing with
+# libref3dtk.so.  tests/golden/make_golden_knn_range.py (RefKD) loads it.
+mkdir -p "$OUT/obj_kd"
+if [ ! -f "$OUT/obj_kd/kd.o" ] || [ "$REF/src/slam6d/kd.cc" -nt "$OUT/obj_kd/kd.o" ]; then
+  g++ $F $INC -c "$REF/src/slam6d/kd.cc" -o "$OUT/obj_kd/kd.o"
+fi
+g++ $F $INC -c "$HERE/ref_kd_driver.cc" -o "$OUT/obj_kd/ref_kd_driver.o"
+g++ -shared -fopenmp -Wl,--no-undefined -o "$OUT/libref_kd.so" "$OUT/obj_kd/kd.o" "$OUT/obj_kd/ref_kd_driver.o"
+echo "built $OUT/libref_kd.so"

@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE ONLY: ctypes faces of the CPU oracle (oracle/liboracle.so,
 built from oracle/oracle.c) and of the reference's own translation units
-(oracle/_ref/libref3dtk.so, built by oracle/build_ref.sh where /root/reference
+(oracle/_ref/libref3dtk.so and libref_kd.so, built by oracle/build_ref.sh where /root/reference
 exists).  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg
 import this module; the product package never does.
 """
@@ -34,9 +34,10 @@ def build(force=False):
         subprocess.check_call(["make", "-C", _HERE, "liboracle.so"], stdout=subprocess.DEVNULL)
     ref = os.environ.get("TDTK_REF", "/root/reference")
     refso = os.path.join(_HERE, "_ref", "libref3dtk.so")
+    kdso = os.path.join(_HERE, "_ref", "libref_kd.so")
     if os.path.isdir(os.path.join(ref, "src", "slam6d")):
-        drv = max(os.path.getmtime(os.path.join(_HERE, f)) for f in ("ref_driver.cc", "ref_ann_driver.cc", "build_ref.sh"))
-        if force or not os.path.exists(refso) or os.path.getmtime(refso) < drv:
+        drv = max(os.path.getmtime(os.path.join(_HERE, f)) for f in ("ref_driver.cc", "ref_ann_driver.cc", "ref_kd_driver.cc", "build_ref.sh"))
+        if force or not os.path.exists(refso) or not os.path.exists(kdso) or min(os.path.getmtime(refso), os.path.getmtime(kdso)) < drv:
             subprocess.check_call([os.path.join(_HERE, "build_ref.sh"), ref], stdout=subprocess.DEVNULL)
 
 

@@ -3,10 +3,9 @@ reference's own compiled kd.cc, on the clouds of k8_kdtree_queries.npz, and the 
 
     python tests/golden/make_golden_knn_range.py        (needs the reference checkout: $TDTK_REF, default /root/reference)
 
-kd.cc is compiled as it is, with the flags of oracle/build_ref.sh, next to a driver of our own (DRIVER below), into a
-temporary directory and loaded through ctypes; nothing of it reaches the repository.  kd.o's only undefined reference-side
-symbol is SearchTree's typeinfo, which the compiler emits with the first out-of-line virtual of the class: the driver gives
-the three of them (searchTree.h:83-112) empty bodies.
+kd.cc is compiled as it is, with the flags of oracle/build_ref.sh, next to a driver of our own (oracle/ref_kd_driver.cc) and
+loaded through ctypes: oracle/_ref/libref_kd.so where build_ref.sh made it, else a build into a temporary directory; nothing
+of it reaches the repository.
 
 The reference returns coordinates (std::vector<Point>), not indices.  Every returned point is bit-equal to a point of the
 cloud (asserted), so a row is stored losslessly as the smallest cloud index with those coordinates: coords = pts[rep].  To
@@ -43,59 +42,17 @@ KOFF = np.concatenate([[0], np.cumsum(KS)])     # row of KS[j]: columns KOFF[j] 
 # the flags of oracle/build_ref.sh
 FLAGS = "-std=c++17 -O3 -fPIC -fopenmp -DOPENMP -DOPENMP_NUM_THREADS=8 -DMAX_OPENMP_NUM_THREADS=512 -w".split()
 
-DRIVER = r"""
-#include <vector>
-#include "slam6d/kd.h"
-
-// SearchTree's three out-of-line virtuals (searchTree.h:83-112): with them the class's vtable and typeinfo are emitted here
-double* SearchTree::FindClosestAlongDir(double*, double*, double, int) const { return 0; }
-void SearchTree::getPtPairs(std::vector<PtPair>*, double*, double* const*, unsigned int, unsigned int, int, int, double,
-                            double&, double*, double*) {}
-void SearchTree::getPtPairs(std::vector<PtPair>*, double*, const DataXYZ&, const DataNormal&, unsigned int, unsigned int, int,
-                            int, double, double&, double*, double*, PairingMode) {}
-
-struct Handle {
-  std::vector<double> xyz;
-  std::vector<double*> ptrs;
-  KDtree* tree;
-};
-
-extern "C" void* kr_create(const double* xyz, int n, int bucket)
-{
-  Handle* h = new Handle;
-  h->xyz.assign(xyz, xyz + 3 * (size_t)n);
-  h->ptrs.resize(n);
-  for (int i = 0; i < n; i++) h->ptrs[i] = &h->xyz[3 * (size_t)i];
-  h->tree = new KDtree(h->ptrs.data(), n, bucket);
-  return h;
-}
-
-extern "C" void kr_destroy(void* p)
-{
-  Handle* h = (Handle*)p;
-  delete h->tree;
-  delete h;
-}
-
-// out [nq][k][3] (untouched behind a row's entries), counts [nq]
-extern "C" void kr_search(void* p, const double* q, int nq, int k, double r2, double* out, int* counts)
-{
-  Handle* h = (Handle*)p;
-  for (int i = 0; i < nq; i++) {
-    double qq[3] = {q[3 * i], q[3 * i + 1], q[3 * i + 2]};
-    std::vector<Point> r = h->tree->kNearestRangeSearch(qq, k, r2, 0);
-    counts[i] = (int)r.size();
-    for (size_t j = 0; j < r.size(); j++) {
-      double* o = out + 3 * ((size_t)i * k + j);
-      o[0] = r[j].x; o[1] = r[j].y; o[2] = r[j].z;
-    }
-  }
-}
-"""
+DRIVER = os.path.join(_ROOT, "oracle", "ref_kd_driver.cc")     # the handle around KDtree and the loop over kNearestRangeSearch
+PREBUILT = os.path.join(_ROOT, "oracle", "_ref", "libref_kd.so")   # oracle/build_ref.sh's build of the same two files
 
 
 def have_ref():
     return os.path.isfile(os.path.join(REF, "src", "slam6d", "kd.cc"))
+
+
+def have_lib():
+    """the prebuilt library is there: what a GPU test asks, which never touches the checkout"""
+    return os.path.isfile(PREBUILT)
 
 
 _lib = None
@@ -103,18 +60,18 @@ _tmp = None
 
 
 def ref_lib():
-    """kd.cc + DRIVER, built into a temporary directory (removed at exit)"""
+    """kd.cc + DRIVER: oracle/_ref/libref_kd.so where it was built, else built into a temporary directory (removed at exit)"""
     global _lib, _tmp
     if _lib is None:
-        _tmp = tempfile.TemporaryDirectory(prefix="k12_ref_")
-        d = _tmp.name
-        with open(os.path.join(d, "driver.cc"), "w") as f:
-            f.write(DRIVER)
-        inc = ["-I" + os.path.join(REF, "include"), "-I" + os.path.join(REF, "3rdparty", "newmat", "newmat-10")]
-        subprocess.check_call(["g++"] + FLAGS + inc + ["-c", os.path.join(REF, "src", "slam6d", "kd.cc"), "-o", os.path.join(d, "kd.o")])
-        subprocess.check_call(["g++"] + FLAGS + inc + ["-c", os.path.join(d, "driver.cc"), "-o", os.path.join(d, "driver.o")])
-        so = os.path.join(d, "libkr.so")
-        subprocess.check_call(["g++", "-shared", "-fopenmp", "-Wl,--no-undefined", "-o", so, os.path.join(d, "kd.o"), os.path.join(d, "driver.o")])
+        so = PREBUILT
+        if not have_lib():
+            _tmp = tempfile.TemporaryDirectory(prefix="k12_ref_")
+            d = _tmp.name
+            inc = ["-I" + os.path.join(REF, "include"), "-I" + os.path.join(REF, "3rdparty", "newmat", "newmat-10")]
+            subprocess.check_call(["g++"] + FLAGS + inc + ["-c", os.path.join(REF, "src", "slam6d", "kd.cc"), "-o", os.path.join(d, "kd.o")])
+            subprocess.check_call(["g++"] + FLAGS + inc + ["-c", DRIVER, "-o", os.path.join(d, "driver.o")])
+            so = os.path.join(d, "libkr.so")
+            subprocess.check_call(["g++", "-shared", "-fopenmp", "-Wl,--no-undefined", "-o", so, os.path.join(d, "kd.o"), os.path.join(d, "driver.o")])
         _lib = C.CDLL(so)
         _lib.kr_create.restype = C.c_void_p
         _lib.kr_create.argtypes = [C.c_void_p, C.c_int, C.c_int]
