@@ -67,6 +67,8 @@ EXPORTS = [
     "tdtk_fixed_range_search_along_dir", "tdtk_fixed_range_search_between", "tdtk_aabb_search", "tdtk_segment_search_all",
     "tdtk_segment_search_nearest", "tdtk_collision_mark", "tdtk_collision_depth_closest", "tdtk_collision_depth_axis",
     "tdtk_cluster_radius", "tdtk_cluster_grid_cap", "tdtk_voxel_walk", "tdtk_peopleremover", "tdtk_peopleremover_timings",
+    "tdtk_forest_create", "tdtk_forest_create_from_points", "tdtk_forest_destroy", "tdtk_forest_insert", "tdtk_forest_last_insert", "tdtk_forest_remove", "tdtk_forest_info",
+    "tdtk_forest_collect", "tdtk_forest_find_closest", "tdtk_forest_knn", "tdtk_forest_fixed_range", "tdtk_forest_plan",
     "tdtk_get_pt_pairs", "tdtk_scan_create", "tdtk_scan_destroy", "tdtk_scan_size",
     "tdtk_scan_transform", "tdtk_scan_download", "tdtk_scan_pairs", "tdtk_align", "tdtk_icp_match", "tdtk_icp_match_rnd",
     "tdtk_lum_link", "tdtk_lum_links", "tdtk_links_pair_sums", "tdtk_lum_update_poses", "tdtk_lum_assemble_solve", "tdtk_point_point_error",
@@ -172,6 +174,20 @@ def lib():
     L.tdtk_peopleremover.argtypes = [C.c_int, _dp, _u64p, _dp, _dp, C.c_size_t, C.c_double, C.c_uint64, C.c_uint64, C.c_int,
                                      C.POINTER(C.c_uint8), _ip, C.c_size_t, _u64p]
     L.tdtk_peopleremover_timings.argtypes = [_dp]
+    L.tdtk_forest_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.tdtk_forest_create_from_points.argtypes = [_dp, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.tdtk_forest_destroy.argtypes = [C.c_void_p]
+    L.tdtk_forest_destroy.restype = None
+    L.tdtk_forest_insert.argtypes = [C.c_void_p, _dp, C.c_size_t, _ip]
+    L.tdtk_forest_remove.argtypes = [C.c_void_p, _dp, C.c_size_t, _ip]
+    L.tdtk_forest_last_insert.argtypes = [C.c_void_p, _dp]
+    L.tdtk_forest_info.argtypes = [C.c_void_p, C.POINTER(C.c_int), _u64p, _u64p, _u64p, _u32p]
+    L.tdtk_forest_collect.argtypes = [C.c_void_p, C.c_int, _ip, _dp, C.c_size_t, _u64p]
+    L.tdtk_forest_find_closest.argtypes = [C.c_void_p, _dp, C.c_size_t, C.c_double, _ip, _dp]
+    L.tdtk_forest_knn.argtypes = [C.c_void_p, _dp, C.c_size_t, C.c_int, _ip, _dp]
+    L.tdtk_forest_fixed_range.argtypes = [C.c_void_p, _dp, C.c_size_t, C.c_double, _u64p, _ip, _dp, C.c_size_t, _u64p]
+    L.tdtk_forest_plan.argtypes = [_u64p, C.c_int, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_int), _u64p,
+                                   C.POINTER(C.c_int64), C.c_size_t, C.POINTER(C.c_size_t), _u64p, _u64p]
     L.tdtk_normals_knn.argtypes = [_dp, C.c_size_t, C.c_int, _dp, C.c_int, C.c_int, _dp, _ip]
     L.tdtk_normals_range.argtypes = [_dp, C.c_size_t, C.c_double, _dp, C.c_int, C.c_int, _dp]
     L.tdtk_normals_knn_range.argtypes = [_dp, C.c_size_t, C.c_int, C.c_double, _dp, C.c_int, C.c_int, _dp, _ip, _ip]

@@ -196,6 +196,9 @@ int tree_finish(Ctx* c, tdtk_tree* t, size_t M);
 int tree_check_args(size_t M, int bucket_size);
 // api_query.cpp
 int adaptive_check_args(const double* xyz, size_t n, int kmin, int kmax, const double* rPos, const double* normals_out);
+struct QueryArgs;
+int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K, QueryArgs& a, const double* d_v = nullptr,
+                  const double* box = nullptr, size_t n_walks = 0);   // (also the forest's queries, api_forest.cpp: t a stand-in that carries max_depth)
 // api_search.cpp
 constexpr uint64_t SUMS_ARMED = 0x7FF8DEADBEEF0001ull;   // a NaN no sum can produce: the word a host arms before it watches for a result
 int prepare_overflow_in(DevBuf& bm2, DevBuf& bref, const tdtk_tree* t, size_t nq, SearchArgs& a);

@@ -13,8 +13,9 @@ using namespace tdtk;
 // (box: 6 doubles, the lower and upper corner the bin's grid spans instead of the tree's root box; n_walks: the number of
 // walks the overflow area is sized for, where that is not K -- the collision kernels bin their model and walk once per
 // (frame, model point))
-static int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K, QueryArgs& a, const double* d_v = nullptr,
-                         const double* box = nullptr, size_t n_walks = 0)
+namespace tdtk {
+int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K, QueryArgs& a, const double* d_v, const double* box,
+                  size_t n_walks)
 {
   int rc;
   int ids[] = {WS_QX, WS_QY, WS_QZ};
@@ -55,6 +56,7 @@ static int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K
   }
   return TDTK_OK;
 }
+}  // namespace tdtk
 
 static int knn_check_k(int k)
 {

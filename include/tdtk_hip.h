@@ -315,6 +315,54 @@ int tdtk_peopleremover(int device, const double* xyz, const uint64_t* scan_offse
 /* HIP-event times of the calling thread's last tdtk_peopleremover, ms: occupancy build, walk, cluster + half-free +
  * classification, and first upload to last download.                                                                 */
 int tdtk_peopleremover_timings(double* ms4);
+/* ---- the dynamic kd-forest: BkdTree (include/slam6d/bkd.h, src/slam6d/bkd.cc), the logarithmic method over the device
+ * kd-trees.  A forest is a buffer of fewer than `bucket` points and slots 0 .. S-1 (S <= 32), each empty or one kd-tree with
+ * a live-point count.  Every inserted point gets an id: the running insertion counter (the reference returns pointers).  The
+ * contract is the reference's stated as sets ("Dynamic kd-forest"): the layout after any sequence of calls
+ * (slots, the id set of every slot, the buffer as a sequence), every returned d2, every id where the answer is unique, the
+ * k-NN distance lists, the fixed-radius lists as id sets and the remove counts are the reference's; the order inside one
+ * tree's contribution to a list and which of several equidistant points or identical copies inside one container is named
+ * are this library's (slots ascending, the walk's visiting order, the buffer in order; the first wins a tie).  A forest's trees
+ * are private to it.  Non-finite coordinates: TDTK_EINVAL, nothing changes.  A forest belongs to one host thread at a time. */
+typedef struct tdtk_forest tdtk_forest;
+int tdtk_forest_create(int bucket, int device, tdtk_forest** out);     /* BkdTree(b): no slots */
+/* BkdTree(pts, n, b): max(1, ceil(log2(n / b))) slots (n / b an integer division), the last one a tree over all n points, ids
+ * 0 .. n-1.  n == 0: TDTK_EINVAL.                                                                                     */
+int tdtk_forest_create_from_points(const double* xyz, size_t n, int bucket, int device, tdtk_forest** out);
+void tdtk_forest_destroy(tdtk_forest* f);
+/* BkdTree::insert for the m points of xyz [m][3] in order, ids *first_id_out .. + m - 1 (nullable).  The layout is the one m
+ * single inserts give; every slot of it that changed is built once (tdtk_forest_plan).                                 */
+int tdtk_forest_insert(tdtk_forest* f, const double* xyz, size_t m, int32_t* first_id_out);
+/* the last tdtk_forest_insert of f, ms: the plan (host clock), the gathers and the builds of the slots it built (HIP events,
+ * summed over those slots), the call end to end (host clock); then the slots built and the merges they stand for.       */
+int tdtk_forest_last_insert(const tdtk_forest* f, double out6[6]);
+/* BkdTree::remove for the m points of xyz in order: in the lowest container (the buffer before slot 0) that holds a live point
+ * with Dist2 < 1e-9 the nearest such point goes.  removed_id_out [m]: its id, or -1 where the request matches nothing.  The
+ * requests of one call behave as if applied one after the other.  A tree whose count reaches 0 becomes an empty slot.   */
+int tdtk_forest_remove(tdtk_forest* f, const double* xyz, size_t m, int32_t* removed_id_out);
+/* counts [32] (the first *nslots written): live points per slot, 0 = empty; the buffer's fill; size(); table_mask: bit s set
+ * when the tree of slot s keeps its leaves in a table.  Every output is nullable.                                       */
+int tdtk_forest_info(const tdtk_forest* f, int* nslots, uint64_t* counts, uint64_t* buffer_fill, uint64_t* size, uint32_t* table_mask);
+/* the live points of slot `slot` in storage order, or of the buffer (slot = -1) in insertion order: ids [cap] and xyz [cap][3]
+ * (nullable each), *n their number -- written also when cap is too small, which is TDTK_EINVAL.                        */
+int tdtk_forest_collect(const tdtk_forest* f, int slot, int32_t* ids, double* xyz, size_t cap, uint64_t* n);
+/* BkdTree::FindClosest for K queries: every tree answers KDtree::FindClosest(p, maxdist2) (strict <), a later slot replaces the
+ * result only with a strictly smaller Dist2; the buffer is then scanned against the best so far, which is DBL_MAX -- not
+ * maxdist2 -- when no tree point was found (the reference's quirk, kept).  idx [K]: the id or -1; d2 [K] nullable, -1.0 then. */
+int tdtk_forest_find_closest(tdtk_forest* f, const double* q, size_t K, double maxdist2, int32_t* idx, double* d2);
+/* BkdTree::kNearestNeighbors: rows of k, ascending d2, -1 / -1.0 behind the live points there are; k <= 64 (TDTK_EUNSUP). */
+int tdtk_forest_knn(tdtk_forest* f, const double* q, size_t K, int k, int32_t* idx, double* d2);
+/* BkdTree::fixedRangeSearch under tdtk_fixed_range_search's contract (offsets [K+1] and *total always; cap < *total returns
+ * TDTK_EINVAL with those filled): tree points with Dist2 < sqRad2, buffer points with Dist2 <= sqRad2 (the reference's quirk). */
+int tdtk_forest_fixed_range(tdtk_forest* f, const double* q, size_t K, double sqRad2, uint64_t* offsets, int32_t* idx, double* d2,
+                            size_t cap, uint64_t* total);
+/* The plan of an insert, host only (no device is touched): live counts [nslots] and the buffer's fill (< bucket) before, m
+ * points inserted one at a time.  counts_out [32] (the first *nslots_out written); segs [cap_segs][4] = { final slot, kind, a,
+ * b } -- kind 0: the live points of old slot a (b of them), 1: the new points [a, b) in order, 2: the old buffer (b points) --,
+ * *nsegs their number (cap_segs too small: TDTK_EINVAL, *nsegs set); buf_out = { 1 if the old buffer stays, a, b }: the final
+ * buffer is the old one (if it stays) followed by the new points [a, b); *merges (nullable): the merges this stands for.  */
+int tdtk_forest_plan(const uint64_t* counts, int nslots, uint64_t fill, int bucket, uint64_t m, int* nslots_out, uint64_t* counts_out,
+                     int64_t* segs, size_t cap_segs, size_t* nsegs, uint64_t buf_out[3], uint64_t* merges);
 /* calculateNormalsKNN (normals.cc:442-516; calculateNormal :518-558): a KDtree(points, bucket) and, for every point, its
  * k nearest neighbours (itself included), their mean and covariance, the eigenvector of the smallest eigenvalue
  * (newmat EigenValues), oriented so that n . (p - rPos) >= 0, normalised.  normals_out [n][3] in point order (the

@@ -43,6 +43,13 @@ download; the voxel visits and visits per second of the walk; the walk again wit
 (what divergent ray lengths inside a wave cost).  The reference's time for the same input comes from
 `python tests/golden/make_golden_peopleremover.py --time` on a machine that has the checkout (one host thread).
 
+--only-forest runs the dynamic kd-forest (3dtk_amd.BkdTree, tdtk_forest_*) alone: a uniform map (density 1) grown from 0 to
+1M points by scans of 100 000 at bucket 20.  Warm, the minimum of --reps runs, per scan: the insert call end to end and its
+stages (the plan on the host clock, the gathers and the builds from HIP events), the slots it built and the occupied slots
+behind it, next to tdtk_tree_create over all the points so far -- what a caller does today.  On the final forest: FindClosest
+of the 1M points at maxdist2 = 625, k-NN at k = 10 and the 20.6-neighbour radius, each next to the same call on one tree over
+the same points; then 10 000 removes (the second batch of two, so that the first warms the code).
+
 Kernel times: run the same command under `rocprofv3 --kernel-trace --stats` (k_knn_reg, k_range_count / k_range_fill,
 k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest, k_knn_adaptive_reg / k_knn_adaptive_lds, k_ann_adaptive, k_knnr_reg / k_knnr_lds,
 k_collide_mark, k_collide_depth_axis)."""
@@ -389,6 +396,66 @@ def peopleremover_legs(tdtk, reps):
     return out
 
 
+def forest_legs(tdtk, reps):
+    """the dynamic kd-forest against the full rebuild and the single tree (see the module docstring)"""
+    n_scans, per = 10, 100_000
+    pts = np.random.default_rng(2031).uniform(-50, 50, (n_scans * per, 3))
+    r2 = (20.0 * 3 / (4 * np.pi)) ** (2.0 / 3.0)
+    out = {"forest_bucket": 20, "forest_scan_points": per}
+    rows = [dict() for _ in range(n_scans)]
+    f = None
+    for rep in range(reps + 1):                       # (the first run is the warm-up)
+        if f is not None:
+            f.close()
+        f = tdtk.BkdTree(20)
+        for i in range(n_scans):
+            scan = pts[i * per:(i + 1) * per]
+            t0 = time.perf_counter()
+            f.insert(scan)
+            ms = (time.perf_counter() - t0) * 1e3
+            st = f.last_insert()
+            if rep == 0:
+                continue
+            r = rows[i]
+            r["insert_ms"] = min(r.get("insert_ms", 1e30), ms)
+            for k in ("plan_ms", "gather_ms", "build_ms"):
+                r[k] = min(r.get(k, 1e30), st[k])
+            r["slots_built"], r["merges"] = st["slots_built"], st["merges"]
+            r["occupied_slots"] = sum(1 for c in f.info()[0] if c)
+            r["map_points"] = (i + 1) * per
+    for i, r in enumerate(rows):
+        r["rebuild_ms"] = timed(lambda: tdtk.KDtree(pts[:(i + 1) * per], 20), reps)["min_ms"]
+        for k in ("insert_ms", "plan_ms", "gather_ms", "build_ms"):
+            r[k] = round(r[k], 3)
+    out["forest_inserts"] = rows
+    occ = sum(1 for c in f.info()[0] if c)
+    out["forest_final_occupied_slots"] = occ
+    out["forest_final_counts"] = f.info()[0]
+    kd = tdtk.KDtree(pts, 20)
+    out["forest_find_closest_1M"] = timed(lambda: f.FindClosest(pts, 625.0), reps)
+    out["tree_find_closest_1M"] = timed(lambda: kd.FindClosestBatch(pts, 625.0), reps)
+    out["forest_knn_k10_1M"] = timed(lambda: f.kNearestNeighbors(pts, 10), reps)
+    out["tree_knn_k10_1M"] = timed(lambda: kd.kNearestNeighborsBatch(pts, 10), reps)
+    out["forest_range_20nn_1M"] = timed(lambda: f.fixedRangeSearch(pts, r2), reps)
+    out["tree_range_20nn_1M"] = timed(lambda: kd.fixedRangeSearchBatch(pts, r2), reps)
+    # the answers are the single tree's (a uniform cloud: no ties)
+    fi, fd = f.FindClosest(pts[:20000], 625.0)
+    ti, td = kd.FindClosestBatch(pts[:20000], 625.0)
+    assert np.array_equal(fi, ti) and np.array_equal(fd, td)
+    fi, fd = f.kNearestNeighbors(pts[:20000], 10)
+    ti, td = kd.kNearestNeighborsBatch(pts[:20000], 10)
+    assert np.array_equal(fd, td) and np.array_equal(fi, ti)
+    pick = np.random.default_rng(2032).permutation(len(pts))[:20000]
+    f.remove(pts[pick[:10000]])
+    t0 = time.perf_counter()
+    got = f.remove(pts[pick[10000:]])
+    out["forest_remove_10000_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+    assert np.array_equal(np.sort(got), np.sort(pick[10000:]))
+    out["forest_remove_occupied_slots"] = occ
+    f.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000000,10000000")
@@ -406,6 +473,7 @@ def main():
     ap.add_argument("--clusters", action="store_true", help="add the radius-clustering legs (1M points, two radii)")
     ap.add_argument("--only-clusters", action="store_true", help="those legs alone")
     ap.add_argument("--only-peopleremover", action="store_true", help="dynamic-object removal on a synthetic room, alone")
+    ap.add_argument("--only-forest", action="store_true", help="the dynamic kd-forest against rebuilds and the single tree, alone")
     args = ap.parse_args()
     tdtk = importlib.import_module("3dtk_amd")
     if tdtk.device_count() < 1:
@@ -413,6 +481,10 @@ def main():
     out = {"workload": "kdtree_queries", "reps": args.reps}
     if args.only_peopleremover:
         out.update(peopleremover_legs(tdtk, args.reps))
+        print(json.dumps(out))
+        return
+    if args.only_forest:
+        out.update(forest_legs(tdtk, args.reps))
         print(json.dumps(out))
         return
     rng = np.random.default_rng(2024)
