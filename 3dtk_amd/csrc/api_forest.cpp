@@ -491,8 +491,7 @@ int tdtk_forest_knn(tdtk_forest* f, const double* q, size_t K, int k, int32_t* i
   int rc;
   if ((rc = forest_check(f, q, K))) return rc;
   if (!idx && K) { set_error("NULL argument"); return TDTK_EINVAL; }
-  if (k < 1) { set_error("k must be >= 1"); return TDTK_EINVAL; }
-  if (k > KNN_MAX_K) { set_error("k = " + std::to_string(k) + " exceeds the supported list capacity of " + std::to_string(KNN_MAX_K)); return TDTK_EUNSUP; }
+  if ((rc = knn_check_k(k))) return rc;
   if (K == 0) return TDTK_OK;
   const size_t L = K * (size_t)k;
   if (f->size() == 0) {
@@ -530,38 +529,12 @@ int tdtk_forest_fixed_range(tdtk_forest* f, const double* q, size_t K, double sq
   Ctx* c;
   if ((rc = get_ctx(f->device, &c))) return rc;
   hipStream_t s = c->stream;
-  const size_t tmpb = range_scan_temp_bytes(K);
   ForestArgs a;
   if ((rc = forest_query_begin(c, f, q, K, a))) return rc;
-  if ((rc = c->ws[WS_KPOS].ensure((K + 1) * sizeof(uint32_t)))) return rc;
-  if ((rc = c->ws[WS_D2].ensure((K + 1) * sizeof(unsigned long long)))) return rc;
-  if ((rc = c->ws[WS_ARENA].ensure(tmpb + 256))) return rc;
   a.q.r2 = sqRad2;
-  a.q.counts = c->ws[WS_KPOS].as<uint32_t>();
-  unsigned long long* d_off = c->ws[WS_D2].as<unsigned long long>();
-  HIPCHK(hipMemsetAsync(a.q.counts + K, 0, sizeof(uint32_t), s));
-  HIPCHK(launch_forest_range_count(a, s));
-  HIPCHK(launch_range_scan(a.q.counts, d_off, K, c->ws[WS_ARENA].p, tmpb, s));
-  HIPCHK(hipMemcpyAsync(offsets, d_off, (K + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const uint64_t tot = offsets[K];
-  *total = tot;
-  if (cap < tot) {
-    set_error("tdtk_forest_fixed_range: " + std::to_string(tot) + " neighbours, capacity " + std::to_string(cap) + " (offsets and total are filled)");
-    return TDTK_EINVAL;
-  }
-  if (tot == 0) return TDTK_OK;
-  if (!idx) { set_error("idx is NULL"); return TDTK_EINVAL; }
-  if ((rc = c->ws[WS_IDX].ensure(tot * sizeof(int32_t)))) return rc;
-  if (d2 && (rc = c->ws[WS_TMPB].ensure(tot * sizeof(double)))) return rc;
-  a.q.offsets = d_off;
-  a.q.idx = c->ws[WS_IDX].as<int32_t>();
-  a.q.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
-  HIPCHK(launch_forest_range_fill(a, s));
-  HIPCHK(hipMemcpyAsync(idx, a.q.idx, tot * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  if (d2) HIPCHK(hipMemcpyAsync(d2, a.q.d2, tot * sizeof(double), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  return TDTK_OK;
+  auto count = [&]() { HIPCHK(launch_forest_range_count(a, s)); return TDTK_OK; };
+  auto fill = [&]() { HIPCHK(launch_forest_range_fill(a, s)); return TDTK_OK; };
+  return list_walks(c, "tdtk_forest_fixed_range", "neighbours", a.q, false, count, fill, offsets, idx, d2, cap, total);
 }
 
 // The insert plan, host only: counts [nslots] and fill (< bucket) before, m points inserted.  counts_out [FOREST_MAX_SLOTS] (the

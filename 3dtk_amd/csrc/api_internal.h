@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -199,6 +200,10 @@ int adaptive_check_args(const double* xyz, size_t n, int kmin, int kmax, const d
 struct QueryArgs;
 int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K, QueryArgs& a, const double* d_v = nullptr,
                   const double* box = nullptr, size_t n_walks = 0);   // (also the forest's queries, api_forest.cpp: t a stand-in that carries max_depth)
+int knn_check_k(int k);
+// count walk, scan, offsets to the host, capacity check, fill walk, downloads: every list query, a tree's or the forest's
+int list_walks(Ctx* c, const char* name, const char* noun, QueryArgs& a, bool timed, const std::function<int()>& count,
+               const std::function<int()>& fill, uint64_t* offsets, int32_t* idx, double* d2, size_t cap, uint64_t* total);
 // api_search.cpp
 constexpr uint64_t SUMS_ARMED = 0x7FF8DEADBEEF0001ull;   // a NaN no sum can produce: the word a host arms before it watches for a result
 int prepare_overflow_in(DevBuf& bm2, DevBuf& bref, const tdtk_tree* t, size_t nq, SearchArgs& a);

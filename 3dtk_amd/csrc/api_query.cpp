@@ -58,12 +58,14 @@ int query_prepare(Ctx* c, const tdtk_tree* t, const double* d_q, size_t K, Query
 }
 }  // namespace tdtk
 
-static int knn_check_k(int k)
+namespace tdtk {
+int knn_check_k(int k)
 {
   if (k < 1) { set_error("k must be >= 1"); return TDTK_EINVAL; }
   if (k > KNN_MAX_K) { set_error("k = " + std::to_string(k) + " exceeds the supported list capacity of " + std::to_string(KNN_MAX_K)); return TDTK_EUNSUP; }
   return TDTK_OK;
 }
+}  // namespace tdtk
 
 // a tree over host points [n][3] for the normal estimators; the points stay in WS_TMPA (the build only reads them)
 static int normals_tree(Ctx* c, const double* xyz, size_t n, int bucket, int device, std::unique_ptr<tdtk_tree>& t)
@@ -94,32 +96,27 @@ static int query_begin(Ctx* c, const tdtk_tree* t, const double* q, const double
 // tdtk_kernel_timing(1): HIP events around the count walk of a list query and the link walk of the clustering
 static bool walk_timed() { return g_kernel_timing.load(std::memory_order_relaxed) > 0; }
 
-// The list queries -- the fixed radius (mode < 0; d2 nullable) and the four shape walks of query.hip (mode: ShapeMode, v
-// their second vector) -- in two walks: the count walk into WS_KPOS, the scan into WS_D2 (WS_ARENA its scratch), the offsets
-// to the host, and, where the caller's capacity holds the total, the fill walk into WS_IDX (and WS_TMPB for d2).
-// `noun`: what the capacity error counts
-static int list_query(const char* name, const char* noun, int mode, const tdtk_tree* t, const double* q, const double* v,
-                      size_t K, double r2, uint64_t* offsets, int32_t* idx, double* d2, size_t cap, uint64_t* total)
+// A list query in two walks over the a.n queries of the prepared block `a` (r2 set): the count walk into WS_KPOS, the scan
+// into WS_D2 (WS_ARENA its scratch), the offsets to the host, and, where the caller's capacity holds the total, the fill walk
+// into WS_IDX (and WS_TMPB for d2, nullable).  count() and fill() launch the two walks on the context's stream and return a
+// TDTK code (the launch's error text is theirs); they read `a` as it stands when they are called.  `noun`: what the capacity
+// error counts; timed: HIP events around the count walk (tdtk_last_kernel_ms)
+namespace tdtk {
+int list_walks(Ctx* c, const char* name, const char* noun, QueryArgs& a, bool timed, const std::function<int()>& count,
+               const std::function<int()>& fill, uint64_t* offsets, int32_t* idx, double* d2, size_t cap, uint64_t* total)
 {
-  Ctx* c;
   int rc;
-  if ((rc = get_ctx(t->device, &c))) return rc;
-  offsets[0] = 0; *total = 0;
-  if (K == 0) return TDTK_OK;
   hipStream_t s = c->stream;
+  const size_t K = a.n;
   const size_t tmpb = range_scan_temp_bytes(K);
-  QueryArgs a;
-  if ((rc = query_begin(c, t, q, v, K, a))) return rc;
   if ((rc = c->ws[WS_KPOS].ensure((K + 1) * sizeof(uint32_t)))) return rc;
   if ((rc = c->ws[WS_D2].ensure((K + 1) * sizeof(unsigned long long)))) return rc;
   if ((rc = c->ws[WS_ARENA].ensure(tmpb + 256))) return rc;
-  a.r2 = r2;
   a.counts = c->ws[WS_KPOS].as<uint32_t>();
   unsigned long long* d_off = c->ws[WS_D2].as<unsigned long long>();
   HIPCHK(hipMemsetAsync(a.counts + K, 0, sizeof(uint32_t), s));
-  const bool timed = walk_timed();      // tdtk_last_kernel_ms: the count walk
   if (timed) HIPCHK(hipEventRecord(c->e0, s));
-  HIPCHK(mode < 0 ? launch_range_count(a, s) : launch_shape_count(a, mode, s));
+  if ((rc = count())) return rc;
   if (timed) { HIPCHK(hipEventRecord(c->e1, s)); c->ev_pending = true; }
   HIPCHK(launch_range_scan(a.counts, d_off, K, c->ws[WS_ARENA].p, tmpb, s));
   HIPCHK(hipMemcpyAsync(offsets, d_off, (K + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
@@ -137,11 +134,31 @@ static int list_query(const char* name, const char* noun, int mode, const tdtk_t
   a.offsets = d_off;
   a.idx = c->ws[WS_IDX].as<int32_t>();
   a.d2 = d2 ? c->ws[WS_TMPB].as<double>() : nullptr;
-  HIPCHK(mode < 0 ? launch_range_fill(a, s) : launch_shape_fill(a, mode, s));
+  if ((rc = fill())) return rc;
   HIPCHK(hipMemcpyAsync(idx, a.idx, tot * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   if (d2) HIPCHK(hipMemcpyAsync(d2, a.d2, tot * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   return TDTK_OK;
+}
+}  // namespace tdtk
+
+// the list queries of a tree: the fixed radius (mode < 0; d2 nullable) and the four shape walks of query.hip (mode: ShapeMode,
+// v their second vector)
+static int list_query(const char* name, const char* noun, int mode, const tdtk_tree* t, const double* q, const double* v,
+                      size_t K, double r2, uint64_t* offsets, int32_t* idx, double* d2, size_t cap, uint64_t* total)
+{
+  Ctx* c;
+  int rc;
+  if ((rc = get_ctx(t->device, &c))) return rc;
+  offsets[0] = 0; *total = 0;
+  if (K == 0) return TDTK_OK;
+  hipStream_t s = c->stream;
+  QueryArgs a;
+  if ((rc = query_begin(c, t, q, v, K, a))) return rc;
+  a.r2 = r2;
+  auto count = [&]() { HIPCHK(mode < 0 ? launch_range_count(a, s) : launch_shape_count(a, mode, s)); return TDTK_OK; };
+  auto fill = [&]() { HIPCHK(mode < 0 ? launch_range_fill(a, s) : launch_shape_fill(a, mode, s)); return TDTK_OK; };
+  return list_walks(c, name, noun, a, walk_timed(), count, fill, offsets, idx, d2, cap, total);
 }
 
 extern "C" {

@@ -1,56 +1,23 @@
 // lib3dtk_hip.so -- the dynamic kd-forest: BkdTree (include/slam6d/bkd.h, src/slam6d/bkd.cc; Procopiuc et al.), the
-// logarithmic method over the device kd-trees.  This file holds what needs the device: the kernarg block, the query kernels
-// (one launch per call over all slots and the buffer), the remove pass and the gathers of a merge.  The walks and everything
-// else a lane does, with the rules of every query, are in forest_lane.h.
+// logarithmic method over the device kd-trees.  This file holds what needs the device: the query kernels (one launch per
+// call over all slots and the buffer), the remove pass and the gathers of a merge, on query.hip's scaffold (query_dev.h: the
+// kernarg block, the lane stack, the launch constants).  Everything a lane does, with the rules of every query, is in
+// forest_lane.h; the tree walks themselves are query_lane.h's.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
-#include "lane_stack.h"
 #include "forest.h"
+#include "query_dev.h"
 
 namespace tdtk {
 
-// block sizes, LDS stack levels and the grid cap of query.hip: query_overflow_entries (query.hip) sizes the overflow area of
-// the lane stack for exactly these
-constexpr int F_BLOCK = 128;
-constexpr int F_SD = 16;
-constexpr int F_BLOCK_L = 64;        // the k-NN kernels (LDS list)
-constexpr int F_MAX_BLOCKS = 2048;
-
-// the argument block through the kernarg segment pointer (as query.hip's q_args): the slot table is indexed by a loop counter,
-// which behind a by-value parameter would copy the block to scratch
-__device__ __forceinline__ const ForestArgs& f_args()
-{
-  typedef const ForestArgs __attribute__((address_space(4))) * kernarg_ptr;
-  kernarg_ptr p = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return *(const ForestArgs*)p;
-}
-
-template <int BLOCK>
-struct ForestLane {
-  LaneStackQ<BLOCK, F_SD> st;
-  size_t i, T;
-  __device__ __forceinline__ ForestLane(const QueryArgs& a, uint4 (*lds)[BLOCK])
-  {
-    st.l_e = &lds[0][threadIdx.x];
-    st.g_m2 = a.ovf_m2;
-    st.g_ref = a.ovf_ref;
-    st.gcol = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    st.gstride = (size_t)gridDim.x * BLOCK;
-    st.sp = 0;
-    T = (size_t)gridDim.x * BLOCK;
-    i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  }
-};
-
 // ---- queries ---------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(F_BLOCK) k_forest_find_closest(const ForestArgs a_)
+__global__ void __launch_bounds__(Q_BLOCK) k_forest_find_closest(const ForestArgs a_)
 {
-  const ForestArgs& f = f_args();
+  const ForestArgs& f = q_args<ForestArgs>();
   const QueryArgs& a = f.q;
-  __shared__ uint4 s_stack[F_SD][F_BLOCK];
-  for (ForestLane<F_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
     const size_t i = q.i;
     const size_t o = a.order ? (size_t)a.order[i] : i;
     int32_t id;
@@ -63,18 +30,18 @@ __global__ void __launch_bounds__(F_BLOCK) k_forest_find_closest(const ForestArg
 
 // KCAP: the list's capacity (k <= KCAP)
 template <int KCAP>
-__global__ void __launch_bounds__(F_BLOCK_L) k_forest_knn(const ForestArgs a_)
+__global__ void __launch_bounds__(Q_BLOCK_L) k_forest_knn(const ForestArgs a_)
 {
-  const ForestArgs& f = f_args();
+  const ForestArgs& f = q_args<ForestArgs>();
   const QueryArgs& a = f.q;
-  __shared__ uint4 s_stack[F_SD][F_BLOCK_L];
-  __shared__ double s_d[KCAP][F_BLOCK_L];
-  __shared__ uint32_t s_s[KCAP][F_BLOCK_L];
-  ListLds<F_BLOCK_L> L;
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK_L];
+  __shared__ double s_d[KCAP][Q_BLOCK_L];
+  __shared__ uint32_t s_s[KCAP][Q_BLOCK_L];
+  ListLds<Q_BLOCK_L> L;
   L.ld = &s_d[0][threadIdx.x];
   L.ls = &s_s[0][threadIdx.x];
   const int k = a.k;
-  for (ForestLane<F_BLOCK_L> q(a, s_stack); q.i < a.n; q.i += q.T) {
+  for (LaneQueries<Q_BLOCK_L> q(a, s_stack); q.i < a.n; q.i += q.T) {
     const size_t i = q.i;
     const size_t o = a.order ? (size_t)a.order[i] : i;
     L.init(k);
@@ -89,12 +56,12 @@ __global__ void __launch_bounds__(F_BLOCK_L) k_forest_knn(const ForestArgs a_)
   }
 }
 
-__global__ void __launch_bounds__(F_BLOCK) k_forest_range_count(const ForestArgs a_)
+__global__ void __launch_bounds__(Q_BLOCK) k_forest_range_count(const ForestArgs a_)
 {
-  const ForestArgs& f = f_args();
+  const ForestArgs& f = q_args<ForestArgs>();
   const QueryArgs& a = f.q;
-  __shared__ uint4 s_stack[F_SD][F_BLOCK];
-  for (ForestLane<F_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
     const size_t i = q.i;
     uint32_t c = 0;
     auto emit = [&](int32_t, double) { ++c; };
@@ -103,12 +70,12 @@ __global__ void __launch_bounds__(F_BLOCK) k_forest_range_count(const ForestArgs
   }
 }
 
-__global__ void __launch_bounds__(F_BLOCK) k_forest_range_fill(const ForestArgs a_)
+__global__ void __launch_bounds__(Q_BLOCK) k_forest_range_fill(const ForestArgs a_)
 {
-  const ForestArgs& f = f_args();
+  const ForestArgs& f = q_args<ForestArgs>();
   const QueryArgs& a = f.q;
-  __shared__ uint4 s_stack[F_SD][F_BLOCK];
-  for (ForestLane<F_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
     const size_t i = q.i;
     const size_t o = a.order ? (size_t)a.order[i] : i;
     unsigned long long w = a.offsets[o];
@@ -138,12 +105,12 @@ __global__ void k_forest_remove_reset(uint32_t* ctl)
   ctl[1] = 0u;
 }
 
-__global__ void __launch_bounds__(F_BLOCK) k_forest_remove_find(const ForestArgs a_)
+__global__ void __launch_bounds__(Q_BLOCK) k_forest_remove_find(const ForestArgs a_)
 {
-  const ForestArgs& f = f_args();
+  const ForestArgs& f = q_args<ForestArgs>();
   const QueryArgs& a = f.q;
-  __shared__ uint4 s_stack[F_SD][F_BLOCK];
-  for (ForestLane<F_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
+  __shared__ uint4 s_stack[Q_SD][Q_BLOCK];
+  for (LaneQueries<Q_BLOCK> q(a, s_stack); q.i < a.n; q.i += q.T) {
     const size_t i = q.i;
     const size_t o = a.order ? (size_t)a.order[i] : i;
     if (f.res[o] != -2) continue;
@@ -163,7 +130,7 @@ __global__ void __launch_bounds__(F_BLOCK) k_forest_remove_find(const ForestArgs
 template <int STEP>
 __global__ void __launch_bounds__(256) k_forest_remove_settle(const ForestArgs a_)
 {
-  const ForestArgs& f = f_args();
+  const ForestArgs& f = q_args<ForestArgs>();
   const size_t T = (size_t)gridDim.x * blockDim.x;
   for (size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x; o < f.q.n; o += T) {
     if (f.res[o] != -2) continue;
@@ -239,18 +206,12 @@ __global__ void __launch_bounds__(256) k_forest_relabel(KdPoint* __restrict__ pt
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------
-static uint32_t f_grid(size_t n, int block)
-{
-  const size_t nb = (n + block - 1) / block;
-  return (uint32_t)(nb < (size_t)F_MAX_BLOCKS ? (nb ? nb : 1) : F_MAX_BLOCKS);
-}
-
 typedef void (*ForestKernel)(const ForestArgs);
 
-static hipError_t launch_f(ForestKernel kernel, const ForestArgs& a, hipStream_t s, int block = F_BLOCK)
+static hipError_t launch_f(ForestKernel kernel, const ForestArgs& a, hipStream_t s, int block = Q_BLOCK)
 {
   if (a.nslots < 0 || a.nslots > FOREST_MAX_SLOTS) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kernel, dim3(f_grid(a.q.n, block)), dim3(block), 0, s, a);
+  hipLaunchKernelGGL(kernel, dim3(q_grid(a.q.n, block)), dim3(block), 0, s, a);
   return hipGetLastError();
 }
 
@@ -259,7 +220,7 @@ hipError_t launch_forest_find_closest(const ForestArgs& a, hipStream_t s) { retu
 hipError_t launch_forest_knn(const ForestArgs& a, hipStream_t s)
 {
   if (a.q.k < 1 || a.q.k > KNN_MAX_K) return hipErrorInvalidValue;
-  return launch_f(a.q.k <= 16 ? k_forest_knn<16> : k_forest_knn<KNN_MAX_K>, a, s, F_BLOCK_L);
+  return launch_f(a.q.k <= 16 ? k_forest_knn<16> : k_forest_knn<KNN_MAX_K>, a, s, Q_BLOCK_L);
 }
 
 hipError_t launch_forest_range_count(const ForestArgs& a, hipStream_t s) { return launch_f(k_forest_range_count, a, s); }
@@ -278,13 +239,13 @@ hipError_t launch_forest_remove_round(const ForestArgs& a, hipStream_t s)
 hipError_t launch_forest_copy_points(const KdPoint* pts, size_t n, double* xyz, int32_t* ids, size_t base, hipStream_t s)
 {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_forest_copy_points, dim3(f_grid(n, 256)), dim3(256), 0, s, pts, n, xyz, ids, base);
+  hipLaunchKernelGGL(k_forest_copy_points, dim3(q_grid(n, 256)), dim3(256), 0, s, pts, n, xyz, ids, base);
   return hipGetLastError();
 }
 
 hipError_t launch_forest_live_flags(const KdPoint* pts, size_t n, uint32_t* flags, hipStream_t s)
 {
-  hipLaunchKernelGGL(k_forest_live_flags, dim3(f_grid(n + 1, 256)), dim3(256), 0, s, pts, n, flags);
+  hipLaunchKernelGGL(k_forest_live_flags, dim3(q_grid(n + 1, 256)), dim3(256), 0, s, pts, n, flags);
   return hipGetLastError();
 }
 
@@ -292,7 +253,7 @@ hipError_t launch_forest_compact_points(const KdPoint* pts, size_t n, const uint
                                         hipStream_t s)
 {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_forest_compact_points, dim3(f_grid(n, 256)), dim3(256), 0, s, pts, n, offs, xyz, ids, base);
+  hipLaunchKernelGGL(k_forest_compact_points, dim3(q_grid(n, 256)), dim3(256), 0, s, pts, n, offs, xyz, ids, base);
   return hipGetLastError();
 }
 
@@ -300,14 +261,14 @@ hipError_t launch_forest_copy_new(const double* src_xyz, size_t a, size_t b, int
                                   hipStream_t s)
 {
   if (b <= a) return hipSuccess;
-  hipLaunchKernelGGL(k_forest_copy_new, dim3(f_grid(b - a, 256)), dim3(256), 0, s, src_xyz, a, b, first_id, xyz, ids, base);
+  hipLaunchKernelGGL(k_forest_copy_new, dim3(q_grid(b - a, 256)), dim3(256), 0, s, src_xyz, a, b, first_id, xyz, ids, base);
   return hipGetLastError();
 }
 
 hipError_t launch_forest_relabel(KdPoint* pts, size_t n, const int32_t* ids, hipStream_t s)
 {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_forest_relabel, dim3(f_grid(n, 256)), dim3(256), 0, s, pts, n, ids);
+  hipLaunchKernelGGL(k_forest_relabel, dim3(q_grid(n, 256)), dim3(256), 0, s, pts, n, ids);
   return hipGetLastError();
 }
 

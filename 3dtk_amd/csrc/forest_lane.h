@@ -2,9 +2,15 @@
 // library's static kd-trees.  A forest is a buffer of fewer than b points and slots 0 .. S-1, each empty or one kd-tree built
 // by the device build over the points handed to it; its points carry their forest id (the running insertion counter) in
 // KdPoint::orig.  Nothing here needs the device: a host compiler reads this file under tests/host_lane_shim.h, and the CPU
-// tier runs these walks against the reference's fixture (tests/test_bkd_host.py).  The stack is a template parameter as in
-// query_lane.h.  What needs the device -- the kernarg block, the kernels, the claims of the remove pass, the gathers of a
-// merge -- is in forest.hip.
+// tier runs this code against the reference's fixture (tests/test_bkd_host.py).  The stack is a template parameter as in
+// query_lane.h.  What needs the device -- the kernels, the claims of the remove pass, the gathers of a merge -- is in
+// forest.hip.
+//
+// No tree is descended here: the loops are query_lane.h's knn_walk, range_walk and nearest_walk, which read a ForestSlot as
+// they read QueryArgs.  What the forest changes in them is stated once: the point policy LiveById (a walk sees the points
+// with orig >= 0 and a list names them by orig, where a tree query sees every point and names it by its slot) and, for
+// nearest_walk, the rule LiveClosestRule (the same filter, no node test beside the box test, position and id of the point
+// taken).  This file adds the order over the containers -- slots ascending, the buffer -- and the quirks between them.
 //
 // Layout of every query kernel: ONE launch per call covers all slots and the buffer.  One query per lane, binned first
 // (launch_bin), a grid-stride loop; a lane loops over the by-value table of slot descriptors (ForestSlot, at most
@@ -12,15 +18,15 @@
 // ones and every decision is the reference's expression on the reference's values.
 //
 // Removed points.  A removed point stays where it is and its KdPoint::orig becomes -1: the liveness word is the id itself.
-// Every walk below loads the whole 32-byte KdPoint anyway, so the test costs no load; a removal is one 4-byte store and
+// Every walk loads the whole 32-byte KdPoint anyway, so the test costs no load; a removal is one 4-byte store and
 // rewrites no node, no packed child reference and no leaf table, so it is the same in packed and in table mode and a leaf
 // that is emptied completely simply contributes nothing.  (The reference swaps the point to the end of its leaf and
-// decrements the leaf's count; the sets a walk sees are the same.)  The walks of query_lane.h do not look at orig, which is
-// why the forest has its own three; its trees are private to it and never handed out as tdtk_tree.
+// decrements the leaf's count; the sets a walk sees are the same.)  The forest's trees are private to it and never handed
+// out as tdtk_tree: under the default policy a walk would see their removed points.
 //
-// The walks, rule by rule:
+// The queries, rule by rule:
 //
-// FindClosest (BkdTree::FindClosest, bkd.cc:227-259, over KDTreeImpl::_FindClosest, kdTreeImpl.h:345-383):
+// FindClosest (BkdTree::FindClosest, bkd.cc:227-259, over KDTreeImpl::_FindClosest, kdTreeImpl.h:345-383: nearest_walk):
 //   * per tree: closest_d2 starts at maxdist2; leaf: a point is taken when Dist2 < closest_d2 (strict: the first visited
 //     point wins a tie), in bucket order.
 //   * internal node: a = max(max(|p0-cx|-hx, |p1-cy|-hy), |p2-cz|-hz); return when a >= 0 && a*a >= closest_d2.
@@ -81,131 +87,30 @@ struct ForestArgs {
   ForestSlot slot[FOREST_MAX_SLOTS];
 };
 
-__device__ __forceinline__ void forest_leaf_span(const ForestSlot& t, const uint32_t ref, uint32_t& start, uint32_t& count)
-{
-  const uint32_t v = ref & REF_VAL;
-  if (t.leaf_tab) { const LeafEntry e = t.leaf_tab[v]; start = (uint32_t)e.start; count = (uint32_t)e.count; }
-  else { start = v >> t.cb; count = v & t.cmask; }
-}
+// the forest's point policy (query_lane.h, "the point policy"): the live points, named by their forest id
+struct LiveById {
+  static __device__ __forceinline__ bool sees(const KdPoint& p) { return p.orig >= 0; }
+  static __device__ __forceinline__ uint32_t name(const KdPoint& p, uint32_t) { return (uint32_t)p.orig; }
+};
+
+// _FindClosest over the live points as nearest_walk's rule: no test beside the box test; pos / id are the position and the
+// id of closest (unchanged: none)
+struct LiveClosestRule {
+  uint32_t& pos;
+  int32_t& id;
+  __device__ __forceinline__ bool skip(const KdPoint& p) const { return p.orig < 0; }
+  __device__ __forceinline__ bool prune(const KdNode&, uint32_t) const { return false; }
+  __device__ __forceinline__ void take(const KdPoint& p, const uint32_t slot) const { pos = slot; id = p.orig; }
+};
 
 // _FindClosest over the live points of one tree: best / pos are closest_d2 / the position of closest (unchanged: none)
 template <class STACK>
 __device__ void forest_closest_walk(const ForestSlot& t, const double qx, const double qy, const double qz, STACK& st,
                                     double& best, uint32_t& pos, int32_t& id)
 {
-  uint32_t cur = t.root_ref;
+  LiveClosestRule rule{pos, id};
   st.sp = 0;
-  for (;;) {
-    if (cur & REF_LEAF) {
-      uint32_t start, count;
-      forest_leaf_span(t, cur, start, count);
-      for (uint32_t i = 0; i < count; i++) {
-        const KdPoint p = t.pts[start + i];
-        if (p.orig < 0) continue;
-        const double md = dist2(p, qx, qy, qz);
-        if (md < best) { best = md; pos = start + i; id = p.orig; }
-      }
-    } else {
-      const KdNode nd = t.nodes[cur & REF_VAL];
-      const double ap = box_dist(nd, qx, qy, qz);
-      if (!(ap >= 0.0 && ap * ap >= best)) {
-        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
-        const double qa = (axis == 0) ? qx : ((axis == 1) ? qy : qz);
-        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2c = nd.c2 & ~REF_AXIS;
-        const double myd = nd.splitval - qa;
-        const bool first = myd >= 0.0;
-        st.push(first ? r2c : r1, myd * myd);
-        cur = first ? r1 : r2c;
-        continue;
-      }
-    }
-    // the far child of the innermost open node, if its plane still lies inside closest_d2
-    bool more = false;
-    while (st.sp > 0) {
-      --st.sp;
-      double m2;
-      st.top(cur, m2);
-      if (m2 < best) { more = true; break; }
-    }
-    if (!more) break;
-  }
-}
-
-// knn_walk over the live points of one tree; the list holds ids
-template <class LIST, class STACK>
-__device__ void forest_knn_walk(const ForestSlot& t, const double qx, const double qy, const double qz, LIST& L, STACK& st)
-{
-  uint32_t cur = t.root_ref;
-  st.sp = 0;
-  for (;;) {
-    if (cur & REF_LEAF) {
-      uint32_t start, count;
-      forest_leaf_span(t, cur, start, count);
-      for (uint32_t i = 0; i < count; i++) {
-        const KdPoint p = t.pts[start + i];
-        if (p.orig < 0) continue;
-        L.insert(dist2(p, qx, qy, qz), (uint32_t)p.orig);
-      }
-    } else {
-      const KdNode nd = t.nodes[cur & REF_VAL];
-      bool pruned = false;
-      if (L.full()) {
-        const double ap = box_dist(nd, qx, qy, qz);
-        pruned = (ap >= 0.0 && ap * ap >= L.kth);
-      }
-      if (!pruned) {
-        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
-        const double qa = (axis == 0) ? qx : ((axis == 1) ? qy : qz);
-        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2 = nd.c2 & ~REF_AXIS;
-        const bool first = qa < nd.splitval;
-        st.push(first ? r2 : r1, 0.0);
-        cur = first ? r1 : r2;
-        continue;
-      }
-    }
-    if (st.sp == 0) break;
-    --st.sp;
-    double unused;
-    st.top(cur, unused);
-  }
-}
-
-// range_walk over the live points of one tree: EMIT(id, d2) in visiting order
-template <class STACK, class EMIT>
-__device__ void forest_range_walk(const ForestSlot& t, const double qx, const double qy, const double qz, const double r2,
-                                  STACK& st, EMIT& emit)
-{
-  uint32_t cur = t.root_ref;
-  st.sp = 0;
-  for (;;) {
-    if (cur & REF_LEAF) {
-      uint32_t start, count;
-      forest_leaf_span(t, cur, start, count);
-      for (uint32_t i = 0; i < count; i++) {
-        const KdPoint p = t.pts[start + i];
-        if (p.orig < 0) continue;
-        const double md = dist2(p, qx, qy, qz);
-        if (md < r2) emit(p.orig, md);
-      }
-    } else {
-      const KdNode nd = t.nodes[cur & REF_VAL];
-      const double ap = box_dist(nd, qx, qy, qz);
-      if (!(ap >= 0.0 && ap * ap >= r2)) {
-        const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
-        const double qa = (axis == 0) ? qx : ((axis == 1) ? qy : qz);
-        const uint32_t r1 = nd.c1 & ~REF_AXIS, r2c = nd.c2 & ~REF_AXIS;
-        const double myd = nd.splitval - qa;
-        const bool first = myd >= 0.0;
-        if (myd * myd < r2) st.push(first ? r2c : r1, 0.0);
-        cur = first ? r1 : r2c;
-        continue;
-      }
-    }
-    if (st.sp == 0) break;
-    --st.sp;
-    double unused;
-    st.top(cur, unused);
-  }
+  nearest_walk(t, qx, qy, qz, rule, st, best);
 }
 
 // ---- one query against the whole forest ---------------------------------------------------------------------------------
@@ -238,7 +143,8 @@ __device__ __forceinline__ void forest_knn(const ForestArgs& f, const double qx,
 {
   for (int s = 0; s < f.nslots; s++) {
     if (f.slot[s].n == 0) continue;
-    forest_knn_walk(f.slot[s], qx, qy, qz, L, st);
+    st.sp = 0;
+    knn_walk<LiveById>(f.slot[s], qx, qy, qz, L, st);
   }
   for (uint32_t i = 0; i < f.nbuf; i++) {
     const KdPoint p = f.buf[i];
@@ -252,9 +158,11 @@ template <class STACK, class EMIT>
 __device__ __forceinline__ void forest_fixed_range(const ForestArgs& f, const double qx, const double qy, const double qz,
                                                    const double r2, STACK& st, EMIT& emit)
 {
+  auto listed = [&](const KdPoint&, const uint32_t id, const double md) { emit((int32_t)id, md); };
   for (int s = 0; s < f.nslots; s++) {
     if (f.slot[s].n == 0) continue;
-    forest_range_walk(f.slot[s], qx, qy, qz, r2, st, emit);
+    st.sp = 0;
+    range_walk<LiveById>(f.slot[s], qx, qy, qz, r2, st, listed);
   }
   for (uint32_t i = 0; i < f.nbuf; i++) {
     const KdPoint p = f.buf[i];

@@ -6,61 +6,20 @@
 // range and segment walks (collision_model.cc:312-430, 714-800); and radius clustering, the connected components of the
 // fixed-radius graph (segment_colliding.cc:55-102), over the range walk under an emitter that hooks a union-find.
 //
-// This file holds what needs the device: the kernarg block, the lane stack's set-up, the register list, list_normal, the
-// kernels and the launchers.  The walks and everything else a lane does, with the rules of every walk, are in query_lane.h.
+// This file holds what needs the device: the register list, list_normal, the kernels and the launchers.  The kernarg block,
+// the lane stack's set-up and the launch constants are in query_dev.h (shared with forest.hip); the walks and everything else
+// a lane does, with the rules of every walk, are in query_lane.h.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 
 #include "kernels.h"
-#include "lane_stack.h"
 #include "eigen3.h"
 #include "query.h"
+#include "query_dev.h"
 #include "query_lane.h"
 #include "cluster_lane.h"
 
 namespace tdtk {
-
-constexpr int Q_BLOCK = 128;     // register-list and range kernels
-constexpr int Q_SD = 16;         // LDS stack levels (16 bytes each): 32 KB per 128-lane workgroup
-constexpr int Q_BLOCK_L = 64;    // the LDS-list k-NN kernel: 64 lanes x 64 slots x 12 bytes = 48 KB + 16 KB of stack
-constexpr int Q_MAX_BLOCKS = 2048;   // grid-stride cap (256 CUs x 8); the overflow area is sized for it
-
-// The argument block read through the kernarg segment pointer (as kernels.hip's kernarg_block): behind an opaque pointer of
-// the constant address space its fields are s_load'ed where they are used instead of being held in SGPRs across the walk
-// (the register lists leave no room for that).  The block is every kernel's only parameter.
-__device__ __forceinline__ const QueryArgs& q_args()
-{
-  typedef const QueryArgs __attribute__((address_space(4))) * kernarg_ptr;
-  kernarg_ptr p = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
-  asm volatile("" : "+s"(p));
-  return *(const QueryArgs*)p;
-}
-
-template <int BLOCK>
-__device__ __forceinline__ void stack_init(LaneStackQ<BLOCK, Q_SD>& st, uint4 (*lds)[BLOCK], const QueryArgs& a)
-{
-  st.l_e = &lds[0][threadIdx.x];
-  st.g_m2 = a.ovf_m2;
-  st.g_ref = a.ovf_ref;
-  st.gcol = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  st.gstride = (size_t)gridDim.x * BLOCK;
-  st.sp = 0;
-}
-
-// the opening of every kernel: the lane's stack and its grid-stride position i over the sorted queries (step T).  The loop
-// itself stays in the kernel, for (LaneQueries<B> q(a, s_stack); q.i < a.n; q.i += q.T): handed over as a lambda the same
-// body costs two to six vector registers in most kernels ("layout of the query code")
-template <int BLOCK>
-struct LaneQueries {
-  LaneStackQ<BLOCK, Q_SD> st;
-  size_t i, T;
-  __device__ __forceinline__ LaneQueries(const QueryArgs& a, uint4 (*lds)[BLOCK])
-  {
-    stack_init<BLOCK>(st, lds, a);
-    T = (size_t)gridDim.x * BLOCK;
-    i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-  }
-};
 
 // ---- the k-NN list, in registers (the LDS form: ListLds, query_lane.h) ---------------------------------------------
 // KC slots, every index static (nothing goes to scratch).  The list is the LAST k slots, k0 = KC - k;
@@ -571,12 +530,7 @@ __global__ void __launch_bounds__(256) k_cluster_pass(const QueryArgs a)
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------
-static uint32_t q_grid(size_t n, int block)
-{
-  const size_t nb = (n + block - 1) / block;
-  return (uint32_t)(nb < (size_t)Q_MAX_BLOCKS ? (nb ? nb : 1) : Q_MAX_BLOCKS);
-}
-
+// the stack overflow area of a launch over n queries, for both block sizes of query_dev.h (the forest's kernels included)
 size_t query_overflow_entries(size_t n, uint32_t max_depth)
 {
   // a path holds at most max_depth internal nodes, each pushes at most one entry

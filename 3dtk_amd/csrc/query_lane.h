@@ -110,7 +110,10 @@ __device__ __forceinline__ double box_dist(const KdNode& nd, const double qx, co
   return (ab < az) ? az : ab;
 }
 
-__device__ __forceinline__ void leaf_span(const QueryArgs& a, const uint32_t ref, uint32_t& start, uint32_t& count)
+// The tree a walk reads is a template parameter (TREE): any record with nodes, pts, leaf_tab, root_ref, cb and cmask --
+// QueryArgs itself, or one slot of the kd-forest (ForestSlot, forest_lane.h).  shape_walk alone needs QueryArgs (r2, node_r).
+template <class TREE>
+__device__ __forceinline__ void leaf_span(const TREE& a, const uint32_t ref, uint32_t& start, uint32_t& count)
 {
   const uint32_t v = ref & REF_VAL;
   if (a.leaf_tab) { const LeafEntry e = a.leaf_tab[v]; start = (uint32_t)e.start; count = (uint32_t)e.count; }
@@ -155,8 +158,15 @@ struct ListLds {
 };
 
 // ---- the walks -------------------------------------------------------------------------------------------------
-template <class LIST, class STACK>
-__device__ void knn_walk(const QueryArgs& a, const double qx, const double qy, const double qz, LIST& L, STACK& st)
+// The point policy (POINTS, the first template parameter of the list walks) decides which bucket points a walk sees and what
+// a list names them by.  The default: every point, by its slot in pts.  (The forest's: forest_lane.h.)
+struct AllBySlot {
+  static __device__ __forceinline__ bool sees(const KdPoint&) { return true; }
+  static __device__ __forceinline__ uint32_t name(const KdPoint&, const uint32_t slot) { return slot; }
+};
+
+template <class POINTS = AllBySlot, class TREE, class LIST, class STACK>
+__device__ void knn_walk(const TREE& a, const double qx, const double qy, const double qz, LIST& L, STACK& st)
 {
   uint32_t cur = a.root_ref;
   for (;;) {
@@ -165,7 +175,8 @@ __device__ void knn_walk(const QueryArgs& a, const double qx, const double qy, c
       leaf_span(a, cur, start, count);
       for (uint32_t i = 0; i < count; i++) {
         const KdPoint p = a.pts[start + i];
-        L.insert(dist2(p, qx, qy, qz), start + i);
+        if (!POINTS::sees(p)) continue;
+        L.insert(dist2(p, qx, qy, qz), POINTS::name(p, start + i));
       }
     } else {
       const KdNode nd = a.nodes[cur & REF_VAL];
@@ -191,9 +202,9 @@ __device__ void knn_walk(const QueryArgs& a, const double qx, const double qy, c
   }
 }
 
-// EMIT(point, slot, d2) for every point of the radius list, in the reference's visiting order
-template <class STACK, class EMIT>
-__device__ void range_walk(const QueryArgs& a, const double qx, const double qy, const double qz, const double r2, STACK& st,
+// EMIT(point, its name, d2) for every point of the radius list, in the reference's visiting order
+template <class POINTS = AllBySlot, class TREE, class STACK, class EMIT>
+__device__ void range_walk(const TREE& a, const double qx, const double qy, const double qz, const double r2, STACK& st,
                            EMIT& emit)
 {
   uint32_t cur = a.root_ref;
@@ -203,8 +214,9 @@ __device__ void range_walk(const QueryArgs& a, const double qx, const double qy,
       leaf_span(a, cur, start, count);
       for (uint32_t i = 0; i < count; i++) {
         const KdPoint p = a.pts[start + i];
+        if (!POINTS::sees(p)) continue;
         const double md = dist2(p, qx, qy, qz);
-        if (md < r2) emit(p, start + i, md);
+        if (md < r2) emit(p, POINTS::name(p, start + i), md);
       }
     } else {
       const KdNode nd = a.nodes[cur & REF_VAL];
@@ -228,8 +240,8 @@ __device__ void range_walk(const QueryArgs& a, const double qx, const double qy,
 }
 
 // k nearest within r2 (_KNNRangeSearch): knn_walk's list under range_walk's child order and plane test
-template <class LIST, class STACK>
-__device__ void knn_range_walk(const QueryArgs& a, const double qx, const double qy, const double qz, const double r2, LIST& L,
+template <class POINTS = AllBySlot, class TREE, class LIST, class STACK>
+__device__ void knn_range_walk(const TREE& a, const double qx, const double qy, const double qz, const double r2, LIST& L,
                                STACK& st)
 {
   uint32_t cur = a.root_ref;
@@ -239,9 +251,10 @@ __device__ void knn_range_walk(const QueryArgs& a, const double qx, const double
       leaf_span(a, cur, start, count);
       for (uint32_t i = 0; i < count; i++) {
         const KdPoint p = a.pts[start + i];
+        if (!POINTS::sees(p)) continue;
         const double md = dist2(p, qx, qy, qz);
         if (md >= r2) continue;
-        L.insert(md, start + i);
+        L.insert(md, POINTS::name(p, start + i));
       }
     } else {
       const KdNode nd = a.nodes[cur & REF_VAL];
@@ -424,13 +437,13 @@ __device__ void shape_walk(const QueryArgs& a, const double px, const double py,
   }
 }
 
-// segmentSearch_1NearestPoint: best / bslot are closest_d2 / the bucket slot of closest (0xFFFFFFFF: none)
-template <class STACK>
-__device__ void segment_nearest_walk(const QueryArgs& a, const Segment& sg, STACK& st, double& best,
-                                     uint32_t& bslot)
+// _FindClosest's loop (kdTreeImpl.h:345-383) from q: best is closest_d2, a point is taken when Dist2 < best (strict: the first
+// visited point wins a tie), the far child's myd*myd goes on the stack and is tested against the then-current best at the pop.
+// What differs between its users is a RULE: skip(point) -- a bucket point the walk does not look at; prune(node, its index) -- a
+// test of an internal node beside the box test; take(point, slot) -- notes the point that has just become the closest.
+template <class TREE, class RULE, class STACK>
+__device__ void nearest_walk(const TREE& a, const double qx, const double qy, const double qz, RULE& rule, STACK& st, double& best)
 {
-  const double md2 = a.r2;
-  const double maxd = __dsqrt_rn(md2);
   uint32_t cur = a.root_ref;
   for (;;) {
     if (cur & REF_LEAF) {
@@ -438,21 +451,18 @@ __device__ void segment_nearest_walk(const QueryArgs& a, const Segment& sg, STAC
       leaf_span(a, cur, start, count);
       for (uint32_t i = 0; i < count; i++) {
         const KdPoint p = a.pts[start + i];
-        if (sg.comp_d2(p.x, p.y, p.z) >= md2) continue;
-        const double nd2 = dist2(p, sg.px, sg.py, sg.pz);
-        if (nd2 < best) { best = nd2; bslot = start + i; }
+        if (rule.skip(p)) continue;
+        const double nd2 = dist2(p, qx, qy, qz);
+        if (nd2 < best) { best = nd2; rule.take(p, start + i); }
       }
     } else {
       const KdNode nd = a.nodes[cur & REF_VAL];
-      const double ap = box_dist(nd, sg.px, sg.py, sg.pz);
+      const double ap = box_dist(nd, qx, qy, qz);
       bool pruned = (ap >= 0.0 && ap * ap >= best);
-      if (!pruned) {
-        const double lim = a.node_r[cur & REF_VAL] + maxd;
-        pruned = sg.comp_d2(nd.cx, nd.cy, nd.cz) > lim * lim;
-      }
+      if (!pruned) pruned = rule.prune(nd, cur & REF_VAL);
       if (!pruned) {
         const uint32_t axis = ((nd.c1 >> 30) & 1u) | (((nd.c2 >> 30) & 1u) << 1);
-        const double pa = (axis == 0) ? sg.px : ((axis == 1) ? sg.py : sg.pz);
+        const double pa = (axis == 0) ? qx : ((axis == 1) ? qy : qz);
         const uint32_t r1 = nd.c1 & ~REF_AXIS, r2c = nd.c2 & ~REF_AXIS;
         const double myd = nd.splitval - pa;
         const bool first = myd >= 0.0;
@@ -471,6 +481,31 @@ __device__ void segment_nearest_walk(const QueryArgs& a, const Segment& sg, STAC
     }
     if (!more) break;
   }
+}
+
+// the two segment tests of segmentSearch_1NearestPoint as nearest_walk's rule
+struct SegmentRule {
+  const QueryArgs& a;
+  const Segment& sg;
+  const double md2, maxd;   // maxdist2, maxdist_d
+  uint32_t& bslot;
+  __device__ __forceinline__ bool skip(const KdPoint& p) const { return sg.comp_d2(p.x, p.y, p.z) >= md2; }
+  __device__ __forceinline__ bool prune(const KdNode& nd, const uint32_t node) const
+  {
+    const double lim = a.node_r[node] + maxd;
+    return sg.comp_d2(nd.cx, nd.cy, nd.cz) > lim * lim;
+  }
+  __device__ __forceinline__ void take(const KdPoint&, const uint32_t slot) const { bslot = slot; }
+};
+
+// segmentSearch_1NearestPoint: best / bslot are closest_d2 / the bucket slot of closest (0xFFFFFFFF: none)
+template <class STACK>
+__device__ void segment_nearest_walk(const QueryArgs& a, const Segment& sg, STACK& st, double& best,
+                                     uint32_t& bslot)
+{
+  const double md2 = a.r2;
+  SegmentRule rule{a, sg, md2, __dsqrt_rn(md2), bslot};
+  nearest_walk(a, sg.px, sg.py, sg.pz, rule, st, best);
 }
 
 // ---- collision detection along a trajectory (collision_model.cc) ----------------------------------------------------------

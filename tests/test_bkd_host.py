@@ -1,7 +1,8 @@
 """The dynamic kd-forest (BkdTree: tdtk_forest_*, 3dtk_amd.BkdTree): the CPU tier.  The model (tests/bkd_model.py) against the
 fixture k19_bkd.npz, which tests/golden/make_golden_bkd.py pins to the reference's compiled bkd.cc; the host-only insert plan
 (tdtk_forest_plan) against every layout of the fixture; the lane code of forest_lane.h compiled for the host, on kd_build.cpp's
-host trees, against the fixture's remove and query cases; the resource remarks of the forest kernels."""
+host trees, against the fixture's remove and query cases; the resource remarks of the forest kernels; and the forest's queries
+against the tree walks of query_lane.h on the same host tree, which pins that the point policy is all that separates them."""
 import ctypes as C
 import importlib.util
 import os
@@ -371,3 +372,187 @@ def test_lane_code_compiled_for_the_host_equals_the_fixture(tdtk, mk, fx, tmp_pa
         f.close()
         n += 1
     assert n >= 36
+
+
+# ---- the forest's queries are the tree walks under the point policy --------------------------------------------------------------
+# One host tree as a forest of one slot with an empty buffer, beside the same tree as QueryArgs: forest_knn / forest_fixed_range /
+# forest_find_closest of forest_lane.h against knn_walk / range_walk of query_lane.h under the default policy, the slots mapped
+# through orig.  kd_build.cpp packs the leaves of a cloud this small; `table` re-encodes the leaf references as leaf ids, as the
+# build does where start and count do not fit in 30 bits.
+_HOST_PAIR = r"""
+#include "forest_lane.h"
+struct HP { HostTree T; std::vector<int32_t> orig; ForestArgs f; };
+extern "C" void* hp_create(const double* xyz, int n, int bucket, int table) {
+  HP* h = new HP; std::string err;
+  if (!build_tree(xyz, (size_t)n, bucket, h->T, err) || h->T.table_mode) return nullptr;
+  HostTree& T = h->T;
+  if (table) {
+    auto by_id = [&](uint32_t ref) -> uint32_t {
+      if (!(ref & REF_LEAF)) return ref;
+      const uint32_t start = (ref & REF_VAL) >> T.cb;
+      for (uint32_t id = 0; id < T.leaf_tab.size(); id++)
+        if ((uint32_t)T.leaf_tab[id].start == start) return (ref & (REF_LEAF | REF_AXIS)) | id;
+      abort();
+    };
+    T.root_ref = by_id(T.root_ref);
+    for (KdNode& nd : T.nodes) { nd.c1 = by_id(nd.c1); nd.c2 = by_id(nd.c2); }
+    T.table_mode = true;
+  }
+  for (KdPoint& p : T.pts) { h->orig.push_back(p.orig); p.pad = FOREST_UNCLAIMED; }
+  h->f = ForestArgs{}; h->f.nslots = 1;
+  ForestSlot& d = h->f.slot[0];
+  d.nodes = T.nodes.data(); d.pts = T.pts.data(); d.leaf_tab = table ? T.leaf_tab.data() : nullptr;
+  d.root_ref = T.root_ref; d.cb = T.cb; d.cmask = (1u << T.cb) - 1; d.n = (uint32_t)n;
+  return h;
+}
+extern "C" void hp_destroy(void* p) { delete (HP*)p; }
+// dead [n] by input index: the forest sees the point removed; the tree walks below do not look at orig
+extern "C" void hp_mark_dead(void* p, const unsigned char* dead) {
+  HP* h = (HP*)p;
+  for (size_t s = 0; s < h->T.pts.size(); s++) h->T.pts[s].orig = dead[h->orig[s]] ? FOREST_DEAD : h->orig[s];
+}
+extern "C" void hp_knn(void* p, int forest, const double* q, int nq, int k, int* ids, double* d2) {
+  HP* h = (HP*)p;
+  QueryArgs a = host_args(h->T);
+  std::vector<double> ld(k); std::vector<uint32_t> ls(k);
+  for (int i = 0; i < nq; i++) {
+    ListLds<1> L; L.ld = ld.data(); L.ls = ls.data(); L.init(k);
+    HostStack st;
+    if (forest) forest_knn(h->f, q[3 * i], q[3 * i + 1], q[3 * i + 2], L, st);
+    else knn_walk(a, q[3 * i], q[3 * i + 1], q[3 * i + 2], L, st);
+    for (int j = 0; j < k; j++) {
+      const bool v = L.dist(j) >= 0.0;
+      ids[i * k + j] = !v ? -1 : forest ? (int)L.slot(j) : h->orig[L.slot(j)];
+      d2[i * k + j] = v ? L.dist(j) : -1.0;
+    }
+  }
+}
+extern "C" long hp_range(void* p, int forest, const double* q, int nq, double r2, long* off, int* ids, double* d2, long cap) {
+  HP* h = (HP*)p;
+  QueryArgs a = host_args(h->T);
+  long w = 0;
+  for (int i = 0; i < nq; i++) {
+    off[i] = w;
+    auto femit = [&](int32_t id, double md) { if (w < cap) { ids[w] = id; d2[w] = md; } ++w; };
+    auto temit = [&](const KdPoint&, uint32_t slot, double md) { if (w < cap) { ids[w] = h->orig[slot]; d2[w] = md; } ++w; };
+    HostStack st;
+    if (forest) forest_fixed_range(h->f, q[3 * i], q[3 * i + 1], q[3 * i + 2], r2, st, femit);
+    else range_walk(a, q[3 * i], q[3 * i + 1], q[3 * i + 2], r2, st, temit);
+  }
+  off[nq] = w;
+  return w;
+}
+extern "C" void hp_closest(void* p, const double* q, int nq, double md2, int* id, double* d2) {
+  HP* h = (HP*)p;
+  for (int i = 0; i < nq; i++) { HostStack st; forest_find_closest(h->f, q[3 * i], q[3 * i + 1], q[3 * i + 2], md2, st, id[i], d2[i]); }
+}
+"""
+
+
+class _Pair:
+    def __init__(self, L, pts, bucket, table):
+        self.L, self.pts = L, np.ascontiguousarray(pts)
+        self.h = L.hp_create(self.pts.ctypes.data, len(pts), bucket, int(table))
+        assert self.h
+
+    def close(self):
+        self.L.hp_destroy(self.h)
+
+    def mark_dead(self, dead):
+        dead = np.ascontiguousarray(dead, np.uint8)
+        self.L.hp_mark_dead(self.h, dead.ctypes.data)
+
+    def knn(self, forest, Q, k):
+        ids, d2 = np.empty((len(Q), k), np.int32), np.empty((len(Q), k))
+        self.L.hp_knn(self.h, int(forest), Q.ctypes.data, len(Q), k, ids.ctypes.data, d2.ctypes.data)
+        return ids, d2
+
+    def range(self, forest, Q, r2):
+        off, cap = np.zeros(len(Q) + 1, np.int64), len(Q) * len(self.pts)
+        ids, d2 = np.empty(cap, np.int32), np.empty(cap)
+        n = self.L.hp_range(self.h, int(forest), Q.ctypes.data, len(Q), r2, off.ctypes.data, ids.ctypes.data, d2.ctypes.data, cap)
+        assert n <= cap
+        return off, ids[:n], d2[:n]
+
+    def closest(self, Q, md2):
+        ids, d2 = np.empty(len(Q), np.int32), np.empty(len(Q))
+        self.L.hp_closest(self.h, Q.ctypes.data, len(Q), md2, ids.ctypes.data, d2.ctypes.data)
+        return ids, d2
+
+
+def _first_minimum(off, ids, d2):
+    """per list its first entry of smallest d2 (FindClosest takes a point on strict '<': the first visited wins a tie, and it visits
+    the range walk's nodes in the range walk's order), -1 / -1.0 for an empty list"""
+    bi, bd = np.full(len(off) - 1, -1, np.int32), np.full(len(off) - 1, -1.0)
+    for i in range(len(off) - 1):
+        if off[i + 1] > off[i]:
+            j = off[i] + int(np.argmin(d2[off[i]:off[i + 1]]))
+            bi[i], bd[i] = ids[j], d2[j]
+    return bi, bd
+
+
+def _filtered(off, ids, d2, keep):
+    m = keep[ids]
+    noff = np.concatenate([[0], np.cumsum([int(m[off[i]:off[i + 1]].sum()) for i in range(len(off) - 1)])]).astype(np.int64)
+    return noff, ids[m], d2[m]
+
+
+def test_forest_queries_are_the_tree_walks_under_the_point_policy(tmp_path):
+    mg = _load("make_golden_knn")
+    L = host_lane.build(_HOST_PAIR, tmp_path, "hp")
+    L.hp_create.restype = C.c_void_p
+    L.hp_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.hp_destroy.argtypes = [C.c_void_p]
+    L.hp_mark_dead.argtypes = [C.c_void_p, C.c_void_p]
+    L.hp_knn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    L.hp_range.restype = C.c_long
+    L.hp_range.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long]
+    L.hp_closest.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]
+    clouds = mg.k8_clouds()
+    checked = 0
+    for name in ("uniform", "duplicates"):
+        pts, Q, _, r2 = clouds[name]
+        pts, Q = np.ascontiguousarray(pts), np.ascontiguousarray(Q)
+        live = np.arange(len(pts)) % 2 == 0                          # every second point goes
+        every = np.broadcast_to(np.arange(len(pts)), (len(Q), len(pts)))
+        D = np.sort(np.where(live[None, :], mg.dist2(pts, Q[:, None, :], every), np.inf), axis=1)     # the live points by brute force
+        for table in (False, True):
+            t = _Pair(L, pts, 5, table)
+            full = {}
+            # nothing removed: the same rows, ids, distances and order
+            for k in (1, 10, 33):
+                fi, fd = t.knn(True, Q, k)
+                ti, td = t.knn(False, Q, k)
+                assert np.array_equal(fi, ti) and np.array_equal(fd, td), (name, table, k)
+                assert (fi[:, 0] >= 0).all()
+                checked += 1
+            for rad in (r2, 9.0 * r2):
+                full[rad] = t.range(False, Q, rad)
+                got = t.range(True, Q, rad)
+                assert all(np.array_equal(g, w) for g, w in zip(got, full[rad])), (name, table, rad)
+                assert len(full[rad][1]) > len(Q)
+                ci, cd = t.closest(Q, rad)
+                wi, wd = _first_minimum(*full[rad])
+                assert np.array_equal(ci, wi) and np.array_equal(cd, wd), (name, table, rad)
+                checked += 1
+            # every second point removed: the live subset of the same lists, and nothing else
+            t.mark_dead(~live)
+            for rad in (r2, 9.0 * r2):
+                want = _filtered(*full[rad], live)
+                got = t.range(True, Q, rad)
+                assert all(np.array_equal(g, w) for g, w in zip(got, want)), (name, table, rad)
+                assert 0 < len(want[1]) < len(full[rad][1])
+                ci, cd = t.closest(Q, rad)
+                wi, wd = _first_minimum(*want)
+                assert np.array_equal(ci, wi) and np.array_equal(cd, wd), (name, table, rad)
+                # the tree walk under the default policy still lists the removed points
+                assert all(np.array_equal(g, w) for g, w in zip(t.range(False, Q, rad), full[rad]))
+                checked += 1
+            for k in (1, 10, 33):
+                fi, fd = t.knn(True, Q, k)
+                assert (fi >= 0).all() and live[fi].all(), (name, table, k)
+                assert np.array_equal(fd, mg.dist2(pts, Q[:, None, :], fi)) and np.array_equal(fd, D[:, :k]), (name, table, k)
+                assert all(len(set(r)) == k for r in fi.tolist())
+                checked += 1
+            t.close()
+    assert checked == 2 * 2 * (3 + 2 + 2 + 3)
