@@ -47,6 +47,14 @@ class TreeInfo(C.Structure):
                 ("device_bytes", C.c_uint64), ("build_ms", C.c_double), ("upload_ms", C.c_double)]
 
 
+class OctreeInfo(C.Structure):
+    _fields_ = [("n_points", C.c_uint64), ("n_nodes", C.c_uint64), ("n_leaves", C.c_uint64),
+                ("max_depth", C.c_int32), ("largest_index", C.c_int32),
+                ("real_voxelSize", C.c_double), ("mult", C.c_double), ("add", C.c_double * 3),
+                ("center", C.c_double * 3), ("size", C.c_double), ("voxel_size", C.c_double),
+                ("earlystop", C.c_int32), ("levels", C.c_int32), ("device_bytes", C.c_uint64), ("build_ms", C.c_double)]
+
+
 class IcpParams(C.Structure):
     _fields_ = [("algo", C.c_int), ("pairing_mode", C.c_int), ("max_num_iterations", C.c_int),
                 ("max_dist_match2", C.c_double), ("epsilon_icp", C.c_double), ("quiet", C.c_int)]
@@ -69,6 +77,8 @@ EXPORTS = [
     "tdtk_cluster_radius", "tdtk_cluster_grid_cap", "tdtk_voxel_walk", "tdtk_peopleremover", "tdtk_peopleremover_timings",
     "tdtk_forest_create", "tdtk_forest_create_from_points", "tdtk_forest_destroy", "tdtk_forest_insert", "tdtk_forest_last_insert", "tdtk_forest_remove", "tdtk_forest_info",
     "tdtk_forest_collect", "tdtk_forest_find_closest", "tdtk_forest_knn", "tdtk_forest_fixed_range", "tdtk_forest_plan",
+    "tdtk_octree_create", "tdtk_octree_create_from_scan", "tdtk_octree_destroy", "tdtk_octree_get_info", "tdtk_octree_leaf_order", "tdtk_octree_node_table",
+    "tdtk_octree_find_closest", "tdtk_octree_find_closest_dev", "tdtk_octree_get_pt_pairs",
     "tdtk_get_pt_pairs", "tdtk_scan_create", "tdtk_scan_destroy", "tdtk_scan_size",
     "tdtk_scan_transform", "tdtk_scan_download", "tdtk_scan_pairs", "tdtk_align", "tdtk_icp_match", "tdtk_icp_match_rnd",
     "tdtk_lum_link", "tdtk_lum_links", "tdtk_links_pair_sums", "tdtk_lum_update_poses", "tdtk_lum_assemble_solve", "tdtk_point_point_error",
@@ -195,6 +205,16 @@ def lib():
     L.tdtk_normals_adaptive_apx_knn.argtypes = [_dp, C.c_size_t, C.c_int, C.c_int, _dp, C.c_double, C.c_int, _dp, _ip, _ip]
     L.tdtk_get_pt_pairs.argtypes = [C.c_void_p, _dp, _dp, _dp, C.c_size_t, C.c_size_t, C.c_int, C.c_int,
                                     C.c_double, C.c_uint32, _dp, _ip, _dp, _dp, _dp, C.POINTER(PairSums)]
+    L.tdtk_octree_create.argtypes = [_dp, C.c_size_t, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    L.tdtk_octree_create_from_scan.argtypes = [C.c_void_p, C.c_double, C.c_int, C.POINTER(C.c_void_p)]
+    L.tdtk_octree_destroy.argtypes = [C.c_void_p]
+    L.tdtk_octree_destroy.restype = None
+    L.tdtk_octree_get_info.argtypes = [C.c_void_p, C.POINTER(OctreeInfo)]
+    L.tdtk_octree_leaf_order.argtypes = [C.c_void_p, _ip]
+    L.tdtk_octree_node_table.argtypes = [C.c_void_p, _u32p, C.c_size_t, _u64p]
+    L.tdtk_octree_find_closest.argtypes = [C.c_void_p, _dp, C.c_size_t, C.c_double, _ip, _dp]
+    L.tdtk_octree_find_closest_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.tdtk_octree_get_pt_pairs.argtypes = L.tdtk_get_pt_pairs.argtypes
     L.tdtk_scan_create.argtypes = [_dp, _dp, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
     L.tdtk_scan_destroy.argtypes = [C.c_void_p]
     L.tdtk_scan_destroy.restype = None

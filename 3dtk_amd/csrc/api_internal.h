@@ -220,6 +220,10 @@ int scan_pass(Ctx* c, const tdtk_tree* model, const double* A16, tdtk_scan* data
 int scan_idx_to_host(Ctx* c, const tdtk_tree* model, tdtk_scan* data, int32_t* idx_out);
 // api_scan.cpp
 int queue_scan_moves(Ctx* c, const std::vector<tdtk_scan*>& moved);
+using PairsPass = std::function<int(tdtk_scan*, int32_t*, tdtk_pair_sums*)>;
+int get_pt_pairs_over(const tdtk_tree* t, const PairsPass& pairs, const double A[16], const double* xyz_r, const double* normal_r,
+                      size_t start, size_t end, int rnd, int pmode, double maxd2, uint32_t want,
+                      int32_t* idx_out, double* p1_out, double* p2_out, double* pn_out, tdtk_pair_sums* sums);
 
 }  // namespace tdtk
 

@@ -210,10 +210,16 @@ int tdtk_point_point_error(const tdtk_tree* model, const double A[16], tdtk_scan
   return TDTK_OK;
 }
 
-int tdtk_get_pt_pairs(const tdtk_tree* t, const double A[16], const double* xyz_r, const double* normal_r,
+}  // extern "C"
+
+namespace tdtk {
+
+// SearchTree::getPtPairs around any tree: `t` gives the device, the leaf-ordered points (dev.pts) and the accumulation point;
+// `pairs` is the whole-scan pass over the resident queries (tdtk_scan_pairs for the k-d tree, the octree's own for BOctTree)
+// and leaves its hits in WS_KPOS
+int get_pt_pairs_over(const tdtk_tree* t, const PairsPass& pairs, const double A[16], const double* xyz_r, const double* normal_r,
                       size_t start, size_t end, int rnd, int pmode, double maxd2, uint32_t want,
-                      const double* lum_D, int32_t* idx_out, double* p1_out, double* p2_out,
-                      double* pn_out, tdtk_pair_sums* sums)
+                      int32_t* idx_out, double* p1_out, double* p2_out, double* pn_out, tdtk_pair_sums* sums)
 {
   if (!t || !A || !xyz_r || !sums || end < start) { set_error("bad argument"); return TDTK_EINVAL; }
   if ((pmode == 1 || pmode == 2 || (want & TDTK_WANT_NAPX)) && !normal_r) {
@@ -250,7 +256,7 @@ int tdtk_get_pt_pairs(const tdtk_tree* t, const double A[16], const double* xyz_
   const bool want_pairs = p1_out || p2_out || pn_out;
   if (rnd > 1 || (!idx_out && want_pairs)) { idx_local.resize(n ? n : 1); idx = idx_local.data(); }
   else idx = idx_out;
-  rc = tdtk_scan_pairs(t, A, sc, pmode, maxd2, want, lum_D, idx, sums);
+  rc = pairs(sc, idx, sums);
   if (rc) { tdtk_scan_destroy(sc); return rc; }
   sums->n_queries = n;
   if (want_pairs && n && sums->n) {
@@ -297,6 +303,19 @@ int tdtk_get_pt_pairs(const tdtk_tree* t, const double A[16], const double* xyz_
   if (rnd > 1 && idx_out)
     for (size_t i = 0; i < n; i++) idx_out[kept_pos[i]] = idx[i];
   return TDTK_OK;
+}
+
+}  // namespace tdtk
+
+extern "C" {
+
+int tdtk_get_pt_pairs(const tdtk_tree* t, const double A[16], const double* xyz_r, const double* normal_r,
+                      size_t start, size_t end, int rnd, int pmode, double maxd2, uint32_t want,
+                      const double* lum_D, int32_t* idx_out, double* p1_out, double* p2_out,
+                      double* pn_out, tdtk_pair_sums* sums)
+{
+  const PairsPass pass = [&](tdtk_scan* sc, int32_t* idx, tdtk_pair_sums* o) { return tdtk_scan_pairs(t, A, sc, pmode, maxd2, want, lum_D, idx, o); };
+  return get_pt_pairs_over(t, pass, A, xyz_r, normal_r, start, end, rnd, pmode, maxd2, want, idx_out, p1_out, p2_out, pn_out, sums);
 }
 
 }  // extern "C"

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _capi as capi
 _dp_type = lambda: C.POINTER(C.c_double)()
-from ._capi import (lib, check, dptr, iptr, f64, PairSums, IcpParams, IcpResult, TreeInfo,
+from ._capi import (lib, check, dptr, iptr, f64, PairSums, IcpParams, IcpResult, TreeInfo, OctreeInfo,
                     ALGO_QUAT, ALGO_SVD, ALGO_APX, ALGO_NAPX, WANT_APX, WANT_NAPX, WANT_LUM)
 
 
@@ -447,6 +447,102 @@ class KDtree:
         check(lib().tdtk_get_pt_pairs(self._h, dptr(A), dptr(xyz_r), dptr(nr), startindex, endindex,
                                       int(rnd), int(pairing_mode), float(max_dist_match2), int(want),
                                       dptr(D), iptr(idx), dptr(p1), dptr(p2), dptr(pn), C.byref(s)))
+        out = _sums_dict(s)
+        out["idx"] = idx
+        out["_raw"] = s
+        if want_pairs:
+            k = out["n"]
+            out["p1"], out["p2"], out["pn"] = p1[:k], p2[:k], pn[:k]
+        return out
+
+
+# ---------------------------------------------------------------------------------------
+# BOctTree<double> : SearchTree   (include/slam6d/Boctree.h; `slam6D -t 2`, basicScan.cc:714-719)
+# ---------------------------------------------------------------------------------------
+class BOctTree:
+    """BOctTree<double>(pts, n, voxelSize, PointType(), earlystop) as a search tree; the defaults are those of
+    BasicScan::createSearchTreePrivate.  pts is copied and uploaded, the tree is built on the device."""
+
+    def __init__(self, pts, voxelSize=10.0, earlystop=True, device=0):
+        pts = f64(pts).reshape(-1, 3)
+        self.n = len(pts)
+        self.device = device
+        h = C.c_void_p()
+        check(lib().tdtk_octree_create(dptr(pts), len(pts), float(voxelSize), int(bool(earlystop)), int(device), C.byref(h)))
+        self._h = h
+
+    @classmethod
+    def from_scan(cls, scan_handle, n, voxelSize=10.0, earlystop=True, device=0):
+        """the tree over a resident scan's original points, built device to device (tdtk_octree_create_from_scan)"""
+        self = cls.__new__(cls)
+        self.n = n
+        self.device = device
+        h = C.c_void_p()
+        check(lib().tdtk_octree_create_from_scan(scan_handle, float(voxelSize), int(bool(earlystop)), C.byref(h)))
+        self._h = h
+        return self
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            try:
+                lib().tdtk_octree_destroy(h)
+            except Exception:      # interpreter shutdown: module globals are already gone
+                pass
+            self._h = None
+
+    def info(self):
+        """init()'s scalars (max_depth, real_voxelSize, mult, add, largest_index), the root cube and countNodes /
+        countOctLeaves / countPoints as n_nodes / n_leaves / n_points"""
+        oi = OctreeInfo()
+        check(lib().tdtk_octree_get_info(self._h, C.byref(oi)))
+        return {k: (np.array(getattr(oi, k)) if k in ("add", "center") else getattr(oi, k)) for k, _ in OctreeInfo._fields_}
+
+    def leaf_order(self):
+        """AllPoints (Boctree.h:708-740) as indices into pts: the leaves depth-first, a leaf's points in its own order"""
+        order = np.empty(self.n, np.int32)
+        check(lib().tdtk_octree_leaf_order(self._h, iptr(order)))
+        return order
+
+    def node_table(self):
+        """tdtk_octree_node_table: uint32 [slots][4] = (valid | leaf << 8, first child's slot, start, count)"""
+        slots = C.c_uint64(0)
+        check(lib().tdtk_octree_node_table(self._h, None, 0, C.byref(slots)))
+        table = np.empty((int(slots.value), 4), np.uint32)
+        check(lib().tdtk_octree_node_table(self._h, table.ctypes.data_as(C.POINTER(C.c_uint32)), len(table), C.byref(slots)))
+        return table
+
+    def FindClosest(self, p, maxdist2, threadNum=0):
+        """Boctree.h:1573-1640.  Returns the index of the point the reference returns, or None (reference: NULL)."""
+        idx, _ = self.FindClosestBatch(np.asarray(p, dtype=np.float64).reshape(1, 3), maxdist2)
+        return None if idx[0] < 0 else int(idx[0])
+
+    def FindClosestBatch(self, q, maxdist2):
+        """tdtk_octree_find_closest: (idx [K], d2 [K]); -1 / maxdist2 where the reference returns NULL"""
+        q = f64(q).reshape(-1, 3)
+        idx = np.empty(len(q), np.int32)
+        d2 = np.empty(len(q), np.float64)
+        check(lib().tdtk_octree_find_closest(self._h, dptr(q), len(q), float(maxdist2), iptr(idx), dptr(d2)))
+        return idx, d2
+
+    def getPtPairs(self, source_alignxf, xyz_r, normal_r=None, startindex=0, endindex=None,
+                   thread_num=0, rnd=0, max_dist_match2=625.0, pairing_mode=0, want=0, lum_D=None,
+                   want_pairs=True):
+        """SearchTree::getPtPairs (searchTree.cc:92-189) over the octree: the dict KDtree.getPtPairs returns"""
+        xyz_r = f64(xyz_r).reshape(-1, 3)
+        endindex = len(xyz_r) if endindex is None else endindex
+        n = endindex - startindex
+        A = f64(source_alignxf, 16)
+        nr = f64(normal_r).reshape(-1, 3) if normal_r is not None else None
+        idx = np.empty(n, np.int32)
+        p1 = np.empty((n, 3)) if want_pairs else None
+        p2 = np.empty((n, 3)) if want_pairs else None
+        pn = np.empty((n, 3)) if want_pairs else None
+        s = PairSums()
+        D = f64(lum_D, 6) if lum_D is not None else None
+        check(lib().tdtk_octree_get_pt_pairs(self._h, dptr(A), dptr(xyz_r), dptr(nr), startindex, endindex,
+                                             int(rnd), int(pairing_mode), float(max_dist_match2), int(want),
+                                             dptr(D), iptr(idx), dptr(p1), dptr(p2), dptr(pn), C.byref(s)))
         out = _sums_dict(s)
         out["idx"] = idx
         out["_raw"] = s

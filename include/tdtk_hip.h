@@ -363,6 +363,64 @@ int tdtk_forest_fixed_range(tdtk_forest* f, const double* q, size_t K, double sq
  * buffer is the old one (if it stays) followed by the new points [a, b); *merges (nullable): the merges this stands for.  */
 int tdtk_forest_plan(const uint64_t* counts, int nslots, uint64_t fill, int bucket, uint64_t m, int* nslots_out, uint64_t* counts_out,
                      int64_t* segs, size_t cap_segs, size_t* nsegs, uint64_t buf_out[3], uint64_t* merges);
+
+/* ---- BOctTree<double> as a search tree (`slam6D -t 2`; include/slam6d/Boctree.h).  Built on the device from host points;
+ * the node table's layout is this library's, the tree it stands for -- which cells are leaves, the order of the leaves and of
+ * the points inside a leaf -- is the reference's.  An octree belongs to one host thread at a time. */
+typedef struct tdtk_octree tdtk_octree;
+typedef struct tdtk_octree_info {
+  uint64_t n_points;        /* countPoints()                                                       Boctree.h:447  */
+  uint64_t n_nodes;         /* countNodes(): inner nodes, the root included                        Boctree.h:444  */
+  uint64_t n_leaves;        /* countOctLeaves()                                                    Boctree.h:446  */
+  int32_t max_depth;        /* init(): 1 + halvings of the root size until it is <= voxelSize      Boctree.h:335-340 */
+  int32_t largest_index;    /* child_bit_depth[0] * 2 - 1                                          Boctree.h:355  */
+  double real_voxelSize, mult, add[3];   /* bit-equal to init()'s                                  Boctree.h:350-353 */
+  double center[3], size;   /* the root cube (size: half edge, largest half extent + 1.0)          Boctree.h:249-255 */
+  double voxel_size;
+  int32_t earlystop, levels;   /* levels: depth of the deepest possible leaf, <= 21 */
+  uint64_t device_bytes;
+  double build_ms;
+} tdtk_octree_info;
+/* BOctTree<double>(pts, n, voxelSize, PointType(), earlystop) (Boctree.h:224-270; branch :1164-1195, countPointsAndQueueFast
+ * :1267-1301, init :333-356) as BasicScan::createSearchTreePrivate builds it with voxelSize 10.0 and earlystop true
+ * (basicScan.cc:714-719): a cell is a leaf when its size is <= voxelSize or, with earlystop, when it holds <= 10 points.
+ * xyz [n][3] host memory.  Errors: n == 0, NULL xyz / out, voxel_size not > 0, non-finite coordinates (TDTK_EINVAL -- n == 0
+ * is a deviation: the reference builds an empty root that no search can use); more than 21 levels (TDTK_EUNSUP, the bound of
+ * tdtk_reduce_octree's 64-bit cell keys).                                                                                  */
+int tdtk_octree_create(const double* xyz, size_t n, double voxel_size, int earlystop, int device, tdtk_octree** out);
+/* the same over a resident scan's points (its original ones, as tdtk_tree_create_from_scan); indices are the scan's caller order */
+int tdtk_octree_create_from_scan(const tdtk_scan* scan, double voxel_size, int earlystop, tdtk_octree** out);
+void tdtk_octree_destroy(tdtk_octree* t);
+int tdtk_octree_get_info(const tdtk_octree* t, tdtk_octree_info* info);
+/* diagnostic: the tree's points in leaf order (AllPoints, Boctree.h:708-740, as indices into the caller's xyz); order [n] */
+int tdtk_octree_leaf_order(const tdtk_octree* t, int32_t* order);
+/* diagnostic: the node table, four 32-bit words per slot = { valid | leaf << 8, first child's slot, start, count } -- the
+ * root in slot 0, then depth by depth, a depth in depth-first order; child ci of a node is slot first + popcount(valid &
+ * ((1 << ci) - 1)); (start, count) is the node's run in leaf order.  *slots = n_nodes + n_leaves is always set; table
+ * (nullable) [cap][4] is filled when cap >= *slots (else TDTK_EINVAL).                                                  */
+int tdtk_octree_node_table(const tdtk_octree* t, uint32_t* table, size_t cap, uint64_t* slots);
+/* batched BOctTree::FindClosest (Boctree.h:1573-1681; findClosestInLeaf :1361-1379) with threadNum-private state: q [K][3],
+ * idx [K] the caller's index of the returned point or -1, d2 (nullable) [K] its Dist2 (maxdist2 when there is none).  This
+ * is NOT the nearest point in general, and not the k-d tree's answer: a point accepted with Dist2 <= 0.0001 ends the search
+ * although a nearer one may follow; at most 10 000 leaves are scanned per query, later ones are skipped; ties go to the
+ * first point in octree order; the search prunes in whole voxels of real_voxelSize.
+ * The reference converts (q + add) * mult and sqrt(maxdist2) * mult + 1 to int.  Where one of these values of the batch is
+ * not within +-2^30 (a NaN included; a negative maxdist2 gives one) that conversion or the sums formed from it are undefined
+ * in C++: the call returns TDTK_EUNSUP for the whole batch and writes nothing.                                            */
+int tdtk_octree_find_closest(const tdtk_octree* t, const double* q, size_t K, double maxdist2, int32_t* idx, double* d2);
+/* the same with device pointers (d_q [K][3], d_idx [K], d_d2 [K] nullable), ordered on `stream` (NULL: the calling thread's
+ * own stream, and the call returns when the results are there).  The range check needs one look at the device.         */
+int tdtk_octree_find_closest_dev(const tdtk_octree* t, const double* d_q, size_t K, double maxdist2, int32_t* d_idx, double* d_d2,
+                                 void* stream);
+/* SearchTree::getPtPairs (searchTree.cc:92-189) over the octree: tdtk_get_pt_pairs's arguments and results, FindClosest
+ * being the octree's.  pairing_mode TDTK_CLOSEST_POINT and TDTK_CLOSEST_PLANE_SIMPLE; TDTK_CLOSEST_POINT_ALONG_NORMAL_SIMPLE
+ * returns TDTK_EUNSUP (BOctTree has no FindClosestAlongDir of its own, it inherits SearchTree's).  The range rule of
+ * tdtk_octree_find_closest applies to the queries after their transform into the tree's frame.                          */
+int tdtk_octree_get_pt_pairs(const tdtk_octree* t, const double source_alignxf[16], const double* xyz_r, const double* normal_r,
+                             size_t start, size_t end, int rnd, int pairing_mode, double max_dist_match2, uint32_t want,
+                             const double* lum_D /*[6] or NULL*/, int32_t* idx_out, double* p1_out, double* p2_out,
+                             double* pn_out, tdtk_pair_sums* sums);
+
 /* calculateNormalsKNN (normals.cc:442-516; calculateNormal :518-558): a KDtree(points, bucket) and, for every point, its
  * k nearest neighbours (itself included), their mean and covariance, the eigenvector of the smallest eigenvalue
  * (newmat EigenValues), oriented so that n . (p - rPos) >= 0, normalised.  normals_out [n][3] in point order (the

@@ -50,6 +50,10 @@ behind it, next to tdtk_tree_create over all the points so far -- what a caller 
 of the 1M points at maxdist2 = 625, k-NN at k = 10 and the 20.6-neighbour radius, each next to the same call on one tree over
 the same points; then 10 000 removes (the second batch of two, so that the first warms the code).
 
+--only-octree runs the octree search tree (3dtk_amd.BOctTree, tdtk_octree_*) alone: FindClosestBatch of 1M queries at maxdist2
+= 625 on a 1M-point uniform cloud (density 1), on the octree (voxel 10, earlystop) and on the k-d tree (bucket 20) -- five runs
+each, alternating between the two trees, min / max / median; both builds; whether the two answers agree.
+
 Kernel times: run the same command under `rocprofv3 --kernel-trace --stats` (k_knn_reg, k_range_count / k_range_fill,
 k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest, k_knn_adaptive_reg / k_knn_adaptive_lds, k_ann_adaptive, k_knnr_reg / k_knnr_lds,
 k_collide_mark, k_collide_depth_axis)."""
@@ -456,6 +460,39 @@ def forest_legs(tdtk, reps):
     return out
 
 
+def octree_legs(tdtk, runs=5):
+    """FindClosestBatch on the octree (BOctTree at the reference's voxel 10 with earlystop) and on the k-d tree (bucket 20):
+    the same 1M-point uniform cloud (density 1), the same 1M queries (the points moved by N(0, 0.3)), maxdist2 625.  Five
+    runs each, alternating between the two trees; end to end on the host clock and the search kernel from HIP events"""
+    rng = np.random.default_rng(2033)
+    pts = rng.uniform(-50, 50, (1_000_000, 3))
+    q = pts + rng.normal(0.0, 0.3, pts.shape)
+    t0 = time.perf_counter()
+    oc = tdtk.BOctTree(pts)
+    out = {"octree_build_ms_cold": round((time.perf_counter() - t0) * 1e3, 3)}
+    out["octree_build"] = timed(lambda: tdtk.BOctTree(pts), 3)
+    out["tree_build"] = timed(lambda: tdtk.KDtree(pts, 20), 3)
+    kd = tdtk.KDtree(pts, 20)
+    info = oc.info()
+    out["octree_info"] = {k: info[k] for k in ("n_nodes", "n_leaves", "levels", "max_depth", "device_bytes")}
+    oi, od = oc.FindClosestBatch(q, 625.0)             # warm: code objects, workspaces -- and the answers
+    ki, kd2 = kd.FindClosestBatch(q, 625.0)
+    same = np.array_equal(oi, ki)
+    out["octree_equals_tree"] = bool(same)             # (a uniform cloud: no ties; a query within 0.01 of a point may differ)
+    if not same:
+        out["octree_differs_at"] = int((oi != ki).sum())
+        assert (od[oi != ki] <= 0.0001).all()
+    ts = {"octree": [], "tree": []}
+    for _ in range(runs):
+        for tag, t in (("octree", oc), ("tree", kd)):
+            t0 = time.perf_counter()
+            t.FindClosestBatch(q, 625.0)
+            ts[tag].append((time.perf_counter() - t0) * 1e3)
+    for tag, v in ts.items():
+        out["%s_find_closest_1M" % tag] = {"min_ms": round(min(v), 3), "max_ms": round(max(v), 3), "median_ms": round(float(np.median(v)), 3)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000000,10000000")
@@ -474,6 +511,7 @@ def main():
     ap.add_argument("--only-clusters", action="store_true", help="those legs alone")
     ap.add_argument("--only-peopleremover", action="store_true", help="dynamic-object removal on a synthetic room, alone")
     ap.add_argument("--only-forest", action="store_true", help="the dynamic kd-forest against rebuilds and the single tree, alone")
+    ap.add_argument("--only-octree", action="store_true", help="FindClosestBatch on the octree and on the k-d tree, alone")
     args = ap.parse_args()
     tdtk = importlib.import_module("3dtk_amd")
     if tdtk.device_count() < 1:
@@ -485,6 +523,10 @@ def main():
         return
     if args.only_forest:
         out.update(forest_legs(tdtk, args.reps))
+        print(json.dumps(out))
+        return
+    if args.only_octree:
+        out.update(octree_legs(tdtk))
         print(json.dumps(out))
         return
     rng = np.random.default_rng(2024)
