@@ -80,7 +80,7 @@ EXPORTS = [
     "tdtk_octree_create", "tdtk_octree_create_from_scan", "tdtk_octree_destroy", "tdtk_octree_get_info", "tdtk_octree_leaf_order", "tdtk_octree_node_table",
     "tdtk_octree_find_closest", "tdtk_octree_find_closest_dev", "tdtk_octree_get_pt_pairs",
     "tdtk_get_pt_pairs", "tdtk_scan_create", "tdtk_scan_destroy", "tdtk_scan_size",
-    "tdtk_scan_transform", "tdtk_scan_download", "tdtk_scan_pairs", "tdtk_align", "tdtk_icp_match", "tdtk_icp_match_rnd",
+    "tdtk_scan_transform", "tdtk_scan_download", "tdtk_scan_pairs", "tdtk_align", "tdtk_icp_match", "tdtk_icp_match_rnd", "tdtk_icp_match_octree", "tdtk_icp_match_octree_rnd",
     "tdtk_lum_link", "tdtk_lum_links", "tdtk_links_pair_sums", "tdtk_lum_update_poses", "tdtk_lum_assemble_solve", "tdtk_point_point_error",
     "tdtk_graph_block_doubles", "tdtk_graph_link_blocks", "tdtk_graph_solve_update", "tdtk_scans_transform2", "tdtk_solve_spd",
     "tdtk_solve_chol_upper", "tdtk_invert", "tdtk_reduce_octree", "tdtk_reduce_octree_nrpts", "tdtk_normals_apx_knn", "tdtk_scan_calc_normals", "tdtk_last_kernel_ms", "tdtk_count_visits",
@@ -229,6 +229,8 @@ def lib():
                                  C.POINTER(IcpResult), _dp, C.c_int]
     L.tdtk_icp_match_rnd.argtypes = [C.c_void_p, _dp, C.c_void_p, _dp, _dp, C.POINTER(IcpParams), C.c_int,
                                      C.POINTER(IcpResult), _dp, C.c_int]
+    L.tdtk_icp_match_octree.argtypes = L.tdtk_icp_match.argtypes
+    L.tdtk_icp_match_octree_rnd.argtypes = L.tdtk_icp_match_rnd.argtypes
     L.tdtk_lum_link.argtypes = [C.c_void_p, _dp, C.c_void_p, C.c_double, _dp, _dp, _u64p, _dp]
     L.tdtk_lum_links.argtypes = [C.c_int, C.POINTER(C.c_void_p), _dp, C.POINTER(C.c_void_p), C.c_double, _dp,
                                  _dp, _u64p, _dp]

@@ -1,5 +1,6 @@
-// icp6D::match on a resident scan: the stepped loop over scan_pass (api_search.cpp), its index hashes and -R keep-masks, and
-// the lab library's loop without the host in it.
+// icp6D::match on a resident scan: the stepped loop over scan_pass (api_search.cpp) -- or over another search tree's pass
+// (icp_match_loop; the octree's is in api_octree.cpp) --, its index hashes and -R keep-masks, and the lab library's loop without
+// the host in it.
 #include "api_internal.h"
 
 using namespace tdtk;
@@ -221,24 +222,14 @@ extern "C" int tdtk_lab_icp_device_solve(int device, const double acc17[17], con
 }
 #endif
 
-static int icp_match_impl(const tdtk_tree* model, const double model_dalignxf[16], tdtk_scan* data,
-                          double data_transMat[16], double data_dalignxf[16], const tdtk_icp_params* prm, int rnd,
-                          tdtk_icp_result* res, double* trace, int trace_cap);
-int tdtk_icp_match(const tdtk_tree* model, const double model_dalignxf[16], tdtk_scan* data,
-                   double data_transMat[16], double data_dalignxf[16], const tdtk_icp_params* prm,
-                   tdtk_icp_result* res, double* trace, int trace_cap)
-{
-  return icp_match_impl(model, model_dalignxf, data, data_transMat, data_dalignxf, prm, 1, res, trace, trace_cap);
-}
-int tdtk_icp_match_rnd(const tdtk_tree* model, const double model_dalignxf[16], tdtk_scan* data,
-                       double data_transMat[16], double data_dalignxf[16], const tdtk_icp_params* prm, int rnd,
-                       tdtk_icp_result* res, double* trace, int trace_cap)
-{
-  return icp_match_impl(model, model_dalignxf, data, data_transMat, data_dalignxf, prm, rnd, res, trace, trace_cap);
-}
-static int icp_match_impl(const tdtk_tree* model, const double model_dalignxf[16], tdtk_scan* data,
-                          double data_transMat[16], double data_dalignxf[16], const tdtk_icp_params* prm, int rnd,
-                          tdtk_icp_result* res, double* trace, int trace_cap)
+}  // extern "C"
+
+// The loop of both search trees.  other == nullptr: the k-d tree `model` (tdtk_icp_match, tdtk_icp_match_rnd), every pass a
+// scan_pass; else the passes are other->pass (api_internal.h) and nothing of the k-d walk's state -- warm start, certificates,
+// cost order, the lab's device loop -- is used or left behind.
+int tdtk::icp_match_loop(const tdtk_tree* model, const IcpTreePass* other, const double model_dalignxf[16], tdtk_scan* data,
+                         double data_transMat[16], double data_dalignxf[16], const tdtk_icp_params* prm, int rnd,
+                         tdtk_icp_result* res, double* trace, int trace_cap)
 {
   if (!model || !model_dalignxf || !data || !prm || !res) { set_error("NULL argument"); return TDTK_EINVAL; }
   if (prm->max_dist_match2 < 0.0 || prm->max_num_iterations < 0) {
@@ -258,9 +249,10 @@ static int icp_match_impl(const tdtk_tree* model, const double model_dalignxf[16
   }
   const int pmode = prm->pairing_mode;
   if ((pmode != 0 || algo == TDTK_ALGO_NAPX) && !data->nx) { set_error("normals required"); return TDTK_EINVAL; }
+  int rc;
+  if (other && (rc = other->check(pmode, prm->max_dist_match2))) return rc;
   Ctx* c;
-  int rc = get_ctx(model->device, &c);
-  if (rc) return rc;
+  if ((rc = get_ctx(model->device, &c))) return rc;
   std::memset(res, 0, sizeof *res);
   if (prm->max_num_iterations == 0 || data->N == 0) return TDTK_OK;  // icp6D.cc:112-114
 
@@ -291,7 +283,7 @@ static int icp_match_impl(const tdtk_tree* model, const double model_dalignxf[16
   const bool cert_ok = [] { const char* e = getenv("TDTK_CERT_SKIP"); return !(e && e[0] == '0'); }();
 #ifdef TDTK_LAB
   // lab: the small-scan loop that runs without the host (see icp_device_loop): -a 1, closest points, every point a candidate
-  if (icp_loop_ahead() > 0 && algo == TDTK_ALGO_QUAT && pmode == 0 && want == 0u && rnd <= 1 && !hashing && !c->counting &&
+  if (!other && icp_loop_ahead() > 0 && algo == TDTK_ALGO_QUAT && pmode == 0 && want == 0u && rnd <= 1 && !hashing && !c->counting &&
       !kernel_timing() && fuse_mode(data->N) == 4 && search_multi_class(data->N) == 10 && search_fused_rows(data->N) <= (uint32_t)ICP_LOOP_MAX_ROWS) {
     IcpLoopOut o;
     if ((rc = icp_device_loop(c, model, model_dalignxf, data, prm, warm_ok, data_transMat, data_dalignxf, res, trace, trace_cap, o))) return rc;
@@ -319,9 +311,14 @@ static int icp_match_impl(const tdtk_tree* model, const double model_dalignxf[16
     // (the warm start stays exact under -R: WS_KPOS holds -1 for whoever was not drawn last time -- a cold start --, and for
     // the others a point of THIS tree, whose distance bounds the nearest neighbour's however the scan has moved since)
     if (!resume_with_acc) {
-      rc = scan_pass(c, model, model_dalignxf, data, pmode, prm->max_dist_match2, want, nullptr,
-                     have_pending ? pend : nullptr, true, acc, shift, iter > 0 && warm_ok, skip,
-                     cert_ok && iter > 0 && rnd <= 1);
+      if (other) {
+        rc = other->pass(have_pending ? pend : nullptr, skip, want, acc, shift);
+        if (rc) res->iterations = iter;      // (the scan and the matrices hold the iterations before this one, all of them)
+      } else {
+        rc = scan_pass(c, model, model_dalignxf, data, pmode, prm->max_dist_match2, want, nullptr,
+                       have_pending ? pend : nullptr, true, acc, shift, iter > 0 && warm_ok, skip,
+                       cert_ok && iter > 0 && rnd <= 1);
+      }
       if (rc) return rc;
       have_pending = false;
     }
@@ -394,6 +391,21 @@ static int icp_match_impl(const tdtk_tree* model, const double model_dalignxf[16
   res->sums_ms = sums_total;
   if (!prm->quiet) std::printf("TIME  %ld   ITER %d\n", (long)res->total_ms, iter);
   return TDTK_OK;
+}
+
+extern "C" {
+
+int tdtk_icp_match(const tdtk_tree* model, const double model_dalignxf[16], tdtk_scan* data,
+                   double data_transMat[16], double data_dalignxf[16], const tdtk_icp_params* prm,
+                   tdtk_icp_result* res, double* trace, int trace_cap)
+{
+  return icp_match_loop(model, nullptr, model_dalignxf, data, data_transMat, data_dalignxf, prm, 1, res, trace, trace_cap);
+}
+int tdtk_icp_match_rnd(const tdtk_tree* model, const double model_dalignxf[16], tdtk_scan* data,
+                       double data_transMat[16], double data_dalignxf[16], const tdtk_icp_params* prm, int rnd,
+                       tdtk_icp_result* res, double* trace, int trace_cap)
+{
+  return icp_match_loop(model, nullptr, model_dalignxf, data, data_transMat, data_dalignxf, prm, rnd, res, trace, trace_cap);
 }
 
 }  // extern "C"

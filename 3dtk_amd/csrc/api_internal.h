@@ -119,6 +119,7 @@ struct Ctx {
   //  groups -- device_build_tree may return with its last kernels still running, see build.hip "no_last_look")
   static constexpr int PIN_BOX = 128;      // 7 doubles: the root bounding box and the non-finite flag (tree_from_device_points)
   static constexpr int PIN_GROUPS = 140;   // 1 uint32: groups of the padded layout (tree_pad_buckets -> tree_finish)
+  static constexpr int PIN_OCT_RANGE = 144;   // 1 uint32: the range word of an octree ICP iteration, copied ahead of its sums
   void* h_build = nullptr;  // 64 KB, pinned: the tree build's looks at the device (BuildSide::h_pin)
   void* h_stage = nullptr;  // pinned staging for descriptor tables of batched launches (grows on demand)
   size_t h_stage_cap = 0;
@@ -218,6 +219,19 @@ int scan_pass(Ctx* c, const tdtk_tree* model, const double* A16, tdtk_scan* data
               unsigned want, const double* lum_D, const double* pending, bool do_search, double* acc_out,
               double shift_out[3], bool warm = false, const unsigned char* skip = nullptr, bool cert_ok = false);
 int scan_idx_to_host(Ctx* c, const tdtk_tree* model, tdtk_scan* data, int32_t* idx_out);
+// api_icp.cpp
+// icp6D::match's loop (tdtk_icp_match) over a search tree that is not the k-d tree: `model` stands in for it where the loop
+// needs a tdtk_tree (the device, the point array the index hashes read), and one iteration's search and sums are the pass's:
+// it applies `pending` (the previous iteration's alignxf, nullable) to the scan, searches -- `skip`: the -R keep bytes,
+// nullable -- and leaves the raw sums in acc [ACC_TOTAL] about shift, the hits in WS_KPOS.  `check` runs behind the argument
+// checks and before anything moves.  A pass that fails ends the loop with res->iterations = its iteration.
+struct IcpTreePass {
+  std::function<int(int pmode, double maxd2)> check;
+  std::function<int(const double* pending, const unsigned char* skip, unsigned want, double* acc, double shift[3])> pass;
+};
+int icp_match_loop(const tdtk_tree* model, const IcpTreePass* other, const double model_dalignxf[16], tdtk_scan* data,
+                   double data_transMat[16], double data_dalignxf[16], const tdtk_icp_params* prm, int rnd,
+                   tdtk_icp_result* res, double* trace, int trace_cap);
 // api_scan.cpp
 int queue_scan_moves(Ctx* c, const std::vector<tdtk_scan*>& moved);
 using PairsPass = std::function<int(tdtk_scan*, int32_t*, tdtk_pair_sums*)>;

@@ -1,6 +1,6 @@
 // The octree entry points: tdtk_octree_create / _create_from_scan / _destroy / _get_info / _leaf_order, tdtk_octree_find_closest
 // (and _dev) and tdtk_octree_get_pt_pairs (kernels: octree.hip and, for keys, sort and within-leaf order, reduce.hip; per-lane
-// code: oct_lane.h).
+// code: oct_lane.h); tdtk_icp_match_octree / _rnd: the octree's pass of an ICP iteration inside api_icp.cpp's loop.
 #include "api_internal.h"
 #include "octree.h"
 
@@ -207,9 +207,93 @@ int octree_scan_pairs(const tdtk_octree* t, const double A[16], tdtk_scan* data,
   return rc;
 }
 
+// One iteration of tdtk_icp_match_octree: the loop-form prepare pass (moves the scan by `pending`, the tree-frame coordinates
+// into WS_DX / WS_DY / WS_DZ, the range word), the walk, the range word on its way to pinned memory, then scan_pass's sums over
+// (query, hit slot) -- whose wait is the only one: the host looks at the range word once the sums are there.
+int octree_loop_pass(Ctx* c, const tdtk_octree* t, const double A[16], tdtk_scan* data, int pmode, double maxd2, unsigned want,
+                     const double* pending, const unsigned char* skip, double* acc, double shift[3])
+{
+  int rc;
+  hipStream_t s = c->stream;
+  const size_t N = data->N;
+  if ((rc = c->ws[WS_KPOS].ensure(N * sizeof(int))) || (rc = c->ws[WS_CNT].ensure(64))) return rc;
+  int ids[] = {WS_DX, WS_DY, WS_DZ};
+  for (int id : ids)
+    if ((rc = c->ws[id].ensure(N * sizeof(double)))) return rc;
+  if ((rc = scan_settle(c, data))) return rc;
+  OctLoopPrepArgs p{};
+  p.x = data->x; p.y = data->y; p.z = data->z;
+  p.nx = data->nx; p.ny = data->ny; p.nz = data->nz;
+  p.ox = c->ws[WS_DX].as<double>(); p.oy = c->ws[WS_DY].as<double>(); p.oz = c->ws[WS_DZ].as<double>();
+  p.n = N;
+  p.has_pending = pending ? 1 : 0;
+  if (pending) std::memcpy(p.pending.m, pending, sizeof p.pending.m);
+  m4inv(A, p.inv.m);          // searchTree.cc:110
+  for (int k = 0; k < 3; k++) p.add[k] = t->view.add[k];
+  p.mult = t->view.mult;
+  p.bad = c->ws[WS_CNT].as<uint32_t>();
+  OctLoopSearchArgs a{};
+  a.T = t->view; a.levels = t->info.levels;
+  a.x = p.ox; a.y = p.oy; a.z = p.oz; a.n = N;
+  a.maxd2 = maxd2;
+  a.kpos = c->ws[WS_KPOS].as<int>();
+  a.skip = skip;
+  a.bad = p.bad;
+  uint32_t* h_bad = reinterpret_cast<uint32_t*>(c->h_pin + Ctx::PIN_OCT_RANGE);
+  HIPCHK(hipMemsetAsync(p.bad, 0, sizeof(uint32_t), s));
+  HIPCHK(launch_oct_loop_prepare(p, s));
+  const bool timed = kernel_timing();
+  if (timed) HIPCHK(hipEventRecord(c->e0, s));
+  HIPCHK(launch_oct_loop_search(a, s));
+  if (timed) { HIPCHK(hipEventRecord(c->e1, s)); c->ev_pending = true; }
+  HIPCHK(hipMemcpyAsync(h_bad, p.bad, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  c->cert_live = false;       // WS_KPOS no longer holds a k-d pass's hits
+  if ((rc = scan_pass(c, &t->kd, A, data, pmode, maxd2, want, nullptr, nullptr, false, acc, shift))) return rc;
+  if (*reinterpret_cast<volatile uint32_t*>(h_bad)) {
+    set_error("a query's voxel coordinate (q + add) * mult does not fit +-2^30: the reference's int conversion is undefined");
+    return TDTK_EUNSUP;
+  }
+  return TDTK_OK;
+}
+
+int octree_icp_match(const tdtk_octree* model, const double model_dalignxf[16], tdtk_scan* data, double data_transMat[16],
+                     double data_dalignxf[16], const tdtk_icp_params* prm, int rnd, tdtk_icp_result* res, double* trace, int trace_cap)
+{
+  if (!model) { set_error("NULL argument"); return TDTK_EINVAL; }
+  IcpTreePass other;
+  other.check = [&](int pmode, double maxd2) {
+    if (pmode == TDTK_CLOSEST_POINT_ALONG_NORMAL_SIMPLE) {
+      set_error("BOctTree has no FindClosestAlongDir of its own (it inherits SearchTree's): pairing mode 1 is not served by the octree");
+      return (int)TDTK_EUNSUP;
+    }
+    if (pmode != TDTK_CLOSEST_POINT && pmode != TDTK_CLOSEST_PLANE_SIMPLE) { set_error("bad pairing mode"); return (int)TDTK_EINVAL; }
+    if (model->device != data->device) { set_error("tree and scan live on different devices"); return (int)TDTK_EINVAL; }
+    return octree_radius_check(model, maxd2);
+  };
+  other.pass = [&](const double* pending, const unsigned char* skip, unsigned want, double* acc, double* shift) {
+    Ctx* c;
+    int rc = get_ctx(model->device, &c);
+    if (rc) return rc;
+    return octree_loop_pass(c, model, model_dalignxf, data, prm->pairing_mode, prm->max_dist_match2, want, pending, skip, acc, shift);
+  };
+  return icp_match_loop(&model->kd, &other, model_dalignxf, data, data_transMat, data_dalignxf, prm, rnd, res, trace, trace_cap);
+}
+
 }  // namespace
 
 extern "C" {
+
+int tdtk_icp_match_octree(const tdtk_octree* model, const double model_dalignxf[16], tdtk_scan* data, double data_transMat[16],
+                          double data_dalignxf[16], const tdtk_icp_params* prm, tdtk_icp_result* res, double* trace, int trace_cap)
+{
+  return octree_icp_match(model, model_dalignxf, data, data_transMat, data_dalignxf, prm, 1, res, trace, trace_cap);
+}
+int tdtk_icp_match_octree_rnd(const tdtk_octree* model, const double model_dalignxf[16], tdtk_scan* data, double data_transMat[16],
+                              double data_dalignxf[16], const tdtk_icp_params* prm, int rnd, tdtk_icp_result* res, double* trace,
+                              int trace_cap)
+{
+  return octree_icp_match(model, model_dalignxf, data, data_transMat, data_dalignxf, prm, rnd, res, trace, trace_cap);
+}
 
 int tdtk_octree_create(const double* xyz, size_t n, double voxel_size, int earlystop, int device, tdtk_octree** out)
 {

@@ -52,4 +52,32 @@ struct OctSearchArgs {
 hipError_t launch_oct_prepare(const OctPrepArgs& a, hipStream_t s);
 hipError_t launch_oct_search(const OctSearchArgs& a, hipStream_t s);
 
+// ---- the ICP loop (tdtk_icp_match_octree): the same two passes with nothing for the host to do in between ---------------
+// the prepare pass of an iteration: first the previous iteration's alignxf in place over the resident scan (k_transform's
+// arithmetic: the octree's SearchArgs::pending), then the tree-frame coordinates and the range word as k_oct_prepare
+struct OctLoopPrepArgs {
+  double *x, *y, *z;         // the resident scan, SoA, spatially sorted: moved in place when has_pending
+  double *nx, *ny, *nz;      // its normals (nullable): moved with it
+  double *ox, *oy, *oz;      // out: transform3(inv, .) of every (moved) point
+  size_t n;
+  Mat4 pending, inv;
+  int has_pending;
+  double add[3], mult;
+  uint32_t* bad;             // one word, zeroed by the caller
+};
+// the walk: reads the range word itself (set: every query gets kpos = -1 and nothing is converted to int) and the -R keep
+// bytes (SearchArgs::skip's format, nullable: a query whose byte is set gets kpos = -1 and is not walked)
+struct OctLoopSearchArgs {
+  OctView T;
+  const double *x, *y, *z;   // queries in the tree's frame (OctLoopPrepArgs::ox ..)
+  size_t n;
+  int levels;
+  double maxd2;
+  int* kpos;
+  const unsigned char* skip;
+  const uint32_t* bad;
+};
+hipError_t launch_oct_loop_prepare(const OctLoopPrepArgs& a, hipStream_t s);
+hipError_t launch_oct_loop_search(const OctLoopSearchArgs& a, hipStream_t s);
+
 }  // namespace tdtk

@@ -22,6 +22,10 @@
 // its per-level stack in LDS ([level][lane], 8-byte entries: a wave's accesses to one level are 512 consecutive bytes).  All
 // decisions are integer voxel arithmetic; fp64 only for (p + add) * mult, Dist2 and sqrt(d2) * mult + 1, FMA contraction off
 // (Makefile), in the reference's association.
+//
+// The ICP loop.  k_oct_loop_prepare / k_oct_loop_find: the same two passes in the form tdtk_icp_match_octree launches once per
+// iteration without looking at the device in between -- the scan's move by the previous alignxf folded into the prepare pass,
+// the range word read by the walk itself.
 #include <hip/hip_runtime.h>
 
 #include "octree.h"
@@ -227,6 +231,81 @@ __global__ __launch_bounds__(OCT_BLOCK) void k_oct_find(const OctSearchArgs a)
     a.kpos[i] = slot;
     if (a.d2) a.d2[i] = d2;
   }
+}
+
+// ---- the ICP loop: one iteration is k_oct_loop_prepare, k_oct_loop_find and the pair sums, the host waits for the sums only --
+// The scan moves here, not in a launch of its own: Scan::transformReduced (scan.cc:851-875) as k_transform does it -- the
+// point (x*a0 + y*a4 + z*a8), then + a12; the normal by the transposed rotation block -- so the scan behind the loop has the
+// bits of one moved by tdtk_scan_transform iteration by iteration.  The rest is k_oct_prepare on the moved point.
+__global__ __launch_bounds__(256) void k_oct_loop_prepare(const OctLoopPrepArgs a)
+{
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  bool bad = false;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
+    double px = a.x[i], py = a.y[i], pz = a.z[i];
+    if (a.has_pending) {
+      const double* m = a.pending.m;
+      const double xn = px * m[0] + py * m[4] + pz * m[8];
+      const double yn = px * m[1] + py * m[5] + pz * m[9];
+      const double zn = px * m[2] + py * m[6] + pz * m[10];
+      px = xn + m[12]; py = yn + m[13]; pz = zn + m[14];
+      a.x[i] = px; a.y[i] = py; a.z[i] = pz;
+      if (a.nx) {
+        const double ux = a.nx[i], uy = a.ny[i], uz = a.nz[i];
+        a.nx[i] = ux * m[0] + uy * m[1] + uz * m[2];
+        a.ny[i] = ux * m[4] + uy * m[5] + uz * m[6];
+        a.nz[i] = ux * m[8] + uy * m[9] + uz * m[10];
+      }
+    }
+    const double qx = px * a.inv.m[0] + py * a.inv.m[4] + pz * a.inv.m[8] + a.inv.m[12];
+    const double qy = px * a.inv.m[1] + py * a.inv.m[5] + pz * a.inv.m[9] + a.inv.m[13];
+    const double qz = px * a.inv.m[2] + py * a.inv.m[6] + pz * a.inv.m[10] + a.inv.m[14];
+    a.ox[i] = qx; a.oy[i] = qy; a.oz[i] = qz;
+    bad |= !oct_in_range((qx + a.add[0]) * a.mult) || !oct_in_range((qy + a.add[1]) * a.mult) || !oct_in_range((qz + a.add[2]) * a.mult);
+  }
+  if (bad) *a.bad = 1u;
+}
+
+// k_oct_find behind a prepare pass nobody has looked at: the range word is read here, once per wave and the same for all of
+// them, and a raised one means no coordinate is converted to int at all -- every query leaves with kpos = -1 and the host,
+// which receives the word with the sums, refuses the iteration.  Behind that the loop is k_oct_find's; SKIP (-R): a query
+// that was not drawn leaves with kpos = -1, unwalked.
+template <bool SKIP>
+__global__ __launch_bounds__(OCT_BLOCK) void k_oct_loop_find(const OctLoopSearchArgs a)
+{
+  extern __shared__ __attribute__((aligned(16))) uint2 oct_lds[];
+  OctStackLds st{oct_lds + threadIdx.x};
+  const size_t stride = (size_t)gridDim.x * OCT_BLOCK;
+  if (*a.bad != 0u) {
+    for (size_t i = (size_t)blockIdx.x * OCT_BLOCK + threadIdx.x; i < a.n; i += stride) a.kpos[i] = -1;
+    return;
+  }
+  for (size_t i = (size_t)blockIdx.x * OCT_BLOCK + threadIdx.x; i < a.n; i += stride) {
+    if (SKIP && a.skip[i]) { a.kpos[i] = -1; continue; }
+    double d2;
+    int32_t slot, leaves;
+    oct_find_closest(a.T, a.x[i], a.y[i], a.z[i], a.maxd2, st, slot, d2, leaves);
+    a.kpos[i] = slot;
+  }
+}
+
+hipError_t launch_oct_loop_prepare(const OctLoopPrepArgs& a, hipStream_t s)
+{
+  if (!a.n) return hipSuccess;
+  hipLaunchKernelGGL(k_oct_loop_prepare, dim3(oct_grid(a.n)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_oct_loop_search(const OctLoopSearchArgs& a, hipStream_t s)
+{
+  if (!a.n) return hipSuccess;
+  const int depth = a.levels > 1 ? a.levels - 1 : 1;      // as launch_oct_search
+  const size_t lds = (size_t)depth * OCT_BLOCK * sizeof(uint2);
+  size_t nb = (a.n + OCT_BLOCK - 1) / OCT_BLOCK;
+  if (nb > 65536) nb = 65536;
+  if (a.skip) hipLaunchKernelGGL(k_oct_loop_find<true>, dim3((uint32_t)nb), dim3(OCT_BLOCK), lds, s, a);
+  else hipLaunchKernelGGL(k_oct_loop_find<false>, dim3((uint32_t)nb), dim3(OCT_BLOCK), lds, s, a);
+  return hipGetLastError();
 }
 
 hipError_t launch_oct_prepare(const OctPrepArgs& a, hipStream_t s)

@@ -217,7 +217,7 @@ def lum_iteration_native(gr, allScans, max_dist_match2, group=None, device=None)
     nl = len(mine)
     Cm = np.empty((nl, 36)); CD = np.empty((nl, 6))
     if nl:
-        first = (C.c_void_p * nl)(*[allScans[gr.getLink(i, 0)].getSearchTree()._h for i in mine])
+        first = (C.c_void_p * nl)(*[allScans[gr.getLink(i, 0)].kdHandle("doGraphSlam6D") for i in mine])
         second = (C.c_void_p * nl)(*[allScans[gr.getLink(i, 1)].handle for i in mine])
         dal = np.ascontiguousarray(np.stack([allScans[gr.getLink(i, 0)].dalignxf for i in mine]))
         m = (C.c_uint64 * nl)(); ss = np.empty(nl)
@@ -293,7 +293,7 @@ def graph_iteration_comm(backend, gr, allScans, max_dist_match2, comm, state=Non
     mine_a = np.flatnonzero(link_owners(gr, world, sc) == rank).astype(np.int32) if world > 1 else np.arange(nlinks, dtype=np.int32)
     nl = len(mine_a)
     fl, tl = frm[mine_a].tolist(), to[mine_a].tolist()
-    first = (C.c_void_p * max(1, nl))(*[sc[a].getSearchTree()._h for a in fl])
+    first = (C.c_void_p * max(1, nl))(*[sc[a].kdHandle("doGraphSlam6D") for a in fl])
     second = (C.c_void_p * max(1, nl))(*[sc[b].handle for b in tl])
     tm = np.array([s.transMat for s in sc], dtype=np.float64).reshape(nscans, 16)
     da = np.array([s.dalignxf for s in sc], dtype=np.float64).reshape(nscans, 16)
@@ -345,7 +345,7 @@ def graph_iteration(backend, gr, allScans, max_dist_match2, state=None, group=No
     Bn = lib().tdtk_graph_block_doubles(int(backend))
     blocks = np.zeros((nlinks, Bn))
     if nl:
-        first = (C.c_void_p * nl)(*[allScans[gr.getLink(i, 0)].getSearchTree()._h for i in mine])
+        first = (C.c_void_p * nl)(*[allScans[gr.getLink(i, 0)].kdHandle("doGraphSlam6D") for i in mine])
         second = (C.c_void_p * nl)(*[allScans[gr.getLink(i, 1)].handle for i in mine])
         dal = np.ascontiguousarray(np.stack([allScans[gr.getLink(i, 0)].dalignxf for i in mine]))
         mb = np.empty((nl, Bn))

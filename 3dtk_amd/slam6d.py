@@ -583,6 +583,7 @@ class Scan:
         self._queue = []
         self._orig = None
         self.kd = None
+        self.nns_method = 0   # searchtree_nnstype (setSearchTreeParameter): 0 simpleKD, 2 BOCTree
         self.frames = []  # (transMat copy, type)
 
     def release(self):
@@ -670,8 +671,35 @@ class Scan:
         check(lib().tdtk_scan_download(h, dptr(xyz), dptr(nrm)))
         return nrm
 
+    def setSearchTreeParameter(self, nns_method, bucketSize=20):
+        """Scan::setSearchTreeParameter (scan.cc:236-240): the search tree getSearchTree builds -- 0 simpleKD (the k-d tree,
+        `-t 0`), 2 BOCTree (`-t 2`).  1 (ANNTree) and 3 (BruteForce) are the reference's types this library does not have:
+        its createSearchTreePrivate's "SearchTree type not implemented" (basicScan.cc:726), raised here.  A tree already
+        built is dropped."""
+        nns_method = int(nns_method)
+        if nns_method not in (0, 2):
+            raise RuntimeError("SearchTree type not implemented")
+        self.nns_method = nns_method
+        self.bucketSize = int(bucketSize)
+        self.kd = None
+        return self
+
+    def requireKd(self, who):
+        """`who` takes a tdtk_tree only: an octree scan (`-t 2`) is refused by name, before any tree is built"""
+        if self.nns_method == 2:
+            raise capi.TdtkError(-5, "%s runs on the k-d tree only (setSearchTreeParameter(0)): this scan's search tree "
+                                     "is a BOctTree" % who)
+
+    def kdHandle(self, who):
+        """the k-d tree's handle for such an entry point"""
+        self.requireKd(who)
+        return self.getSearchTree()._h
+
     def getSearchTree(self):
         """scan.cc:268-306 -> basicScan.cc:702-728: lazily built over "xyz reduced original"."""
+        if self.kd is None and self.nns_method == 2:
+            # BOctTree<double>(ar, n, 10.0, PointType(), true), basicScan.cc:714-719: device to device over the original points
+            self.kd = BOctTree.from_scan(self.handle, self.n, 10.0, True, self.device)
         if self.kd is None:
             if self._h is None and self._queue:     # never resident, already moved: go through a temporary upload
                 self.kd = KDtree(self.xyz_reduced_original, self.bucketSize, self.device)
@@ -762,8 +790,7 @@ class Scan:
         s = PairSums()
         idx = np.empty(Target.n, np.int32) if want_idx else None
         D = f64(lum_D, 6) if lum_D is not None else None
-        tree = Source.getSearchTree()
-        check(lib().tdtk_scan_pairs(tree._h, dptr(Source.dalignxf), Target.handle, int(pairing_mode),
+        check(lib().tdtk_scan_pairs(Source.kdHandle("Scan.getPtPairs"), dptr(Source.dalignxf), Target.handle, int(pairing_mode),
                                     float(max_dist_match2), int(want), dptr(D), iptr(idx), C.byref(s)))
         out = _sums_dict(s)
         out["_raw"] = s
@@ -819,7 +846,18 @@ class MetaScan:
                 else:
                     sc.addFrame("ICPINACTIVE" if found == 0 else "INVALID")
 
+    def requireKd(self, who):
+        """KDtreeMetaManaged is a k-d tree (metaScan.cc:82-104 has the other types commented out): member scans that ask for
+        a BOctTree are refused"""
+        if any(getattr(s, "nns_method", 0) == 2 for s in self.m_scans):
+            raise capi.TdtkError(-5, "%s runs on the k-d tree only: a member scan of the MetaScan asks for a BOctTree" % who)
+
+    def kdHandle(self, who):
+        return self.getSearchTree()._h
+
     def getSearchTree(self):
+        if self.kd is None:
+            self.requireKd("MetaScan.getSearchTree")
         if self.kd is None:   # device to device: the scans' current points never visit the host
             hs = (C.c_void_p * len(self.m_scans))(*[s.handle for s in self.m_scans])
             kd = KDtree.__new__(KDtree)
@@ -970,12 +1008,13 @@ ALGO_TYPE = {"INVALID": 0, "ICP": 1, "ICPINACTIVE": 2, "LUM": 3, "ELCH": 4}   # 
 
 
 def openDirectory(path, start=0, end=-1, range_max=0.0, range_min=0.0, bucketSize=20, device=0, red=-1.0,
-                  use_normals=False):
+                  use_normals=False, nns_method=0):
     """Scan::openDirectory for the uos format (src/slam6d/scan.cc / basicScan.cc:39-122):
     scanNNN.3d + scanNNN.pose, NNN = start..end; red = -r voxel size (setReductionParameter).
     use_normals = what slam6D.cc:688-692 asks for with -z / --normal_shoot-simple (PointType::USE_NORMAL): every
     scan gets Scan::calcNormals.  Not together with red > 0: the reference's centre-mode octree reduction does not
-    carry normals (it copies POINTDIM values out of a 3-element centre, Boctree.h:928-941)."""
+    carry normals (it copies POINTDIM values out of a 3-element centre, Boctree.h:928-941).
+    nns_method = -t (setSearchTreeParameter on every scan): 0 the k-d tree, 2 the octree."""
     if use_normals and red > 0:
         raise ValueError("normals are not carried through the octree reduction (see DESIGN.md section 9)")
     import os
@@ -991,6 +1030,7 @@ def openDirectory(path, start=0, end=-1, range_max=0.0, range_min=0.0, bucketSiz
         if red > 0:
             pts = calcReducedPoints(pts, red, device)
         s = Scan(rP, rT, pts, bucketSize=bucketSize, device=device)
+        s.setSearchTreeParameter(nns_method, bucketSize)
         if use_normals:
             s.calcNormals()
         s.identifier = "%03d" % i
@@ -1123,6 +1163,7 @@ class icp6D:
         self.max_num_metascans = max_num_metascans
         self.eP = eP
         self.epsilonICP = epsilonICP
+        self.nns_method = nns_method      # icp6D.cc:434 hands it to MetaScan alone; the scans' own type decides (setSearchTreeParameter)
         self.nr_pointPair = 0
         self.last = None
 
@@ -1144,12 +1185,16 @@ class icp6D:
         trace = np.zeros((cap, 18))
         tm = CurrentScan.transMat.copy()
         da = CurrentScan.dalignxf.copy()
+        # the resident loop of the tree's type (-t 0 / -t 2): the same arguments, results and trace
+        octree = isinstance(tree, BOctTree)
+        f_match = lib().tdtk_icp_match_octree if octree else lib().tdtk_icp_match
+        f_match_rnd = lib().tdtk_icp_match_octree_rnd if octree else lib().tdtk_icp_match_rnd
         if self.rnd > 1:       # -R: the keep-mask of every iteration is drawn on the host (std::rand, index order), the loop stays resident
-            check(lib().tdtk_icp_match_rnd(tree._h, dptr(PreviousScan.dalignxf), CurrentScan.handle, dptr(tm),
-                                           dptr(da), C.byref(prm), int(self.rnd), C.byref(res), dptr(trace), cap))
+            check(f_match_rnd(tree._h, dptr(PreviousScan.dalignxf), CurrentScan.handle, dptr(tm),
+                              dptr(da), C.byref(prm), int(self.rnd), C.byref(res), dptr(trace), cap))
         else:
-            check(lib().tdtk_icp_match(tree._h, dptr(PreviousScan.dalignxf), CurrentScan.handle, dptr(tm),
-                                       dptr(da), C.byref(prm), C.byref(res), dptr(trace), cap))
+            check(f_match(tree._h, dptr(PreviousScan.dalignxf), CurrentScan.handle, dptr(tm),
+                          dptr(da), C.byref(prm), C.byref(res), dptr(trace), cap))
         # frames as the reference's loop writes them (anim = -1): one after iteration 0 (transform(alignxf, ICP, 0),
         # icp6D.cc:258-264), one when the loop ends by convergence or at the cap (transform(id, ICP, 0),
         # :266-279) -- none on the "<= 3 pairs" break (:235-243 fall through to the end of the function)
@@ -1218,13 +1263,13 @@ class icp6D:
         algo = int(self.my_icp6Dminimizer.getAlgorithmID())
         if algo not in (ALGO_QUAT, ALGO_SVD):
             raise capi.TdtkError(-5, "a MetaScan as data scan is matched with -a 1 or -a 2 only")
+        PreviousScan.requireKd("icp6D.match with a MetaScan as data")
         CurrentMeta.transform(M4identity(), "ICP", 0)                      # icp6D.cc:109
         if self.max_num_iterations == 0:
             return 0
-        tree = PreviousScan.getSearchTree()
         members = CurrentMeta.m_scans
         nl = len(members)
-        first = (C.c_void_p * nl)(*[tree._h] * nl)
+        first = (C.c_void_p * nl)(*[PreviousScan.kdHandle("icp6D.match with a MetaScan as data")] * nl)
         second = (C.c_void_p * nl)(*[m.handle for m in members])
         dal = np.ascontiguousarray(np.tile(f64(PreviousScan.dalignxf, 16), (nl, 1)))
         ret = prev_ret = prev_prev_ret = 0.0
@@ -1257,7 +1302,7 @@ class icp6D:
             scale_max = 0.000001          # include/slam6d/icp6D.h default
         err = C.c_double(0.0)
         npairs = C.c_uint64(0)
-        check(lib().tdtk_point_point_error(PreviousScan.getSearchTree()._h, dptr(PreviousScan.dalignxf),
+        check(lib().tdtk_point_point_error(PreviousScan.kdHandle("icp6D.Point_Point_Error"), dptr(PreviousScan.dalignxf),
                                            CurrentScan.handle, float(max_dist_match), float(scale_max),
                                            C.byref(npairs), C.byref(err)))
         return err.value, int(npairs.value)
@@ -1382,8 +1427,7 @@ def covarianceEuler(first, second, max_dist_match2):
     """lum6DEuler::covarianceEuler (lum6Deuler.cc:94-251) -> (C 6x6, CD 6, m, ss)."""
     Cm = np.zeros(36); CD = np.zeros(6)
     m = C.c_uint64(0); ss = C.c_double(0.0)
-    tree = first.getSearchTree()
-    check(lib().tdtk_lum_link(tree._h, dptr(first.dalignxf), second.handle, float(max_dist_match2),
+    check(lib().tdtk_lum_link(first.kdHandle("covarianceEuler"), dptr(first.dalignxf), second.handle, float(max_dist_match2),
                               dptr(Cm), dptr(CD), C.byref(m), C.byref(ss)))
     return Cm.reshape(6, 6), CD, int(m.value), ss.value
 
@@ -1561,7 +1605,7 @@ class elch6Deuler(loopSlam6D):
         edges = list(g)
         # one covarianceEuler per edge (elch6Deuler.cc:53-66): all of them in one batched device call
         ne = len(edges)
-        firsts = (C.c_void_p * ne)(*[allScans[a].getSearchTree()._h for a, b in edges])
+        firsts = (C.c_void_p * ne)(*[allScans[a].kdHandle("ELCH (close_loop)") for a, b in edges])
         seconds = (C.c_void_p * ne)(*[allScans[b].handle for a, b in edges])
         dal = np.ascontiguousarray(np.stack([allScans[a].dalignxf for a, b in edges]))
         blocks = np.empty((ne, 42))
@@ -1627,7 +1671,7 @@ class _elchQuatBase(loopSlam6D):
         n = max(max(a, b) for a, b in g) + 1
         edges = list(g)
         ne = len(edges)
-        firsts = (C.c_void_p * ne)(*[allScans[a].getSearchTree()._h for a, b in edges])
+        firsts = (C.c_void_p * ne)(*[allScans[a].kdHandle("ELCH (close_loop)") for a, b in edges])
         seconds = (C.c_void_p * ne)(*[allScans[b].handle for a, b in edges])
         dal = np.ascontiguousarray(np.stack([allScans[a].dalignxf for a, b in edges]))
         blocks = np.empty((ne, 56))
@@ -1746,7 +1790,7 @@ def computeGraph6Dautomatic(allScans, clpairs, max_dist_match2_LUM=625.0, group=
     counts = np.zeros(len(cand))
     if mine:
         nl = len(mine)
-        first = (C.c_void_p * nl)(*[allScans[cand[i][0]].getSearchTree()._h for i in mine])
+        first = (C.c_void_p * nl)(*[allScans[cand[i][0]].kdHandle("computeGraph6Dautomatic") for i in mine])
         second = (C.c_void_p * nl)(*[allScans[cand[i][1]].handle for i in mine])
         dal = np.ascontiguousarray(np.stack([allScans[cand[i][0]].dalignxf for i in mine]))
         sums = (PairSums * nl)()

@@ -528,6 +528,26 @@ int tdtk_icp_match_rnd(const tdtk_tree* model, const double model_dalignxf[16], 
                        double data_transMat[16], double data_dalignxf[16], const tdtk_icp_params* prm, int rnd,
                        tdtk_icp_result* res, double* trace, int trace_cap);
 
+/* icp6D::match on the octree search tree (`slam6D -t 2`): tdtk_icp_match's arguments, checks, messages, results and trace,
+ * FindClosest being BOctTree's (tdtk_octree_find_closest: NOT the nearest point in general, so these are not the k-d
+ * loop's poses).  All ten minimizers; pairing_mode TDTK_CLOSEST_POINT and TDTK_CLOSEST_PLANE_SIMPLE,
+ * TDTK_CLOSEST_POINT_ALONG_NORMAL_SIMPLE returns TDTK_EUNSUP as tdtk_octree_get_pt_pairs.  An iteration is a fixed sequence
+ * of launches -- the previous alignxf applied to the scan together with the queries' transform into the tree's frame and
+ * their range check, the walk, the pair sums -- and one wait of the host, for the sums.  The range rule of
+ * tdtk_octree_find_closest:
+ *   sqrt(max_dist_match2) * mult + 1 outside +-2^30: TDTK_EUNSUP before anything moves (res untouched);
+ *   a query whose voxel coordinate leaves +-2^30 in iteration k: TDTK_EUNSUP with res->iterations = k; the scan, data_transMat
+ *   and data_dalignxf then hold exactly the transforms of the k iterations that completed (no query of iteration k was
+ *   searched, nothing of it is applied), the other fields of res and the trace rows from k on are not meaningful.
+ * The loop keeps no state of a k-d loop and leaves none: the next tdtk_icp_match on this thread starts cold.            */
+int tdtk_icp_match_octree(const tdtk_octree* model, const double model_dalignxf[16], tdtk_scan* data,
+                          double data_transMat[16], double data_dalignxf[16], const tdtk_icp_params* prm,
+                          tdtk_icp_result* res, double* trace, int trace_cap);
+/* ... with `-R <rnd>`: tdtk_icp_match_rnd's draws (one std::rand() per point, in index order, when the iteration starts) */
+int tdtk_icp_match_octree_rnd(const tdtk_octree* model, const double model_dalignxf[16], tdtk_scan* data,
+                              double data_transMat[16], double data_dalignxf[16], const tdtk_icp_params* prm, int rnd,
+                              tdtk_icp_result* res, double* trace, int trace_cap);
+
 /* ---- lum6DEuler::covarianceEuler (src/slam6d/lum6Deuler.cc:94-251) for one link:
  * first = model tree + its dalignxf, second = resident data scan.  C[36] row-major, CD[6].
  * Returns the pair count through *m; C/CD are zero if m <= 2 or ss < 1e-13.              */

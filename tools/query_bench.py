@@ -54,6 +54,12 @@ the same points; then 10 000 removes (the second batch of two, so that the first
 = 625 on a 1M-point uniform cloud (density 1), on the octree (voxel 10, earlystop) and on the k-d tree (bucket 20) -- five runs
 each, alternating between the two trees, min / max / median; both builds; whether the two answers agree.
 
+--only-octree-icp runs icp6D::match on the octree search tree alone, per iteration (-a 1, maxdist2 625, epsilon 0, so every
+run makes all its iterations: 50 on the pair, 10 on the cloud): the resident loop (icp6D.match on scans with setSearchTreeParameter(2): tdtk_icp_match_octree) next to the loop stepped
+from the host (BOctTree.getPtPairs + Align_Parallel + Scan.transform per iteration), on the bundled scan pair and on the 1M-point
+uniform cloud of --only-octree (voxel 10, earlystop) -- five runs each, alternating between the two loops, host clock, min / max
+/ median; then one resident run with tdtk_kernel_timing on: the walk's and the pair sums' share from HIP events.
+
 Kernel times: run the same command under `rocprofv3 --kernel-trace --stats` (k_knn_reg, k_range_count / k_range_fill,
 k_range_normals, k_shape_count / k_shape_fill, k_segment_nearest, k_knn_adaptive_reg / k_knn_adaptive_lds, k_ann_adaptive, k_knnr_reg / k_knnr_lds,
 k_collide_mark, k_collide_depth_axis)."""
@@ -493,6 +499,51 @@ def octree_legs(tdtk, runs=5):
     return out
 
 
+def octree_icp_legs(tdtk, runs=5):
+    """the resident octree ICP loop against the host-stepped one, ms per iteration (see the module docstring)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from boctree_model import dat_pair, move
+    rng = np.random.default_rng(2033)
+    pts = rng.uniform(-50, 50, (1_000_000, 3))
+    A = tdtk.EulerToMatrix4([0.3, -0.2, 0.1], [0.002, -0.003, 0.001])
+    sets = {"dat_pair": dat_pair() + (50,), "uniform_1M": (pts, move(pts + rng.normal(0.0, 0.3, pts.shape), A), 10)}
+    z3 = [0.0, 0.0, 0.0]
+    out = {}
+    for tag, (model, data, iters) in sets.items():
+        out["octree_icp_%s_iterations" % tag] = iters
+        prev = tdtk.Scan(z3, z3, model).setSearchTreeParameter(2)
+        prev.getSearchTree()
+
+        def one(stepped, timing=False):
+            cur = tdtk.Scan(z3, z3, data)
+            _ = cur.handle
+            icp = tdtk.icp6D(tdtk.icp6D_QUAT(True), 25.0, iters, quiet=True, epsilonICP=0.0)
+            was = tdtk.lib().tdtk_kernel_timing(1 if timing else 0)
+            t0 = time.perf_counter()
+            it = icp._match_stepped(prev, cur) if stepped else icp.match(prev, cur)
+            ms = (time.perf_counter() - t0) * 1e3
+            tdtk.lib().tdtk_kernel_timing(was)
+            assert it == iters - 1
+            last = icp.last
+            cur.release()
+            return ms / iters, last
+        ref = {False: one(False)[1], True: one(True)[1]}             # warm: code objects, workspaces -- and the answers
+        out["octree_icp_%s_pairs_equal" % tag] = bool(np.array_equal(ref[False]["trace"][:, 0], ref[True]["trace"][:, 0]))
+        out["octree_icp_%s_max_pose_diff" % tag] = float(np.abs(ref[False]["trace"][:, 2:] - ref[True]["trace"][:, 2:]).max())
+        ts = {"resident": [], "stepped": []}
+        for _ in range(runs):
+            for name, stepped in (("resident", False), ("stepped", True)):
+                ts[name].append(one(stepped)[0])
+        for name, v in ts.items():
+            out["octree_icp_%s_%s_ms_per_iteration" % (tag, name)] = {"min_ms": round(min(v), 3), "max_ms": round(max(v), 3),
+                                                                      "median_ms": round(float(np.median(v)), 3)}
+        ms, last = one(False, timing=True)
+        out["octree_icp_%s_timed_run" % tag] = {"ms_per_iteration": round(ms, 3), "walk_ms_per_iteration": round(last["nn_ms"] / iters, 3),
+                                                "sums_ms_per_iteration": round(last["sums_ms"] / iters, 3)}
+        prev.release()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1000000,10000000")
@@ -512,6 +563,7 @@ def main():
     ap.add_argument("--only-peopleremover", action="store_true", help="dynamic-object removal on a synthetic room, alone")
     ap.add_argument("--only-forest", action="store_true", help="the dynamic kd-forest against rebuilds and the single tree, alone")
     ap.add_argument("--only-octree", action="store_true", help="FindClosestBatch on the octree and on the k-d tree, alone")
+    ap.add_argument("--only-octree-icp", action="store_true", help="the resident octree ICP loop against the host-stepped one, alone")
     args = ap.parse_args()
     tdtk = importlib.import_module("3dtk_amd")
     if tdtk.device_count() < 1:
@@ -527,6 +579,10 @@ def main():
         return
     if args.only_octree:
         out.update(octree_legs(tdtk))
+        print(json.dumps(out))
+        return
+    if args.only_octree_icp:
+        out.update(octree_icp_legs(tdtk))
         print(json.dumps(out))
         return
     rng = np.random.default_rng(2024)
