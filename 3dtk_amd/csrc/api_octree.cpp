@@ -137,7 +137,7 @@ int octree_check_args(size_t n, double voxel_size, tdtk_octree** out)
 // the range rule of the header: sqrt(maxdist2) * mult + 1 on the host, the queries' voxel coordinates on the device
 int octree_radius_check(const tdtk_octree* t, double maxd2)
 {
-  if (!(std::fabs(std::sqrt(maxd2) * t->view.mult + 1) <= OCT_INT_LIMIT)) {      // oct_in_range; a NaN: refused
+  if (!(std::fabs(std::sqrt(maxd2) * t->view.mult + 1) < OCT_INT_LIMIT)) {       // oct_in_range; a NaN: refused
     set_error("sqrt(maxdist2) * mult + 1 does not fit +-2^30: the reference's int conversion is undefined");
     return TDTK_EUNSUP;
   }

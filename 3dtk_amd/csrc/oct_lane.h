@@ -12,8 +12,9 @@
 //
 // The walk, rule by rule (each is the reference's own operation on the reference's own values; easy to get subtly wrong):
 //   * voxel coordinates: x = int((p + add) * mult), C++ truncation toward zero, negative outside the root cube;
-//     closest_v = int(sqrt(maxdist2) * mult + 1).  The entry point refuses batches where one of these leaves +-2^30
-//     (oct_in_range), so every int expression below stays inside int32.
+//     closest_v = int(sqrt(maxdist2) * mult + 1).  The entry point refuses batches where one of these, before its
+//     conversion, is not strictly inside +-2^30 (oct_in_range: |v| < 2^30), so every int expression below stays inside int32
+//     (the extreme, x + closest_v, is 2^31 - 2).
 //   * the box [x - closest_v, x + closest_v] is clamped to [0, largest_index] (max with 0 below, min with largest_index above:
 //     an upper bound may stay negative and a lower one may exceed largest_index; only the bits tested matter).
 //   * descent while the box's two corners select the same child at child_bit: that child a leaf -> scan it, the search is over;
@@ -74,7 +75,8 @@ __device__ __forceinline__ uint32_t oct_order(const uint32_t octant)
 }
 
 // (p + add) * mult and sqrt(maxdist2) * mult + 1 before their conversion to int: false when the conversion would be undefined
-__device__ __forceinline__ bool oct_in_range(const double v) { return fabs(v) <= OCT_INT_LIMIT; }   // a NaN: false
+// (strictly inside: after truncation |x| and closest_v are at most 2^30 - 1, so x +- closest_v is at most 2^31 - 2)
+__device__ __forceinline__ bool oct_in_range(const double v) { return fabs(v) < OCT_INT_LIMIT; }   // a NaN: false
 
 struct OctLane {
   double qx, qy, qz, d2;

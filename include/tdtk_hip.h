@@ -405,8 +405,8 @@ int tdtk_octree_node_table(const tdtk_octree* t, uint32_t* table, size_t cap, ui
  * although a nearer one may follow; at most 10 000 leaves are scanned per query, later ones are skipped; ties go to the
  * first point in octree order; the search prunes in whole voxels of real_voxelSize.
  * The reference converts (q + add) * mult and sqrt(maxdist2) * mult + 1 to int.  Where one of these values of the batch is
- * not within +-2^30 (a NaN included; a negative maxdist2 gives one) that conversion or the sums formed from it are undefined
- * in C++: the call returns TDTK_EUNSUP for the whole batch and writes nothing.                                            */
+ * not strictly inside +-2^30 (|v| >= 2^30; a NaN included; a negative maxdist2 gives one) that conversion or the sums formed
+ * from it (x +- closest_v) are undefined in C++: the call returns TDTK_EUNSUP for the whole batch and writes nothing.     */
 int tdtk_octree_find_closest(const tdtk_octree* t, const double* q, size_t K, double maxdist2, int32_t* idx, double* d2);
 /* the same with device pointers (d_q [K][3], d_idx [K], d_d2 [K] nullable), ordered on `stream` (NULL: the calling thread's
  * own stream, and the call returns when the results are there).  The range check needs one look at the device.         */
@@ -535,8 +535,8 @@ int tdtk_icp_match_rnd(const tdtk_tree* model, const double model_dalignxf[16], 
  * of launches -- the previous alignxf applied to the scan together with the queries' transform into the tree's frame and
  * their range check, the walk, the pair sums -- and one wait of the host, for the sums.  The range rule of
  * tdtk_octree_find_closest:
- *   sqrt(max_dist_match2) * mult + 1 outside +-2^30: TDTK_EUNSUP before anything moves (res untouched);
- *   a query whose voxel coordinate leaves +-2^30 in iteration k: TDTK_EUNSUP with res->iterations = k; the scan, data_transMat
+ *   sqrt(max_dist_match2) * mult + 1 not strictly inside +-2^30: TDTK_EUNSUP before anything moves (res untouched);
+ *   a query whose voxel coordinate is not strictly inside +-2^30 in iteration k: TDTK_EUNSUP with res->iterations = k; the scan, data_transMat
  *   and data_dalignxf then hold exactly the transforms of the k iterations that completed (no query of iteration k was
  *   searched, nothing of it is applied), the other fields of res and the trace rows from k on are not meaningful.
  * The loop keeps no state of a k-d loop and leaves none: the next tdtk_icp_match on this thread starts cold.            */

@@ -15,11 +15,21 @@ G = os.path.join(ROOT, "tests", "golden")
 KDPOINT = np.dtype([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("orig", "<i4"), ("pad", "<i4")])
 
 
+_generators = {}
+
+
+def load_generator(name):
+    """a fixture generator of tests/golden as a module, loaded once"""
+    if name not in _generators:
+        spec = importlib.util.spec_from_file_location(name, os.path.join(G, name + ".py"))
+        m = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(m)
+        _generators[name] = m
+    return _generators[name]
+
+
 def generator():
-    spec = importlib.util.spec_from_file_location("make_golden_boctree_search", os.path.join(G, "make_golden_boctree_search.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
+    return load_generator("make_golden_boctree_search")
 
 
 def _sort(P, a, lo, n, split, axis):
@@ -161,6 +171,128 @@ def lane_find(L, m, q, maxd2):
     rc = L.oct_host_find(m.nodes.ctypes.data, m.pts.ctypes.data, add.ctypes.data, float(m.mult), int(m.largest_index), int(m.top_bit),
                          q.ctypes.data, K, float(maxd2), slot.ctypes.data, d2.ctypes.data, leaves.ctypes.data)
     return None if rc else (slot, d2, leaves)
+
+
+_models = {}
+
+
+def model_of(fx, name, voxel, early):
+    """the restatement over a fixture's cloud, built once per (fixture, case)"""
+    key = (id(fx), name, voxel, early)
+    if key not in _models:
+        _models[key] = (fx, Model(fx.cloud(name), voxel, early))
+    return _models[key][1]
+
+
+def check_model_equals_fixture(fx, m, name, voxel, early):
+    """the restatement's tree is the reference's: init()'s scalars by bits, countNodes / countOctLeaves / countPoints, the
+    full leaf order; the table's own invariants"""
+    pts = fx.cloud(name)
+    assert same_bits(m.scalars, fx.get(name, voxel, early, "scalars"))
+    assert [m.n_nodes, m.n_leaves, len(pts)] == [int(v) for v in fx.get(name, voxel, early, "counts")]
+    assert same_bits(pts[m.leaf], pts[fx.get(name, voxel, early, "leaf")])
+    # the table's own invariants: children in ascending child index behind `first`, leaf runs tile the point array in order
+    valid = m.nodes[:, 0] & 0xFF
+    leafm = (m.nodes[:, 0] >> 8) & 0xFF
+    assert (leafm & ~valid).sum() == 0
+    runs = []
+    for s in range(len(m.nodes)):
+        k = 0
+        for ci in range(8):
+            if (valid[s] >> ci) & 1:
+                ch = m.nodes[s, 1] + k
+                k += 1
+                if (leafm[s] >> ci) & 1:
+                    runs.append((int(m.nodes[ch, 2]), int(m.nodes[ch, 3])))
+    runs.sort()
+    assert runs[0][0] == 0 and all(a[0] + a[1] == b[0] for a, b in zip(runs, runs[1:])) and runs[-1][0] + runs[-1][1] == len(pts)
+    assert len(runs) == m.n_leaves
+
+
+def check_lane_equals_batches(L, m, fx, name, voxel, early):
+    """FindClosest of every query of every batch: the returned point (as the first position in leaf order with its
+    coordinates: what strict < returns), Dist2 and the leaves scanned, by bits; returns the number of queries compared"""
+    n = 0
+    for qq, maxd2, pos, d2, leaves in fx.batches(name, voxel, early):
+        slot, gd2, gl = lane_find(L, m, qq, maxd2)
+        assert np.array_equal(slot, pos), (name, voxel, early, maxd2, np.flatnonzero(slot != pos)[:5])
+        assert same_bits(gd2, d2) and np.array_equal(gl, leaves), (name, voxel, early, maxd2)
+        n += len(qq)
+    return n
+
+
+def expect_idx(order, pos):
+    """fixture positions in leaf order -> the caller's indices the device returns for them"""
+    return np.where(pos >= 0, order[np.maximum(pos, 0)], -1).astype(np.int32)
+
+
+def check_sums(got, model, A, want, producer, nrm=None, D=None):
+    """the sums inside the tolerance pair_sums_ref derives from the pair list the call returned"""
+    import pair_sums_ref as R
+    shift = R.shift_of(model, A)
+    fin = R.finished(got["p1"], got["p2"], nrm, shift, want, D)
+    disc = R.discrimination(got["p1"], got["p2"], nrm, shift, want, D, fin=fin)
+    R.check_struct(got["_raw"], fin, disc, producer)
+
+
+def info_scalars(info):
+    """BOctTree.info() in the order of the fixtures' `scalars`"""
+    return np.array([info["max_depth"], info["real_voxelSize"], info["mult"], *info["add"], info["largest_index"], info["size"],
+                     *info["center"]], np.float64)
+
+
+def horn(p1, p2):
+    """a rigid motion that takes p2 onto p1 in the least-squares sense (SVD), column-major like the library's"""
+    c1, c2 = p1.mean(0), p2.mean(0)
+    U, _, Vt = np.linalg.svd((p2 - c2).T @ (p1 - c1))
+    R = (U @ np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt))]) @ Vt).T
+    A = np.eye(4)
+    A[:3, :3], A[:3, 3] = R, c1 - R @ c2
+    return A.T.reshape(16)
+
+
+# ---- the refusal bound: what the entry points admit may not let x +- closest_v leave int32 ----------------------------------------
+TWO30 = 2.0 ** 30
+
+
+def bound_tree():
+    """[[-1,-1,-1],[1,1,1]] at voxel 0.1: mult 16, add 2"""
+    m = Model(np.array([[-1.0, -1.0, -1.0], [1.0, 1.0, 1.0]]), 0.1, False)
+    assert m.mult == 16.0 and (m.add == 2.0).all()
+    return m
+
+
+def bound_cv(m, maxd2):
+    return np.sqrt(maxd2) * m.mult + 1
+
+
+def bound_cases(m):
+    """[(tag, query, maxdist2, admitted)] around |v| == 2^30.  The radii are found by stepping nextafter around
+    ((2^30 - 1) / mult)^2: `exact` is one whose sqrt * mult + 1 is 2^30, `below` the largest under it whose value is smaller."""
+    exact = ((TWO30 - 1) / m.mult) ** 2
+    for _ in range(64):
+        if bound_cv(m, exact) == TWO30:
+            break
+        exact = np.nextafter(exact, np.inf if bound_cv(m, exact) < TWO30 else -np.inf)
+    assert bound_cv(m, exact) == TWO30
+    below = exact
+    for _ in range(64):
+        if bound_cv(m, below) < TWO30:
+            break
+        below = np.nextafter(below, -np.inf)
+    assert bound_cv(m, below) < TWO30 <= bound_cv(m, np.nextafter(below, np.inf)) and int(bound_cv(m, below)) == 2 ** 30 - 1
+    hi, lo = TWO30 / m.mult - 2.0, -TWO30 / m.mult - 2.0              # (q + add) * mult == +-2^30 exactly
+    assert (hi + 2.0) * 16.0 == TWO30 and (lo + 2.0) * 16.0 == -TWO30
+    hi_in, lo_in = np.nextafter(hi, 0.0), np.nextafter(lo, 0.0)
+    assert int((hi_in + 2.0) * 16.0) == 2 ** 30 - 1 and int((lo_in + 2.0) * 16.0) == -(2 ** 30 - 1)
+    q = lambda x: np.array([[x, 0.25, -0.5]])                         # noqa: E731
+    return [("x=+2^30, cv=2^30", q(hi), exact, False), ("x=-2^30, cv=2^30", q(lo), exact, False),
+            ("x=+2^30 alone", q(hi), 625.0, False), ("x=-2^30 alone", q(lo), 625.0, False),
+            ("cv=2^30 alone", q(0.0), exact, False), ("cv=2^30 alone, y", np.array([[0.0, hi, 0.0]]), 625.0, False),
+            ("x=2^30-1, cv=2^30-1", q(hi_in), below, True), ("x=-(2^30-1), cv=2^30-1", q(lo_in), below, True),
+            ("x=2^30-1 alone", q(hi_in), 625.0, True), ("x=-(2^30-1) alone", q(lo_in), 625.0, True),
+            ("cv=2^30-1 alone", q(0.0), below, True),
+            ("all three axes at the bound", np.array([[hi_in, lo_in, hi_in], [lo_in, hi_in, lo_in]]), below, True)]
 
 
 def same_bits(a, b):

@@ -22,6 +22,7 @@ struct HostOctStack {
 using namespace tdtk;
 
 // FindClosest for K queries over a node table and a leaf-ordered point array; -1 when the entry point would refuse the batch
+// (oct_in_range, the one statement of the rule: a value not strictly inside +-2^30)
 extern "C" int oct_host_find(const void* nodes, const void* pts, const double* add, double mult, int largest_index, unsigned top_bit,
                              const double* q, int K, double maxd2, int* slot, double* d2, int* leaves)
 {

@@ -26,14 +26,8 @@ def lane(tmp_path_factory):
     return bm.host_lane(tmp_path_factory.mktemp("oct_host"))
 
 
-_models = {}
-
-
 def _model(fx, name, voxel, early):
-    key = (name, voxel, early)
-    if key not in _models:
-        _models[key] = bm.Model(fx.cloud(name), voxel, early)
-    return _models[key]
+    return bm.model_of(fx, name, voxel, early)
 
 
 def test_fixture_is_what_the_generator_says(fx):
@@ -55,27 +49,7 @@ def test_fixture_is_what_the_generator_says(fx):
 def test_model_equals_fixture(fx, name, voxel, early):
     """the restatement's tree is the reference's: init()'s scalars by bits, countNodes / countOctLeaves / countPoints, the
     full leaf order"""
-    m = _model(fx, name, voxel, early)
-    pts = fx.cloud(name)
-    assert bm.same_bits(m.scalars, fx.get(name, voxel, early, "scalars"))
-    assert [m.n_nodes, m.n_leaves, len(pts)] == [int(v) for v in fx.get(name, voxel, early, "counts")]
-    assert bm.same_bits(pts[m.leaf], pts[fx.get(name, voxel, early, "leaf")])
-    # the table's own invariants: children in ascending child index behind `first`, leaf runs tile the point array in order
-    valid = m.nodes[:, 0] & 0xFF
-    leafm = (m.nodes[:, 0] >> 8) & 0xFF
-    assert (leafm & ~valid).sum() == 0
-    runs = []
-    for s in range(len(m.nodes)):
-        k = 0
-        for ci in range(8):
-            if (valid[s] >> ci) & 1:
-                ch = m.nodes[s, 1] + k
-                k += 1
-                if (leafm[s] >> ci) & 1:
-                    runs.append((int(m.nodes[ch, 2]), int(m.nodes[ch, 3])))
-    runs.sort()
-    assert runs[0][0] == 0 and all(a[0] + a[1] == b[0] for a, b in zip(runs, runs[1:])) and runs[-1][0] + runs[-1][1] == len(pts)
-    assert len(runs) == m.n_leaves
+    bm.check_model_equals_fixture(fx, _model(fx, name, voxel, early), name, voxel, early)
 
 
 @pytest.mark.parametrize("name,voxel,early", CASES)
@@ -83,12 +57,7 @@ def test_host_lane_equals_fixture(fx, lane, name, voxel, early):
     """FindClosest of every query of every batch: the returned point (as the first position in leaf order with its
     coordinates: what strict < returns), Dist2 and the leaves scanned, by bits; no case and no query left out"""
     m = _model(fx, name, voxel, early)
-    n = 0
-    for qq, maxd2, pos, d2, leaves in fx.batches(name, voxel, early):
-        slot, gd2, gl = bm.lane_find(lane, m, qq, maxd2)
-        assert np.array_equal(slot, pos), (name, voxel, early, np.flatnonzero(slot != pos)[:5])
-        assert bm.same_bits(gd2, d2) and np.array_equal(gl, leaves)
-        n += len(qq)
+    n = bm.check_lane_equals_batches(lane, m, fx, name, voxel, early)
     if (name, voxel, early) in set(gen.EDGE_CASES):
         for q1, maxd2, pos, d2, leaves in fx.edge(name, voxel, early):          # maxdist2 == d2 and one ulp above, per query
             slot, gd2, gl = bm.lane_find(lane, m, q1[None], maxd2)
@@ -191,16 +160,6 @@ extern "C" void hq_two_nearest(void* p, const double* q, int nq, int* idx, doubl
 """
 
 
-def _horn(p1, p2):
-    """a rigid motion that takes p2 onto p1 in the least-squares sense (SVD), column-major like the library's"""
-    c1, c2 = p1.mean(0), p2.mean(0)
-    U, _, Vt = np.linalg.svd((p2 - c2).T @ (p1 - c1))
-    R = (U @ np.diag([1.0, 1.0, np.sign(np.linalg.det(U @ Vt))]) @ Vt).T
-    A = np.eye(4)
-    A[:3, :3], A[:3, 3] = R, c1 - R @ c2
-    return A.T.reshape(16)
-
-
 def test_dat_pair_is_tie_free_along_an_icp(lane, tmp_path):
     """What the GPU tier's five-iteration ICP by hand relies on when it asks the octree's pair lists to equal the k-d tree's:
     on the bundled pair, along five iterations of a closest-point ICP at maxdist2 625, every query's nearest model point is
@@ -222,7 +181,7 @@ def test_dat_pair_is_tie_free_along_an_icp(lane, tmp_path):
             slot, od2, leaves = bm.lane_find(lane, m, cur, 625.0)
             assert np.array_equal(np.where(slot >= 0, m.leaf[np.maximum(slot, 0)], -1), np.where(hit, idx[:, 0], -1)), it
             assert bm.same_bits(od2[hit], d2[hit, 0]) and leaves.max() < 5000
-            cur = bm.move(cur, _horn(model[idx[hit, 0]], cur[hit]))
+            cur = bm.move(cur, bm.horn(model[idx[hit, 0]], cur[hit]))
     finally:
         L.host_tree_destroy(C.c_void_p(T))
 

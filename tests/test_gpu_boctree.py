@@ -26,9 +26,7 @@ def fx():
     return gen.load()
 
 
-def _expect_idx(order, pos):
-    """fixture positions in leaf order -> the caller's indices the device returns for them"""
-    return np.where(pos >= 0, order[np.maximum(pos, 0)], -1).astype(np.int32)
+_expect_idx, _check_sums = bm.expect_idx, bm.check_sums
 
 
 @pytest.mark.parametrize("name,voxel,early", CASES)
@@ -141,14 +139,6 @@ def test_second_tree_after_destroy_reuses_pooled_blocks(tdtk, gpu, fx):
         assert first[0][k] == again[0][k]
     assert np.array_equal(first[1], again[1])
     assert np.array_equal(first[2][0], again[2][0]) and bm.same_bits(first[2][1], again[2][1])
-
-
-def _check_sums(got, model, A, want, producer, nrm=None):
-    """the sums inside the tolerance pair_sums_ref derives from the pair list the call returned"""
-    shift = R.shift_of(model, A)
-    fin = R.finished(got["p1"], got["p2"], nrm, shift, want)
-    disc = R.discrimination(got["p1"], got["p2"], nrm, shift, want, fin=fin)
-    R.check_struct(got["_raw"], fin, disc, producer)
 
 
 def test_get_pt_pairs_equals_kdtree_on_the_tie_free_pair(tdtk, gpu):

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 
 import boctree_model as bm
+from boctree_icp_run import POSE_ATOL, Z3
+from boctree_icp_run import c_match as _c_match, model_scan as _model_scan, resident_against_stepped as _resident_against_stepped, run as _run
 from boctree_model import dat_pair
 
 pytestmark = pytest.mark.gpu
@@ -25,8 +27,6 @@ def _generator():
 
 gen = _generator()
 RUN_IDS = [gen.prefix(r).rstrip("_") for r in gen.RUNS]
-Z3 = [0.0, 0.0, 0.0]
-POSE_ATOL = 1e-9          # the project's pose bound
 
 
 @pytest.fixture(scope="module")
@@ -40,34 +40,6 @@ def hashes(tdtk):
     was = tdtk.lib().tdtk_icp_index_hashes(1)
     yield True
     tdtk.lib().tdtk_icp_index_hashes(was)
-
-
-def _minimizer(tdtk, algo):
-    return {1: tdtk.icp6D_QUAT, 2: tdtk.icp6D_SVD, 5: tdtk.icp6D_HELIX, 6: tdtk.icp6D_APX, 10: tdtk.icp6D_NAPX}[algo](True)
-
-
-def _model_scan(tdtk, model, nns, voxel=10.0, early=1):
-    """the model scan (pose zero: its original points are `model`) with its tree built"""
-    s = tdtk.Scan(Z3, Z3, model).setSearchTreeParameter(nns)
-    if nns == 2 and (voxel, early) != (10.0, 1):
-        s.kd = tdtk.BOctTree(model, voxel, bool(early))          # a tree other than createSearchTreePrivate's
-    s.getSearchTree()
-    return s
-
-
-def _run(tdtk, prev, data, normals, algo, mode, maxd2, iters, eps, rnd=1, stepped=False):
-    cur = tdtk.Scan(Z3, Z3, data, normals)
-    _ = cur.handle
-    icp = tdtk.icp6D(_minimizer(tdtk, algo), float(np.sqrt(maxd2)), iters, quiet=True, rnd=rnd, epsilonICP=eps)
-    assert icp.max_dist_match2 == maxd2
-    if rnd > 1:
-        C.CDLL(None).srand(11)
-    if stepped:
-        icp.stepped_rnd = True
-        it = icp._match_stepped(prev, cur, mode)
-    else:
-        it = icp.match(prev, cur, mode)
-    return it, icp.last, cur
 
 
 @pytest.mark.parametrize("run", gen.RUNS, ids=RUN_IDS)
@@ -104,24 +76,6 @@ def test_every_fixture_run(tdtk, gpu, fx, hashes, run):
         assert all(a != b for a, b in zip(klast["index_hashes"][2:], last["index_hashes"][2:]))
 
 
-def _resident_against_stepped(tdtk, model, data, maxd2, iters):
-    prev = _model_scan(tdtk, model, 2)
-    it, last, cur = _run(tdtk, prev, data, None, 1, 0, maxd2, iters, 0.0)
-    sit, slast, scur = _run(tdtk, prev, data, None, 1, 0, maxd2, iters, 0.0, stepped=True)
-    assert it == sit == iters - 1 and len(last["trace"]) == len(slast["trace"]) == iters
-    print("max |alignxf resident - stepped|", np.abs(last["trace"][:, 2:] - slast["trace"][:, 2:]).max())
-    assert np.array_equal(last["trace"][:, 0], slast["trace"][:, 0])
-    assert np.allclose(last["trace"][:, 2:], slast["trace"][:, 2:], rtol=0, atol=POSE_ATOL)
-    # the scan behind the resident loop: a copy moved by tdtk_scan_transform with the loop's own alignxf, row by row -- by bits
-    copy = tdtk.Scan(Z3, Z3, data)
-    for row in last["trace"]:
-        A = np.ascontiguousarray(row[2:])
-        assert tdtk.lib().tdtk_scan_transform(copy.handle, A.ctypes.data_as(C.POINTER(C.c_double))) == 0
-    assert bm.same_bits(cur.get_xyz_reduced(), copy.get_xyz_reduced())
-    assert np.allclose(cur.get_transMat(), scur.get_transMat(), rtol=0, atol=1e-8)
-    return last
-
-
 def test_resident_loop_equals_the_stepped_loop_on_the_seam(tdtk, gpu, fx, hashes):
     model, data, _ = gen.cloud_of(fx, "seam")
     _resident_against_stepped(tdtk, model, data, gen.SEAM_MAXD2, gen.SEAM_ITERS)
@@ -148,20 +102,6 @@ def test_rnd_resident_equals_stepped(tdtk, gpu, fx):
     assert (last["trace"][:, 0] < len(data) / 2).all() and (last["trace"][:, 0] > 3).all()
     assert len(set(last["trace"][:, 0])) > 1                                  # a fresh draw per iteration
     assert np.allclose(last["trace"][:, 2:], slast["trace"][:, 2:], rtol=0, atol=POSE_ATOL)
-
-
-def _c_match(tdtk, fn, tree_h, scan_h, algo, mode, iters, maxd2, eps=0.0):
-    capi = tdtk.lib
-    from importlib import import_module
-    cm = import_module("3dtk_amd._capi")
-    prm = cm.IcpParams(int(algo), int(mode), int(iters), float(maxd2), float(eps), 1)
-    res = cm.IcpResult()
-    tm, da = np.eye(4).reshape(16).copy(), np.eye(4).reshape(16).copy()
-    trace = np.zeros((max(1, iters), 18))
-    dp = C.POINTER(C.c_double)
-    rc = getattr(capi(), fn)(tree_h, gen.I16.ctypes.data_as(dp), scan_h, tm.ctypes.data_as(dp), da.ctypes.data_as(dp), C.byref(prm),
-                             C.byref(res), trace.ctypes.data_as(dp), len(trace))
-    return rc, res, tm, da, trace
 
 
 def test_refusals(tdtk, gpu, fx):
