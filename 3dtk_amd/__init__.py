@@ -31,3 +31,4 @@ from .slam6d import (KDtree, BOctTree, Scan, icp6Dminimizer, icp6D_QUAT, icp6D_S
 from .collision import read_trajectory, handle_pointcloud, calculate_collidingdist, calculate_collidingdist2, segment_colliding  # noqa: F401
 from .peopleremover import walk_voxels, peopleremover, synthetic_room  # noqa: F401  (the function, not the module, is the name)
 from .bkd import BkdTree  # noqa: F401
+from .hough import ConfigFileHough, Hough, hough_normals  # noqa: F401

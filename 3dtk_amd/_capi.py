@@ -75,6 +75,8 @@ EXPORTS = [
     "tdtk_fixed_range_search_along_dir", "tdtk_fixed_range_search_between", "tdtk_aabb_search", "tdtk_segment_search_all",
     "tdtk_segment_search_nearest", "tdtk_collision_mark", "tdtk_collision_depth_closest", "tdtk_collision_depth_axis",
     "tdtk_cluster_radius", "tdtk_cluster_grid_cap", "tdtk_voxel_walk", "tdtk_peopleremover", "tdtk_peopleremover_timings",
+    "tdtk_hough_normals", "tdtk_hough_vote", "tdtk_hough_peaks", "tdtk_hough_cell_plane", "tdtk_hough_plane_points",
+    "tdtk_hough_fit_plane", "tdtk_hough_timings",
     "tdtk_forest_create", "tdtk_forest_create_from_points", "tdtk_forest_destroy", "tdtk_forest_insert", "tdtk_forest_last_insert", "tdtk_forest_remove", "tdtk_forest_info",
     "tdtk_forest_collect", "tdtk_forest_find_closest", "tdtk_forest_knn", "tdtk_forest_fixed_range", "tdtk_forest_plan",
     "tdtk_octree_create", "tdtk_octree_create_from_scan", "tdtk_octree_destroy", "tdtk_octree_get_info", "tdtk_octree_leaf_order", "tdtk_octree_node_table",
@@ -184,6 +186,14 @@ def lib():
     L.tdtk_peopleremover.argtypes = [C.c_int, _dp, _u64p, _dp, _dp, C.c_size_t, C.c_double, C.c_uint64, C.c_uint64, C.c_int,
                                      C.POINTER(C.c_uint8), _ip, C.c_size_t, _u64p]
     L.tdtk_peopleremover_timings.argtypes = [_dp]
+    L.tdtk_hough_normals.argtypes = [C.c_int, _u32p, _dp, C.c_size_t, C.POINTER(C.c_size_t), _ip]
+    L.tdtk_hough_vote.argtypes = [C.c_int, _dp, C.c_size_t, _dp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_double, _ip]
+    L.tdtk_hough_peaks.argtypes = [C.c_int, _ip, C.c_int, _u32p, C.c_double, _ip, C.c_size_t, _u64p, _ip]
+    L.tdtk_hough_cell_plane.argtypes = [C.c_int, _u32p, _ip, _dp]
+    L.tdtk_hough_plane_points.argtypes = [C.c_int, _dp, C.c_size_t, _dp, C.c_double, C.c_double, C.POINTER(C.c_uint8), _ip,
+                                          C.c_size_t, _u64p]
+    L.tdtk_hough_fit_plane.argtypes = [C.c_int, _dp, C.c_size_t, _ip, C.c_size_t, _dp, _dp]
+    L.tdtk_hough_timings.argtypes = [_dp]
     L.tdtk_forest_create.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.tdtk_forest_create_from_points.argtypes = [_dp, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.tdtk_forest_destroy.argtypes = [C.c_void_p]

@@ -155,6 +155,12 @@ struct Ctx {
   // WS_CERT holds the certificates (SearchArgs::cert) the last scan_pass of the running tdtk_icp_match loop wrote for exactly
   // the queries and the tree of its next pass: set by a pass that wrote them, cleared by every other pass and where a loop starts
   bool cert_live = false;
+  // the Hough transform's own buffers (api_hough.cpp): the cloud of the last call that uploaded one, the last vote's table and
+  // counts -- kept from call to call, so a Hough object's steps upload the cloud once and peaks read the vote's counts in place
+  DevBuf hough_xyz, hough_normals, hough_counts, hough_rho;
+  size_t hough_n = 0, hough_cells = 0;
+  uint32_t hough_rho_num = 0;
+  bool hough_have_xyz = false, hough_have_counts = false;
   // a context dies with its host thread (worker threads of a prefetch pool come and go): give everything back
   ~Ctx();
 };

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "hough_geom.h"
 #include "tdtk_internal.h"
 
 namespace tdtk {
@@ -322,6 +323,24 @@ static void jacobi_eigen(double A[N][N], double V[N][N], double w[N])
       }
   }
   for (int i = 0; i < N; i++) w[i] = A[i][i];
+}
+
+// calcPlane's ending (src/shapes/hough.cc:1283-1309): the eigenvector of the eigenvalue smallest in absolute value (the first
+// such, as MinimumAbsoluteValue1 does), plane[3] = n . centroid, planarity = that eigenvalue over the sum of the three
+void hough_plane_from_moments(const double c[3], const double m[6], double plane[4], double* planarity)
+{
+  double A[3][3] = {{m[0], m[3], m[4]}, {m[3], m[1], m[5]}, {m[4], m[5], m[2]}}, V[3][3], w[3];
+  jacobi_eigen<3>(A, V, w);
+  int index = 0;
+  for (int i = 1; i < 3; i++)
+    if (std::fabs(w[i]) < std::fabs(w[index])) index = i;
+  plane[0] = V[0][index];
+  plane[1] = V[1][index];
+  plane[2] = V[2][index];
+  plane[3] = plane[0] * c[0] + plane[1] * c[1] + plane[2] * c[2];
+  double sum = 0.0;
+  for (int i = 0; i < 3; i++) sum += w[i];
+  *planarity = w[index] / sum;
 }
 
 // one-sided (Hestenes) Jacobi SVD of a 3x3: H = U diag(sv) V^T

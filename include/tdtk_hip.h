@@ -315,6 +315,71 @@ int tdtk_peopleremover(int device, const double* xyz, const uint64_t* scan_offse
 /* HIP-event times of the calling thread's last tdtk_peopleremover, ms: occupancy build, walk, cluster + half-free +
  * classification, and first upload to last download.                                                                 */
 int tdtk_peopleremover_timings(double* ms4);
+/* ---- the standard 3D Hough transform for plane detection (src/shapes: Hough::SHT hough.cc:222-265, accumulator.cc), up to
+ * plane candidates.  An accumulator is C cells (plane directions) x RhoNum bins of rho; counts [C][RhoNum] int32, cell-major.
+ * Accumulator types as ConfigFileHough's AccumulatorType: 0 Simple, 1 Ball, 2 Cube, 3 BallI.  dims [4] = { RhoNum, PhiNum,
+ * ThetaNum, RhoMax }, the reference's unsigned ints.  An entry of a peak list is the reference's int array: (count, rho,
+ * theta, phi) for types 0, 1, 3, (count, rho, face, i, j) for type 2.  Not covered: the randomized variants (RHT, PHT, PPHT,
+ * APHT), peakWindow, accumulate(theta, phi, rho) / accumulateRet / accumulateAPHT, and the second half of deletePoints
+ * (projection, clustering, convex hull, the deletion of points between peaks).
+ *
+ * The cell normals of an accumulator, host only: the n of Accumulator*::accumulate(Point) for every cell, in the order of that
+ * type's getMax() loops without the rho loop (phi, theta; type 2: face, i, j), quirks as written -- the 0.99999999999 /
+ * 0.999999999 factors in phi, the clamps, Normalize3 on every normal, BallI's south pole recognised by i == RhoNum - 1 (which
+ * makes RhoNum an input of type 3's table; it is dims[0] for every type).  *C (always filled when the arguments pass) is the
+ * number of cells; slice_sizes (nullable) [PhiNum] the cells per phi slice (type 2: [6], nrCells^2 each); normals [cap][3],
+ * written when cap >= *C, else nothing is and the call returns TDTK_EINVAL (normals NULL with cap 0: a count).
+ * TDTK_EINVAL, in this order: NULL dims or C; type outside 0 .. 3; RhoNum, PhiNum or ThetaNum 0.  TDTK_EUNSUP: PhiNum or
+ * ThetaNum >= 2^24; the (PhiNum, ThetaNum) for which the reference's constructor writes outside ballNr or leaves a slice
+ * unsized -- type 1: ThetaNum < 2, or a PhiNum whose slice loop (phi += 180.0 / PhiNum while phi < 180.0) does not run
+ * exactly PhiNum times; type 2: ThetaNum < 4; type 3: PhiNum < 3 (the message says which).                        */
+int tdtk_hough_normals(int type, const uint32_t* dims, double* normals, size_t cap, size_t* C, int32_t* slice_sizes);
+/* Accumulator*::accumulate(Point) for every point: counts[c][k] = the points with fabs(p.n_c - rho_k) < D, rho_k = (k + 0.5)
+ * * RhoMax / RhoNum, the reference's expressions operation for operation (hough_lane.h) -- the reference's counts bit for bit
+ * over the same table.  xyz [N][3] host memory, or NULL: the cloud the calling thread uploaded last on this device (N must be
+ * its size).  normals [C][3] host memory: the table is an argument (tdtk_hough_normals gives the reference's).  counts
+ * (nullable) [C][RhoNum] host memory; they also stay on the device for tdtk_hough_peaks.  Any RhoNum >= 1; N == 0 gives
+ * zeros.  Checked in this order: NULL normals (TDTK_EINVAL); N >= 2^31 (TDTK_EUNSUP); C or RhoNum 0 (TDTK_EINVAL); C *
+ * RhoNum >= 2^31 (TDTK_EUNSUP); xyz NULL and no resident cloud of N points (TDTK_EINVAL).  Coordinates are not checked: a
+ * NaN votes nowhere, as in the reference.                                                                              */
+int tdtk_hough_vote(int device, const double* xyz, size_t N, const double* normals, size_t C, uint32_t RhoNum, uint32_t RhoMax,
+                    double D, int32_t* counts);
+/* The head of Accumulator*::getMax()'s multiset: the entries with count > (int)(max * PlaneRatio), max the largest count
+ * (Hough::SHT's loop condition, hough.cc:248-253), count descending, equal counts in that type's insertion order (rho, phi,
+ * theta for types 0, 1, 3; face, i, j, rho for type 2 -- std::multiset::insert puts an equal key behind its equals).  counts
+ * [C][RhoNum] host memory, or NULL: the counts of the calling thread's last tdtk_hough_vote on this device, whose C and
+ * RhoNum must be this accumulator's.  *n and *max are always filled; cells [cap][4 or 5] is written when cap >= *n, else
+ * nothing is and the call returns TDTK_EINVAL (tdtk_fixed_range_search's contract).  The device finds the maximum and
+ * compacts the entries; their final order is made on the host.  Checked in this order: NULL dims, n or max, a NaN
+ * PlaneRatio (TDTK_EINVAL); tdtk_hough_normals' checks of type and dims; C * RhoNum >= 2^31 (TDTK_EUNSUP); counts NULL
+ * without a matching vote (TDTK_EINVAL).                                                                               */
+int tdtk_hough_peaks(int device, const int32_t* counts, int type, const uint32_t* dims, double PlaneRatio, int32_t* cells,
+                     size_t cap, uint64_t* n, int32_t* max);
+/* Accumulator*::getMax(int* cell), host only: the plane { nx, ny, nz, rho } at the centre of a cell, as written for each type
+ * -- not the vote's formulas (no 0.999.. factor in phi), and for type 2 the reference reads the entry as (rho, face - 1, i, j)
+ * from cell[0 .. 3], which is not the layout its getMax() lists: cell[0] (the count) becomes rho's bin, cell[1] + 1 the face;
+ * a face outside 1 .. 6 gives NaN normals (the reference: uninitialised memory).  cell [4] (type 2: [5]).
+ * TDTK_EINVAL: NULL; a phi index outside the accumulator (types 1, 3: it selects the slice size); then
+ * tdtk_hough_normals' checks of type and dims.                                                                        */
+int tdtk_hough_cell_plane(int type, const uint32_t* dims, const int32_t* cell, double* plane4);
+/* deletePoints' first loop (hough.cc:759-779): n is normalised first (Normalize3, on a copy), then mask[i] = fabs(p.x*n[0]
+ * + p.y*n[1] + p.z*n[2] - rho) < D.  xyz as in tdtk_hough_vote.  mask (nullable) [N] bytes; *count is always filled;
+ * indices [cap] the points in input order, written when cap >= *count, else they are not and the call returns TDTK_EINVAL
+ * (indices NULL with cap 0 and mask given: mask and count only, TDTK_OK).  TDTK_EINVAL: NULL n or count; no cloud.
+ * TDTK_EUNSUP: N >= 2^31.                                                                                             */
+int tdtk_hough_plane_points(int device, const double* xyz, size_t N, const double* n, double rho, double D, uint8_t* mask,
+                            int32_t* indices, size_t cap, uint64_t* count);
+/* calcPlane (hough.cc:1252-1310) over the points xyz[indices[0 .. m)]: centroid, the six centred second moments about it
+ * (two fp64 passes on the device, summed in a fixed order: the same bits every run, not the reference's sequential order),
+ * then on the host a Jacobi eigensolver, the eigenvector of the eigenvalue smallest in absolute value, plane4[3] = n .
+ * centroid and *planarity = that eigenvalue / the sum of the three.  m < 3: *planarity = 0, plane4 untouched, TDTK_OK, as
+ * calcPlane returns.  TDTK_EINVAL: NULL indices (with m > 0), plane4 or planarity; no cloud; an index outside [0, N).  */
+int tdtk_hough_fit_plane(int device, const double* xyz, size_t N, const int32_t* indices, size_t m, double* plane4,
+                         double* planarity);
+/* ms5: HIP-event times, ms, of the calling thread's last vote (kernels only), peaks, plane_points and fit_plane (kernels and
+ * their small copies), and [4] how often this thread's Hough device buffers were (re)allocated so far: a second vote of the
+ * same size allocates nothing.                                                                                        */
+int tdtk_hough_timings(double* ms5);
 /* ---- the dynamic kd-forest: BkdTree (include/slam6d/bkd.h, src/slam6d/bkd.cc), the logarithmic method over the device
  * kd-trees.  A forest is a buffer of fewer than `bucket` points and slots 0 .. S-1 (S <= 32), each empty or one kd-tree with
  * a live-point count.  Every inserted point gets an id: the running insertion counter (the reference returns pointers).  The

@@ -43,6 +43,14 @@ download; the voxel visits and visits per second of the walk; the walk again wit
 (what divergent ray lengths inside a wave cost).  The reference's time for the same input comes from
 `python tests/golden/make_golden_peopleremover.py --time` on a machine that has the checkout (one host thread).
 
+--only-hough runs the standard 3D Hough transform (3dtk_amd.Hough, tdtk_hough_*) alone, at the reference's default settings
+(AccumulatorBallI, RhoNum 500, PhiNum 176, ThetaNum 360, RhoMax 1500, MaxPointPlaneDist 1.5) on one scan of 1M points of
+3dtk_amd.synthetic_room's box room.  Warm, the minimum of --reps runs, from HIP events: the vote, the peak list, one
+plane_points + fit_plane on the first peak; point-cell pairs per second of the vote and the fp64 rate they stand for (5 flops
+per pair: three products, two additions; the window and the predicate come on top).  The reference's time for the same vote
+comes from `python tests/golden/make_golden_hough.py --time` on a machine that has the checkout: accumulate(Point) over 100
+points on one host thread, times N / 100 (the loop is serial and linear in N).
+
 --only-forest runs the dynamic kd-forest (3dtk_amd.BkdTree, tdtk_forest_*) alone: a uniform map (density 1) grown from 0 to
 1M points by scans of 100 000 at bucket 20.  Warm, the minimum of --reps runs, per scan: the insert call end to end and its
 stages (the plan on the host clock, the gathers and the builds from HIP events), the slots it built and the occupied slots
@@ -406,6 +414,50 @@ def peopleremover_legs(tdtk, reps):
     return out
 
 
+def hough_legs(tdtk, reps):
+    """the vote, the peaks and one plane's points and fit at the reference's defaults (see the module docstring)"""
+    hough = importlib.import_module("3dtk_amd.hough")
+    scans, _ = tdtk.synthetic_room(1, 1_000_000, seed=22)
+    cfg = hough.ConfigFileHough()
+    h = hough.Hough(scans[0], cfg)
+    cells, n = len(h.normals), len(h.points)
+    out = {"hough_points": n, "hough_cells": cells, "hough_rho_bins": int(cfg.RhoNum)}
+    best = {}
+
+    def keep(key):
+        ms = hough.last_timings()[key]
+        best[key] = min(best.get(key, ms), ms)
+    t0 = time.perf_counter()
+    cand = None
+    for rep in range(reps + 1):                        # the first run is the warm-up
+        if rep == 1:
+            best.clear()
+        h.votes()
+        keep("vote_ms")
+        h._resident = True                             # the steps behind the vote read the cloud and the counts in place
+        try:
+            peaks = h.peaks()
+            keep("peaks_ms")
+            plane = h.cell_plane(peaks[0])
+            _, idx = h.plane_points(plane[:3], plane[3])
+            keep("plane_points_ms")
+            fit, planarity = h.fit_plane(idx)
+            keep("fit_ms")
+        finally:
+            h._resident = False
+        cand = dict(cell=peaks[0].tolist(), plane=plane.tolist(), inliers=int(len(idx)),
+                    fit=None if fit is None else fit.tolist(), planarity=planarity)
+    out["hough_loop_wall_s"] = round(time.perf_counter() - t0, 3)
+    for k, v in best.items():
+        out["hough_" + k] = round(v, 3)
+    pairs = float(n) * cells
+    out["hough_Gpairs_per_s"] = round(pairs / best["vote_ms"] / 1e6, 2)
+    out["hough_vote_fp64_Tflops"] = round(5 * pairs / best["vote_ms"] / 1e9, 3)
+    out["hough_peaks"] = int(len(peaks))
+    out["hough_first_candidate"] = cand
+    return out
+
+
 def forest_legs(tdtk, reps):
     """the dynamic kd-forest against the full rebuild and the single tree (see the module docstring)"""
     n_scans, per = 10, 100_000
@@ -561,6 +613,7 @@ def main():
     ap.add_argument("--clusters", action="store_true", help="add the radius-clustering legs (1M points, two radii)")
     ap.add_argument("--only-clusters", action="store_true", help="those legs alone")
     ap.add_argument("--only-peopleremover", action="store_true", help="dynamic-object removal on a synthetic room, alone")
+    ap.add_argument("--only-hough", action="store_true", help="the standard 3D Hough transform at the reference's defaults, alone")
     ap.add_argument("--only-forest", action="store_true", help="the dynamic kd-forest against rebuilds and the single tree, alone")
     ap.add_argument("--only-octree", action="store_true", help="FindClosestBatch on the octree and on the k-d tree, alone")
     ap.add_argument("--only-octree-icp", action="store_true", help="the resident octree ICP loop against the host-stepped one, alone")
@@ -571,6 +624,10 @@ def main():
     out = {"workload": "kdtree_queries", "reps": args.reps}
     if args.only_peopleremover:
         out.update(peopleremover_legs(tdtk, args.reps))
+        print(json.dumps(out))
+        return
+    if args.only_hough:
+        out.update(hough_legs(tdtk, args.reps))
         print(json.dumps(out))
         return
     if args.only_forest:
