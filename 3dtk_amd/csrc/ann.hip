@@ -19,6 +19,8 @@
 //     one thread per scan point, in leaf order so that neighbouring lanes walk neighbouring paths; the k best are a
 //     sorted list in registers; the far-child stack lives in LDS with a spill area in global memory; then the
 //     neighbour mean, covariance, newmat's tred2/tql2 (evalue.cpp:24-156) on the 3x3, the flip towards the sensor.
+//     The per-lane code of the search (list, stack, the walk) is ann_lane.h, which the CPU tier compiles for the host and
+//     runs against the library's search (tests/test_ann_walk_host.py).
 //
 // All fp64, no contraction: neighbour lists and normals are bit-identical to the library's.
 #include <cfloat>
@@ -43,8 +45,6 @@ namespace tdtk {
 #define ANN_MID 2048u         // round 5: cells up to this size are taken down to ANN_SMALL-point cells by one workgroup in LDS (k_ann_mid)
 #endif
 #define ANN_ERR 0.001         // kd_split.cpp:34
-#define A_LEAF 0x20000000u    // child reference: leaf flag | position (29 bits); c0 bits 30..31 = cutting dimension
-#define A_VAL 0x1FFFFFFFu
 #define NOSEG 0xFFFFFFFFu
 #define ANN_MAX_LEVELS 4096
 
@@ -279,6 +279,50 @@ __global__ void k_ann_decide(const ASeg* __restrict__ segs, const uint32_t* __re
   dec[i] = d;
 }
 
+// The run-wise count behind k_ann_count and k_ann_part_scan<1>: a wave holds ROWS rows of 64 consecutive positions (cell sg[r],
+// NOSEG outside any cell; coordinate c[r] against the cell's cutting value cv[r]); cells are runs of positions, so per run the
+// wave sees: one ballot-and-popcount of "< cv" | "== cv" << 32 and one 64-bit atomicAdd; the workgroup's WAVES waves cover
+// adjacent ranges and merge their last runs in LDS first.  Same reduction as k_ann_measure's, which keeps per-lane partials.
+template <uint32_t ROWS, uint32_t WAVES>
+static __device__ __forceinline__ void ann_run_counts(const uint32_t (&sg)[ROWS], const double (&c)[ROWS], const double (&cv)[ROWS],
+                                                      unsigned long long* __restrict__ cnt, const uint32_t lane, const uint32_t wv)
+{
+  __shared__ uint32_t s_seg[WAVES];
+  __shared__ unsigned long long s_cnt[WAVES];
+  uint32_t pend = NOSEG;
+  unsigned long long pcnt = 0;
+#pragma unroll
+  for (uint32_t r = 0; r < ROWS; r++) {
+    const uint32_t g = sg[r];
+    const bool lt = (g != NOSEG) && (c[r] < cv[r]);
+    const bool eq = (g != NOSEG) && (c[r] == cv[r]);
+    unsigned long long todo = __ballot(g != NOSEG);
+    while (todo) {
+      const int leader = __ffsll((long long)todo) - 1;
+      const uint32_t cur = __shfl(g, leader, WAVE);
+      const bool mine = (g == cur);
+      const unsigned long long add = (unsigned long long)__popcll(__ballot(mine && lt)) | ((unsigned long long)__popcll(__ballot(mine && eq)) << 32);
+      if (cur != pend) {
+        if (pend != NOSEG && lane == 0) atomicAdd(&cnt[pend], pcnt);
+        pend = cur; pcnt = add;
+      } else pcnt += add;
+      todo &= ~__ballot(mine);
+    }
+  }
+  if (lane == 0) { s_seg[wv] = pend; s_cnt[wv] = pcnt; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t cur = NOSEG;
+    unsigned long long acc = 0;
+    for (uint32_t w = 0; w < WAVES; w++) {
+      if (s_seg[w] == NOSEG) continue;
+      if (s_seg[w] != cur) { if (cur != NOSEG) atomicAdd(&cnt[cur], acc); cur = s_seg[w]; acc = s_cnt[w]; }
+      else acc += s_cnt[w];
+    }
+    if (cur != NOSEG) atomicAdd(&cnt[cur], acc);
+  }
+}
+
 // Per cell: how many of its points lie below the cutting plane (-> br1) and how many on it (br2 = br1 + that):
 // all annPlaneSplit's breaks need, and independent of the order of the points.  Same run-wise reduction as
 // k_ann_measure; one 64-bit atomicAdd per run (low word "< cv", high word "== cv").
@@ -287,8 +331,6 @@ __global__ void __launch_bounds__(256) k_ann_count(const uint32_t* __restrict__ 
                                                    const double* __restrict__ cy, const double* __restrict__ cz,
                                                    unsigned long long* __restrict__ cnt)
 {
-  __shared__ uint32_t s_seg[4];
-  __shared__ unsigned long long s_cnt[4];
   const uint32_t lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   const uint32_t base = (blockIdx.x * 4u + wv) * (WAVE * MEAS_ITERS);
   uint32_t sgs[MEAS_ITERS];
@@ -311,41 +353,7 @@ __global__ void __launch_bounds__(256) k_ann_count(const uint32_t* __restrict__ 
     cs[it] = 0.0;
     if (sgs[it] != NOSEG) cs[it] = coord_of(cx, cy, cz, cds[it], p);
   }
-  uint32_t pend = NOSEG;
-  unsigned long long pcnt = 0;
-#pragma unroll
-  for (int it = 0; it < MEAS_ITERS; it++) {
-    const uint32_t sg = sgs[it];
-    const bool lt = (sg != NOSEG) && (cs[it] < cvs[it]);
-    const bool eq = (sg != NOSEG) && (cs[it] <= cvs[it]) && !lt;
-    unsigned long long todo = __ballot(sg != NOSEG);
-    while (todo) {
-      const int leader = __ffsll((long long)todo) - 1;
-      const uint32_t cur = __shfl(sg, leader, WAVE);
-      const bool mine = (sg == cur);
-      const unsigned long long add = (unsigned long long)__popcll(__ballot(mine && lt)) |
-                                     ((unsigned long long)__popcll(__ballot(mine && eq)) << 32);
-      if (cur != pend) {
-        if (pend != NOSEG && lane == 0) atomicAdd(&cnt[pend], pcnt);
-        pend = cur; pcnt = add;
-      } else pcnt += add;
-      todo &= ~__ballot(mine);
-    }
-  }
-  if (lane == 0) { s_seg[wv] = pend; s_cnt[wv] = pcnt; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t cur = NOSEG;
-    unsigned long long acc = 0;
-    for (int w = 0; w < 4; w++) {
-      if (s_seg[w] == NOSEG) continue;
-      if (s_seg[w] != cur) {
-        if (cur != NOSEG) atomicAdd(&cnt[cur], acc);
-        cur = s_seg[w]; acc = s_cnt[w];
-      } else acc += s_cnt[w];
-    }
-    if (cur != NOSEG) atomicAdd(&cnt[cur], acc);
-  }
+  ann_run_counts<MEAS_ITERS, 4>(sgs, cs, cvs, cnt, lane, wv);
 }
 
 // pass 1: "< cv" belongs left of br1.  pass 2 (positions >= br1 only): "<= cv", i.e. "== cv", belongs left of br2
@@ -477,40 +485,7 @@ __global__ void __launch_bounds__(PS_THREADS) k_ann_part_scan(const uint32_t* __
     if (PASS == 1) {
       // the cell's counts on the way (what k_ann_count's own pass over the points did): points below the cutting value |
       // points ON it << 32, one atomic per run a wave sees, the workgroup's waves merged first
-      __shared__ uint32_t s_cseg[PS_THREADS / WAVE];
-      __shared__ unsigned long long s_ccnt[PS_THREADS / WAVE];
-      uint32_t pend = NOSEG;
-      unsigned long long pcnt = 0;
-#pragma unroll
-      for (uint32_t r = 0; r < PS_ROWS; r++) {
-        const uint32_t g = sg[r];
-        const bool lt = (g != NOSEG) && (c[r] < cvs[r]);
-        const bool eq = (g != NOSEG) && (c[r] == cvs[r]);
-        unsigned long long todo = __ballot(g != NOSEG);
-        while (todo) {
-          const int leader = __ffsll((long long)todo) - 1;
-          const uint32_t cur = __shfl(g, leader, WAVE);
-          const bool mine = (g == cur);
-          const unsigned long long add = (unsigned long long)__popcll(__ballot(mine && lt)) | ((unsigned long long)__popcll(__ballot(mine && eq)) << 32);
-          if (cur != pend) {
-            if (pend != NOSEG && lane == 0) atomicAdd(&cnt[pend], pcnt);
-            pend = cur; pcnt = add;
-          } else pcnt += add;
-          todo &= ~__ballot(mine);
-        }
-      }
-      if (lane == 0) { s_cseg[wv] = pend; s_ccnt[wv] = pcnt; }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        uint32_t cur = NOSEG;
-        unsigned long long acc = 0;
-        for (uint32_t w = 0; w < PS_THREADS / WAVE; w++) {
-          if (s_cseg[w] == NOSEG) continue;
-          if (s_cseg[w] != cur) { if (cur != NOSEG) atomicAdd(&cnt[cur], acc); cur = s_cseg[w]; acc = s_ccnt[w]; }
-          else acc += s_ccnt[w];
-        }
-        if (cur != NOSEG) atomicAdd(&cnt[cur], acc);
-      }
+      ann_run_counts<PS_ROWS, PS_THREADS / WAVE>(sg, c, cvs, cnt, lane, wv);
     }
   }
   uint32_t ext = 0u, win = 0u;
@@ -1212,27 +1187,20 @@ AnnBuildResult ann_build_tree(const double* d_xyz, size_t M_, void* arena_, AnnN
       if (!part2_level) hipLaunchKernelGGL(k_ann_count, dim3(cdiv(M, 256 * MEAS_ITERS)), dim3(256), 0, s, seg_of, M, dec, cx, cy, cz, cnt);
       // the library's first Hoare pass, then its second one on what lies right of br1
       for (int pass = 1; pass <= 2; pass++) {
+        const uint32_t* const gate = (pass == 2) ? flag : nullptr;
         if (part2_level) {      // (lab, TDTK_ANN_PART=0: round 3's four launches)
           // a Hoare pass = a scan that writes the index list + the swaps
           const uint32_t ntiles = cdiv(M, PS_TILE), nbw = cdiv(M, 256u * APW_ROWS);
           uint32_t* counter = reinterpret_cast<uint32_t*>(scan_state);
           unsigned long long* status = reinterpret_cast<unsigned long long*>(scan_state + 64);
-          if (pass == 1) {
-            hipLaunchKernelGGL(k_ann_part_scan<1>, dim3(ntiles), dim3(PS_THREADS), 0, s, seg_of, segs, dec, cnt, cx, cy, cz, M, posL, status, counter,
-                               2u * level + 1u, ntiles, small + 2, flag);
-            hipLaunchKernelGGL(k_ann_part_swap<1>, dim3(nbw), dim3(256), 0, s, posL, seg_of, segs, cnt, M, perm, cx, cy, cz, (const uint32_t*)nullptr);
-          } else {
-            hipLaunchKernelGGL(k_ann_part_scan<2>, dim3(ntiles), dim3(PS_THREADS), 0, s, seg_of, segs, dec, cnt, cx, cy, cz, M, posL, status, counter,
-                               2u * level + 2u, ntiles, small + 2, flag);
-            hipLaunchKernelGGL(k_ann_part_swap<2>, dim3(nbw), dim3(256), 0, s, posL, seg_of, segs, cnt, M, perm, cx, cy, cz, (const uint32_t*)flag);
-          }
+          hipLaunchKernelGGL(pass == 1 ? k_ann_part_scan<1> : k_ann_part_scan<2>, dim3(ntiles), dim3(PS_THREADS), 0, s, seg_of, segs, dec, cnt, cx, cy,
+                             cz, M, posL, status, counter, 2u * level + (uint32_t)pass, ntiles, small + 2, flag);
+          hipLaunchKernelGGL(pass == 1 ? k_ann_part_swap<1> : k_ann_part_swap<2>, dim3(nbw), dim3(256), 0, s, posL, seg_of, segs, cnt, M, perm, cx,
+                             cy, cz, gate);
           continue;
         }
-        const uint32_t* const gate = (pass == 2) ? flag : nullptr;
-        if (pass == 1)
-          hipLaunchKernelGGL(k_ann_misplaced<1>, dim3(cdiv(n1, 256)), dim3(256), 0, s, seg_of, segs, dec, cnt, cx, cy, cz, M, LR, flag);
-        else
-          hipLaunchKernelGGL(k_ann_misplaced<2>, dim3(cdiv(n1, 256)), dim3(256), 0, s, seg_of, segs, dec, cnt, cx, cy, cz, M, LR, flag);
+        hipLaunchKernelGGL(pass == 1 ? k_ann_misplaced<1> : k_ann_misplaced<2>, dim3(cdiv(n1, 256)), dim3(256), 0, s, seg_of, segs, dec, cnt, cx, cy,
+                           cz, M, LR, flag);
         if (one_launch) {
           ACHK(launch_scan_pair27(LR, AB, n1, scan_state, 2u * level + (uint32_t)pass, small + 2, s, gate));
         } else {
@@ -1292,97 +1260,41 @@ AnnBuildResult ann_build_tree(const double* d_xyz, size_t M_, void* arena_, AnnN
 }
 
 // ---- search + PCA -------------------------------------------------------------------------------
-#define ANN_LDS_STACK 12   // far-child entries per thread kept in LDS; deeper ones spill to global memory
-
+// (the per-lane code -- list, far-child stack, the walk -- is ann_lane.h)
+//
 // One thread per scan point (grid-stride over leaf positions).  KMAX >= k; the list keeps KMAX - k sentinels
 // (key -1) in front so that every register index is static.
 // COUNT: also tally the splitting nodes and leaf points every query visits (cnt[0], cnt[1]) -- the instrumented
 // instantiation bench.py takes the algorithmic bytes of the launch from.
 template <int KMAX, bool COUNT>
-__global__ void __launch_bounds__(256) k_ann_normals(const AnnNode* __restrict__ nodes, uint32_t root_ref,
-                                                     const KdPoint* __restrict__ pts, uint32_t n, int k,
-                                                     double max_err, const double* __restrict__ bb, double rx,
-                                                     double ry, double rz, uint32_t* __restrict__ spill_ref,
-                                                     double* __restrict__ spill_bd, uint32_t spill_depth,
-                                                     double* __restrict__ normals, int32_t* __restrict__ knn_out,
-                                                     unsigned long long* __restrict__ cnt)
+__global__ void __launch_bounds__(ANN_BLOCK) k_ann_normals(const AnnNode* __restrict__ nodes, uint32_t root_ref,
+                                                           const KdPoint* __restrict__ pts, uint32_t n, int k,
+                                                           double max_err, const double* __restrict__ bb, double rx,
+                                                           double ry, double rz, uint32_t* __restrict__ spill_ref,
+                                                           double* __restrict__ spill_bd, uint32_t spill_depth,
+                                                           double* __restrict__ normals, int32_t* __restrict__ knn_out,
+                                                           unsigned long long* __restrict__ cnt)
 {
   unsigned c_split = 0, c_leaf = 0;
-  __shared__ uint32_t s_ref[ANN_LDS_STACK][256];
-  __shared__ double s_bd[ANN_LDS_STACK][256];
-  const uint32_t T = gridDim.x * blockDim.x, tid = blockIdx.x * blockDim.x + threadIdx.x, tx = threadIdx.x;
+  __shared__ uint32_t s_ref[ANN_LDS_STACK][ANN_BLOCK];
+  __shared__ double s_bd[ANN_LDS_STACK][ANN_BLOCK];
+  AnnStack st{s_ref, s_bd, spill_ref, spill_bd, gridDim.x * blockDim.x, blockIdx.x * blockDim.x + threadIdx.x, threadIdx.x, 0};
   (void)spill_depth;
   const double blo[3] = {bb[0], bb[1], bb[2]}, bhi[3] = {bb[3], bb[4], bb[5]};
-  for (uint32_t qi = tid; qi < n; qi += T) {
+  for (uint32_t qi = st.tid; qi < n; qi += st.T) {
     const KdPoint qp = pts[qi];
-    const double q[3] = {qp.x, qp.y, qp.z};
     double key[KMAX];
     uint32_t info[KMAX];
-#pragma unroll
-    for (int j = 0; j < KMAX; j++) { key[j] = (j < KMAX - k) ? -1.0 : DBL_MAX; info[j] = 0xFFFFFFFFu; }
-    // annBoxDistance (kd_util.cpp:127-150)
-    double bd = 0.0;
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      if (q[d] < blo[d]) { const double t = blo[d] - q[d]; bd = bd + t * t; }
-      else if (q[d] > bhi[d]) { const double t = q[d] - bhi[d]; bd = bd + t * t; }
-    }
-    uint32_t cur = root_ref;
-    int sp = 0;
-    for (;;) {
-      while (!(cur & A_LEAF)) {                      // ANNkd_split::ann_search (kd_search.cpp:128-170)
-        if (COUNT) ++c_split;
-        const AnnNode nd = nodes[cur & A_VAL];
-        const uint32_t cd = nd.c0 >> 30;
-        const double qd = (cd == 0) ? q[0] : ((cd == 1) ? q[1] : q[2]);
-        const double cut_diff = qd - nd.cut_val;
-        const bool low = cut_diff < 0;
-        double box_diff = low ? (nd.lo - qd) : (qd - nd.hi);
-        if (box_diff < 0) box_diff = 0;
-        const double fbd = bd + (cut_diff * cut_diff - box_diff * box_diff);
-        const uint32_t c0 = nd.c0 & (A_LEAF | A_VAL), c1 = nd.c1;
-        const uint32_t far = low ? c1 : c0;
-        // the reference tests "box_dist * max_err < max_key()" after the near subtree; the k-th key only ever
-        // shrinks, so a far child failing now fails then too and need not be remembered
-        if (fbd * max_err < key[KMAX - 1]) {
-          if (sp < ANN_LDS_STACK) { s_ref[sp][tx] = far; s_bd[sp][tx] = fbd; }
-          else { spill_ref[(size_t)(sp - ANN_LDS_STACK) * T + tid] = far; spill_bd[(size_t)(sp - ANN_LDS_STACK) * T + tid] = fbd; }
-          sp++;
-        }
-        cur = low ? c0 : c1;
-      }
-      {                                              // ANNkd_leaf::ann_search, one point (kd_search.cpp:177-210)
-        const uint32_t pos = cur & A_VAL;
-        if (COUNT) ++c_leaf;
-        const KdPoint p = pts[pos];
-        const double t0 = q[0] - p.x, t1 = q[1] - p.y, t2 = q[2] - p.z;
-        const double dist = (t0 * t0 + t1 * t1) + t2 * t2;
-        if (!(dist > key[KMAX - 1])) {               // no partial sum exceeded the k-th key
-          // ANNmin_k::insert (pr_queue_k.h:100-114): behind every key <= dist, the last one drops out
-          double ck = dist;
-          uint32_t ci = pos;
-          bool shifting = false;
-#pragma unroll
-          for (int j = 0; j < KMAX; j++) {
-            shifting = shifting || (key[j] > ck);
-            if (shifting) {
-              const double tk = key[j]; key[j] = ck; ck = tk;
-              const uint32_t ti = info[j]; info[j] = ci; ci = ti;
-            }
-          }
-        }
-      }
-      bool done = false;
-      for (;;) {
-        if (sp == 0) { done = true; break; }
-        sp--;
-        if (sp < ANN_LDS_STACK) { cur = s_ref[sp][tx]; bd = s_bd[sp][tx]; }
-        else { cur = spill_ref[(size_t)(sp - ANN_LDS_STACK) * T + tid]; bd = spill_bd[(size_t)(sp - ANN_LDS_STACK) * T + tid]; }
-        if (bd * max_err < key[KMAX - 1]) break;
-      }
-      if (done) break;
-    }
+    ann_list_init(key, info, KMAX - k);
+    ann_search<KMAX, COUNT>(nodes, pts, root_ref, qp.x, qp.y, qp.z, ann_box_distance(qp.x, qp.y, qp.z, blo, bhi), max_err, key,
+                            info, st, c_split, c_leaf);
     // ---- normals.cc:64-105 ----
+    // The mean and covariance are list_cov's arithmetic (query_lane.h), here and in k_ann_adaptive, kept as copies because of
+    // what the compiler makes of list_cov over a lambda that walks the live slots: k_ann_normals<10> 109 / 112 VGPRs for 93 /
+    // 96, k_ann_normals<16, true> 170 VGPRs and two waves per SIMD for three, k_ann_adaptive 146 / 170 / 234 VGPRs for 120 /
+    // 144 / 208 and a wave per SIMD less at KMAX 10 and 16 (the closure holds the list's address, and the list is then no
+    // longer kept as a vector value: ann_lane.h).  One function of their own over a slot predicate, the list by reference,
+    // keeps k_ann_normals within its bounds but takes the same waves from k_ann_adaptive (138 / 170 / 234 VGPRs).
     double mean[3] = {0.0, 0.0, 0.0};
 #pragma unroll
     for (int j = 0; j < KMAX; j++)
@@ -1405,7 +1317,7 @@ __global__ void __launch_bounds__(256) k_ann_normals(const AnnNode* __restrict__
 #pragma unroll
           for (int c = 0; c <= r; c++) z[r][c] += (sc * x[c]) * x[r];
       }
-    normal_from_cov(z, q[0], q[1], q[2], rx, ry, rz, normals + 3 * (size_t)qp.orig);
+    normal_from_cov(z, qp.x, qp.y, qp.z, rx, ry, rz, normals + 3 * (size_t)qp.orig);
   }
   if (COUNT && cnt) {
     unsigned long long a = c_split, b = c_leaf;
@@ -1422,27 +1334,21 @@ __global__ void __launch_bounds__(256) k_ann_normals(const AnnNode* __restrict__
 // are formed in vector registers at that place instead of being kept as lane masks across the search.
 // normals [n][3], k_used [n] (nullable), knn_out [n][kmax + 1] (nullable, -1 behind the chosen list), caller order.
 template <int KMAX>
-__global__ void __launch_bounds__(256) k_ann_adaptive(const AnnNode* __restrict__ nodes, uint32_t root_ref,
-                                                      const KdPoint* __restrict__ pts, uint32_t n, int kmin, int kmax,
-                                                      double max_err, const double* __restrict__ bb, double rx, double ry,
-                                                      double rz, uint32_t* __restrict__ spill_ref,
-                                                      double* __restrict__ spill_bd, double* __restrict__ normals,
-                                                      int32_t* __restrict__ k_used, int32_t* __restrict__ knn_out)
+__global__ void __launch_bounds__(ANN_BLOCK) k_ann_adaptive(const AnnNode* __restrict__ nodes, uint32_t root_ref,
+                                                            const KdPoint* __restrict__ pts, uint32_t n, int kmin, int kmax,
+                                                            double max_err, const double* __restrict__ bb, double rx, double ry,
+                                                            double rz, uint32_t* __restrict__ spill_ref,
+                                                            double* __restrict__ spill_bd, double* __restrict__ normals,
+                                                            int32_t* __restrict__ k_used, int32_t* __restrict__ knn_out)
 {
-  __shared__ uint32_t s_ref[ANN_LDS_STACK][256];
-  __shared__ double s_bd[ANN_LDS_STACK][256];
-  const uint32_t T = gridDim.x * blockDim.x, tid = blockIdx.x * blockDim.x + threadIdx.x, tx = threadIdx.x;
+  __shared__ uint32_t s_ref[ANN_LDS_STACK][ANN_BLOCK];
+  __shared__ double s_bd[ANN_LDS_STACK][ANN_BLOCK];
+  AnnStack st{s_ref, s_bd, spill_ref, spill_bd, gridDim.x * blockDim.x, blockIdx.x * blockDim.x + threadIdx.x, threadIdx.x, 0};
+  unsigned unused = 0;
   const double blo[3] = {bb[0], bb[1], bb[2]}, bhi[3] = {bb[3], bb[4], bb[5]};
-  for (uint32_t qi = tid; qi < n; qi += T) {
+  for (uint32_t qi = st.tid; qi < n; qi += st.T) {
     const KdPoint qp = pts[qi];
-    const double q[3] = {qp.x, qp.y, qp.z};
-    // annBoxDistance (kd_util.cpp:127-150)
-    double bd0 = 0.0;
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-      if (q[d] < blo[d]) { const double t = blo[d] - q[d]; bd0 = bd0 + t * t; }
-      else if (q[d] > bhi[d]) { const double t = q[d] - bhi[d]; bd0 = bd0 + t * t; }
-    }
+    const double bd0 = ann_box_distance(qp.x, qp.y, qp.z, blo, bhi);
     double key[KMAX];
     uint32_t info[KMAX];
     double z[3][3], D[3];
@@ -1451,60 +1357,8 @@ __global__ void __launch_bounds__(256) k_ann_adaptive(const AnnNode* __restrict_
       const int k = kidx + 1;
       k0 = KMAX - k;
       asm volatile("" : "+v"(k0));
-#pragma unroll
-      for (int j = 0; j < KMAX; j++) { key[j] = (j < k0) ? -1.0 : DBL_MAX; info[j] = 0xFFFFFFFFu; }
-      double bd = bd0;
-      uint32_t cur = root_ref;
-      int sp = 0;
-      for (;;) {
-        while (!(cur & A_LEAF)) {                      // ANNkd_split::ann_search (kd_search.cpp:128-170)
-          const AnnNode nd = nodes[cur & A_VAL];
-          const uint32_t cd = nd.c0 >> 30;
-          const double qd = (cd == 0) ? q[0] : ((cd == 1) ? q[1] : q[2]);
-          const double cut_diff = qd - nd.cut_val;
-          const bool low = cut_diff < 0;
-          double box_diff = low ? (nd.lo - qd) : (qd - nd.hi);
-          if (box_diff < 0) box_diff = 0;
-          const double fbd = bd + (cut_diff * cut_diff - box_diff * box_diff);
-          const uint32_t c0 = nd.c0 & (A_LEAF | A_VAL), c1 = nd.c1;
-          const uint32_t far = low ? c1 : c0;
-          if (fbd * max_err < key[KMAX - 1]) {         // (as k_ann_normals: the k-th key only ever shrinks)
-            if (sp < ANN_LDS_STACK) { s_ref[sp][tx] = far; s_bd[sp][tx] = fbd; }
-            else { spill_ref[(size_t)(sp - ANN_LDS_STACK) * T + tid] = far; spill_bd[(size_t)(sp - ANN_LDS_STACK) * T + tid] = fbd; }
-            sp++;
-          }
-          cur = low ? c0 : c1;
-        }
-        {                                              // ANNkd_leaf::ann_search, one point (kd_search.cpp:177-210)
-          const uint32_t pos = cur & A_VAL;
-          const KdPoint p = pts[pos];
-          const double t0 = q[0] - p.x, t1 = q[1] - p.y, t2 = q[2] - p.z;
-          const double dist = (t0 * t0 + t1 * t1) + t2 * t2;
-          if (!(dist > key[KMAX - 1])) {
-            // ANNmin_k::insert (pr_queue_k.h:100-114): behind every key <= dist, the last one drops out
-            double ck = dist;
-            uint32_t ci = pos;
-            bool shifting = false;
-#pragma unroll
-            for (int j = 0; j < KMAX; j++) {
-              shifting = shifting || (key[j] > ck);
-              if (shifting) {
-                const double tk = key[j]; key[j] = ck; ck = tk;
-                const uint32_t ti = info[j]; info[j] = ci; ci = ti;
-              }
-            }
-          }
-        }
-        bool done = false;
-        for (;;) {
-          if (sp == 0) { done = true; break; }
-          sp--;
-          if (sp < ANN_LDS_STACK) { cur = s_ref[sp][tx]; bd = s_bd[sp][tx]; }
-          else { cur = spill_ref[(size_t)(sp - ANN_LDS_STACK) * T + tid]; bd = spill_bd[(size_t)(sp - ANN_LDS_STACK) * T + tid]; }
-          if (bd * max_err < key[KMAX - 1]) break;
-        }
-        if (done) break;
-      }
+      ann_list_init(key, info, k0);
+      ann_search<KMAX, false>(nodes, pts, root_ref, qp.x, qp.y, qp.z, bd0, max_err, key, info, st, unused, unused);
       // ---- normals.cc:154-182 ----
       double mean[3] = {0.0, 0.0, 0.0};
 #pragma unroll
@@ -1539,7 +1393,7 @@ __global__ void __launch_bounds__(256) k_ann_adaptive(const AnnNode* __restrict_
       if (adaptive_k_accepts(D) || kidx >= kmax) break;
       ++kidx;
     }
-    orient_normal(z[0][0], z[1][0], z[2][0], q[0], q[1], q[2], rx, ry, rz, normals + 3 * (size_t)qp.orig);
+    orient_normal(z[0][0], z[1][0], z[2][0], qp.x, qp.y, qp.z, rx, ry, rz, normals + 3 * (size_t)qp.orig);
     if (k_used) k_used[qp.orig] = kidx;
     if (knn_out) {
       int32_t* row = knn_out + (size_t)qp.orig * (size_t)(kmax + 1);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "tdtk_internal.h"
+#include "ann_lane.h"   // AnnNode
 
 namespace tdtk {
 
@@ -288,10 +289,6 @@ DevBuildResult device_build_tree(const double* d_xyz, size_t M, int bucket, void
                                  const BuildSide* side = nullptr, int no_finish = 0);
 
 // ---- normals: the ANN kd-tree (one point per leaf, sliding midpoint) + approximate k-NN + PCA (ann.hip) -------
-struct AnnNode {          // 32 B: one splitting node (ANNkd_split: cut_val, cd_bnds[2], child[2], cut_dim)
-  double cut_val, lo, hi;
-  uint32_t c0, c1;        // child references: bit 29 = leaf, bits 0..28 = node index / point position; c0 bits 30..31 = cut_dim
-};
 struct AnnBuildResult {
   hipError_t err;
   bool degenerate;

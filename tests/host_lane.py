@@ -1,5 +1,5 @@
-"""Compiles a driver for the per-lane device code (3dtk_amd/csrc/query_lane.h under tests/host_lane_shim.h) for the host and
-loads it: the CPU-tier tests that execute the device walks on kd_build.cpp's host tree."""
+"""Compiles a driver for the per-lane device code (3dtk_amd/csrc/query_lane.h and ann_lane.h under tests/host_lane_shim.h) for
+the host and loads it: the CPU-tier tests that execute the device walks on kd_build.cpp's host tree, or on the oracle's ANN tree."""
 import ctypes as C
 import os
 import subprocess
